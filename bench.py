@@ -24,21 +24,31 @@ The steps themselves live in cuda-fft-convolution_amd/multi_gpu.py (shared with 
 
 Untimed set-up and warm-up: the headline runs on DEFAULT plan options (round 5).  The library's default for plan option tune_placement is
 automatic: a plan whose launches write >= 2 GiB of maps on a mostly free device times five candidate allocations of its intermediate at its
-first convolve (~100 ms, inside the warm-up); the other policy runs beside it as `value_untuned_placement` / `value_tuned_placement`; the W warm-up
+first convolve (~100 ms, inside the warm-up); with --full the other policy runs beside it as `value_untuned_placement` / `value_tuned_placement`; the W warm-up
 steps are followed by more untimed steps where they are shorter than the ~40 ms the GPU's clocks
 need to settle after an idle gap (config.clock_warm_steps).  The timed region is exactly K steps.
 
-Order of a run (round 4): set-up -> `cpu_baseline` (CPU only, rank 0 at N = 1) -> W warm-up steps + >= 1 s of settled
-load (`--settle-s`) -> the K timed steps -> checks -> untimed extra passes (`host_output`: the MEX-faithful host-in /
-host-out entry, one-shot and reused plan; `multi_feature`: F > 1, the reference's sumAlongFeatures case; `vendor_fft_baseline`: the
-reference's loop ported straight onto the vendor FFT library of the same GPU -- rocFFT through torch.fft -- a baseline like cpu_baseline).  The timed
-step contains the upload of the step's kernels from pinned host memory (double-buffered on an upload
-stream: multi_gpu.HipPlanEngine); `value_kernels_resident` is the same K steps with the kernels kept in HBM.
+Order of a plain run: set-up -> W warm-up steps + >= 1 s of settled load (`--settle-s`) -> the K timed steps ->
+`--dump-outputs DIR` (if given) -> the result line.  The timed step contains the upload of the step's kernels from pinned
+host memory (double-buffered on an upload stream: multi_gpu.HipPlanEngine).
 
-Prints ONE JSON line on rank 0 (contract in the task description) with `roofline` (dominant
-kernel, algorithmic bytes / its HIP-event time over the launches of the timed region itself), `cpu_baseline` (the CPU oracle timed on this
-host on a bounded sample, rank 0 at N = 1 only) and `check_max_rel_err` (every map's checksum on
-the device + the oracle's maps where they were computed); a failed check exits non-zero.
+`--full` adds everything the headline does not need (round 4's order): `cpu_baseline` (CPU only, rank 0 at N = 1) before the
+warm-up; HIP-event timing of the two hot kernels inside the timed region; after it the checks, a separate per-kernel
+profiling pass and untimed extra passes (`value_kernels_resident`: the same K steps with the kernels kept in HBM; the other
+placement policy; `host_output`: the MEX-faithful host-in / host-out entry, one-shot and reused plan; `multi_feature`: F > 1,
+the reference's sumAlongFeatures case; `vendor_fft_baseline`: the reference's loop ported straight onto the vendor FFT library
+of the same GPU -- rocFFT through torch.fft -- a baseline like cpu_baseline).  The `--no-*` options still opt out of parts of it.
+
+Prints ONE JSON line on rank 0 (contract in the task description): `value` and `ms_per_step` of the K timed steps.  With
+`--full` it also carries `roofline` (dominant kernel, algorithmic bytes / its HIP-event time over the launches of the timed
+region itself), `kernels`, `cpu_baseline` (the CPU oracle timed on this host on a bounded sample, rank 0 at N = 1 only) and
+`check_max_rel_err` (every map's checksum on the device + the oracle's maps where they were computed); `--check` alone runs
+the checks too.  A failed check exits non-zero.
+
+`--dump-outputs DIR` writes what the last timed step left in the maps, the arrays a caller of the device-resident path
+receives ([maps][fft_w][fft_h], float32): `maps.npy` whole where they are small, otherwise `maps_sample.npy` at the fixed,
+seeded flat positions of `maps_sample_index.npy` (float64); and `map_sums.npy`, every map's float64 sum.  At N > 1 each rank
+writes its own maps, with a `_rank<r>` suffix.  Inputs are seeded, so runs with the same arguments compare output for output.
 """
 import argparse
 import json
@@ -71,6 +81,9 @@ CHECK_TOL_ORACLE = 1e-4   # north_star parity bar (max|out - ref| / max|ref| per
 CHECK_TOL_CHECKSUM = 1e-5  # sum(map) vs sum(image) * sum(kernel), relative
 CLOCK_WARM_S = 1.0        # untimed load before the timed region (--settle-s): the clock ramp after idle is ~40 ms, and a sampler
                           # of GPU utilisation outside this process needs about a second of continuous load to see the run
+DUMP_WHOLE_MAX = 1 << 23  # --dump-outputs: maps of up to this many elements in all (32 MB of float32) are written whole ...
+DUMP_SAMPLE = 1 << 21     # ... larger ones as this many positions (8 MB of values + 16 MB of float64 positions), split over the ranks
+DUMP_SEED = 20240611      # seed of the sampled positions: the same for every run of the same arguments
 
 
 def ceil16(n):
@@ -427,6 +440,26 @@ def multi_feature_figures(fc, util, np, torch, dev, steps, cases=(("cfg3f4", 409
     return res
 
 
+def output_sample(torch, np, maps, world):
+    """--dump-outputs: host copies of what the timed steps left in `maps` ([n][fft_w][fft_h] on the device) -- every map's
+    float64 sum, and the maps themselves: whole up to DUMP_WHOLE_MAX elements over all ranks, else a fixed, seeded sample."""
+    res = {"map_sums": maps.sum(dim=(1, 2), dtype=torch.float64).cpu().numpy()}
+    total = maps.numel()
+    if total <= DUMP_WHOLE_MAX // world:
+        res["maps"] = maps.cpu().numpy()
+    else:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, total, DUMP_SAMPLE // world, dtype=np.int64))
+        res["maps_sample"] = maps.reshape(-1)[torch.from_numpy(idx).to(maps.device)].cpu().numpy()
+        res["maps_sample_index"] = idx.astype(np.float64)
+    return res
+
+
+def write_outputs(np, arrays, out_dir, suffix=""):
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+
+
 def library_sha256(fc):
     import hashlib
     try:
@@ -541,13 +574,14 @@ def main():
                          "tune_placement).  -1 = the library's default = the headline's: automatic (five candidates where a launch writes "
                          ">= 2 GiB of maps and the device is mostly free); 0 = never.  Where a launch covers >= 5e8 padded pixels the line "
                          "carries the other policy beside it: `value_untuned_placement` (a second plan with tune_placement = 0) beside a "
-                         "plan that tuned, `value_tuned_placement` (5 candidates) beside one that did not")
+                         "plan that tuned, `value_tuned_placement` (5 candidates) beside one that did not (--full)")
     ap.add_argument("--rows-group", type=int, default=0, help="maps per workgroup of the spectral-row kernel (0 = auto)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample", type=int, default=0,
                     help="filters (= threads) of the CPU baseline sample; 0 = one per usable core, capped by the filter count and by memory")
     ap.add_argument("--check", action="store_true",
-                    help="also verify three maps of every rank against the oracle (the cheap all-maps checksum always runs)")
+                    help="verify three maps of every rank against the oracle, and every map's checksum (the checksum also "
+                         "runs with --full)")
     ap.add_argument("--images", type=int, default=0,
                     help="streamed mode (BASELINE configs[4]): this many images in total, dealt over the ranks; per rank "
                          "every image against all kernels, the next image's H2D copy (pinned host memory, side "
@@ -588,7 +622,15 @@ def main():
                          "timed steps -- a stand-in for a collective's channels co-resident with the step (single GPU)")
     ap.add_argument("--force-collective", action="store_true",
                     help="run the broadcast code path even with one rank (self-test of the N > 1 step on a 1-GPU box)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: cpu_baseline, checks, per-kernel figures and roofline, the untimed "
+                         "extra passes (the --no-* options still skip parts of it).  Off: set-up, warm-up, the K timed steps only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (a fixed, seeded sample "
+                         "of large maps, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -747,9 +789,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
-    # the CPU baseline FIRST (CPU only, ~15 s): the GPU phases then run in one piece at the end of the process
+    # the CPU baseline FIRST (CPU only, ~15 s; --full): the GPU phases then run in one piece at the end of the process
     cpu = cpu_ref = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu, cpu_ref = cpu_baseline(cfg, args.cpu_sample)
 
     run_steps(args.warmup)
@@ -797,9 +839,9 @@ def main():
     # here; their figures come from the separate pass below)
     # ... where a hot launch is long enough not to feel them: a pair costs ~5-20 us of stream time, which
     # is 5 % of a cfg5 launch and most of a cfg1 step (profiles/r02w_live_event_cost.txt), so launches under
-    # 5e8 padded pixels (< ~0.7 ms) are timed in the separate pass only
+    # 5e8 padded pixels (< ~0.7 ms) are timed in the separate pass only.  A plain run (no --full) records no events.
     per_launch_px = min(args.batch_maps or 64, max(nf, 1)) * P
-    live_profile = graph is None and not args.no_live_profile and per_launch_px >= 5e8
+    live_profile = args.full and graph is None and not args.no_live_profile and per_launch_px >= 5e8
     if live_profile:
         plan.set_option("profile_kinds", (1 << 1) | (1 << 2))   # indices of fftconv_profile: spectral_rows, cols_c2r
         plan.set_option("profile", 1)
@@ -859,13 +901,19 @@ def main():
         per_rank = [None] * world
         dist.all_gather_object(per_rank, mine)
 
-    # self-check of what the timed steps left in `out` (every map of this rank, on the device):
+    # what the last timed step left in `out`, copied out before anything else runs on the maps
+    dumped = None
+    if args.dump_outputs and nf and (not streamed or n_img):
+        dumped = output_sample(torch, np, out[:nf], world)
+
+    # self-check of what the timed steps left in `out` (every map of this rank, on the device; --full or --check):
     # the sum over the whole window of a linear convolution is sum(image) * sum(kernel)
+    checked = args.full or args.check
     chk_img = img_d
     if streamed and n_img:
         chk_img = conv.buf[conv.last_buf]         # the maps in `out` belong to the image convolved last
     check = {"checksum_max_rel_err": 0.0}
-    if nf and (not streamed or n_img):
+    if checked and nf and (not streamed or n_img):
         s_img = chk_img.sum(dim=(1, 2), dtype=torch.float64)                        # [F]
         s_ker = kern_d.sum(dim=(2, 3), dtype=torch.float64)                         # [n][F]
         want = (s_ker * s_img[None, :]).sum(dim=1)
@@ -877,22 +925,24 @@ def main():
 
     # HIP-event timing of EVERY kernel of the same steps, on the plan's stream, in a separate pass (so that the
     # one-off passes carry no event records inside the headline timing).  The check above left the GPU idle
-    # and the clocks take ~40 ms of load to settle again (tools/clock_ramp.py): a few unobserved steps first
-    n_sep = max(1, min(args.steps, 3))
-    run_steps(max(1, min(200, int(0.06 / max(dt / args.steps, 1e-6)) + 1)))   # same count on every rank (dt is the max over ranks)
-    plan.set_option("profile", 1)
-    plan.profile(reset=True)
-    run_steps(n_sep)
-    torch.cuda.synchronize(dev)
-    prof = plan.profile(reset=True)
-    plan.set_option("profile", 0)
+    # and the clocks take ~40 ms of load to settle again (tools/clock_ramp.py): a few unobserved steps first (--full)
+    prof = None
+    if args.full:
+        n_sep = max(1, min(args.steps, 3))
+        run_steps(max(1, min(200, int(0.06 / max(dt / args.steps, 1e-6)) + 1)))   # same count on every rank (dt is the max over ranks)
+        plan.set_option("profile", 1)
+        plan.profile(reset=True)
+        run_steps(n_sep)
+        torch.cuda.synchronize(dev)
+        prof = plan.profile(reset=True)
+        plan.set_option("profile", 0)
 
-    # Extra, untimed-for-the-headline passes (N = 1, plain steps only):
+    # Extra, untimed-for-the-headline passes (--full; N = 1, plain steps only):
     #  * the same K steps with the kernels uploaded from (pinned) host memory inside every step -- SURVEY 8(d) counts
     #    the kernel H2D (63 KB each) in the timed region; the headline keeps the kernels resident as the maps are;
     #  * the same K steps on a second plan with DEFAULT options (no placement tuning) writing into the same maps.
     extras = {}
-    if world == 1 and not use_dist and not streamed and graph is None and not args.no_extras and nf:
+    if args.full and world == 1 and not use_dist and not streamed and graph is None and not args.no_extras and nf:
         def timed(fn, k):
             fn(max(1, min(k, 3)))
             torch.cuda.synchronize(dev)
@@ -955,7 +1005,7 @@ def main():
         for j, r in enumerate(cpu_ref[:nf]):
             errs.append(util.rel_err(out[j].cpu().numpy().T, r))
     oracle_err = max(errs) if errs else None
-    if use_dist:
+    if use_dist and checked:
         tt = torch.tensor([check["checksum_max_rel_err"], oracle_err if oracle_err is not None else -1.0],
                           dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -966,7 +1016,7 @@ def main():
     if rank == 0:
         ab = alg_bytes(H, W, F, kh, kw)
         per = {}
-        for name in ("spectral_rows", "cols_c2r"):
+        for name in ("spectral_rows", "cols_c2r") if prof else ():
             p = prof[name]
             if p["launches"]:
                 avg_ms = p["ms"] / p["launches"]
@@ -1043,12 +1093,14 @@ def main():
             # row kernel re-uses the image-spectrum row from registers, so this is BELOW the algorithmic figure
             "hbm_physical_gbps": (physical_per_map * total_maps * args.steps / dt / 1e9) if physical_per_map else None,
             "hbm_physical_frac": (physical_per_map * total_maps * args.steps / dt / 1e9 / (HBM_PEAK_GBPS * world)) if physical_per_map else None,
-            "kernels": per,
-            "image_ms": (prof["image_cols"]["ms"] + prof["image_rows"]["ms"]) / max(1, prof["image_cols"]["launches"]),
-            "check_max_rel_err": oracle_err,
-            "check_checksum_max_rel_err": check["checksum_max_rel_err"],
-            "check_ok": ok,
         }
+        if prof is not None:
+            result["kernels"] = per
+            result["image_ms"] = (prof["image_cols"]["ms"] + prof["image_rows"]["ms"]) / max(1, prof["image_cols"]["launches"])
+        if checked:
+            result["check_max_rel_err"] = oracle_err
+            result["check_checksum_max_rel_err"] = check["checksum_max_rel_err"]
+            result["check_ok"] = ok
         if dom:
             result["roofline"] = {"bound": "hbm", "kernel": dom, "achieved": per[dom]["gbps"], "peak": HBM_PEAK_GBPS,
                                   "unit": "GB/s", "frac": per[dom]["gbps"] / HBM_PEAK_GBPS, "traffic": traffic,
@@ -1059,7 +1111,7 @@ def main():
                                   "algorithmic_bytes_per_launch": ab[dom] * per[dom]["units_per_launch"],
                                   "avg_launch_ms": per[dom]["avg_ms"]}
         result.update(extras)
-        if world > 1 and not streamed and cfg == "cfg4" and nf_total == CONFIGS["cfg4"][5] and not args.weak:
+        if args.full and world > 1 and not streamed and cfg == "cfg4" and nf_total == CONFIGS["cfg4"][5] and not args.weak:
             # the driver's N = 1 run is the headline (cfg3); the strong-scaling denominator of THIS workload on one GPU is
             # the newest committed single-GPU run of it (python bench.py --config cfg4)
             import glob
@@ -1091,7 +1143,8 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     plan.destroy()
-    if rank == 0 and world == 1 and not use_dist and not args.no_extras and result is not None and args.config is None and not streamed and graph is None:
+    if (args.full and rank == 0 and world == 1 and not use_dist and not args.no_extras and result is not None and args.config is None
+            and not streamed and graph is None):
         # untimed for the headline: the MEX-faithful surface (host in / host out) and the F > 1 case, from THIS binary
         del engine, conv, out
         torch.cuda.empty_cache()
@@ -1109,6 +1162,8 @@ def main():
             result["vendor_fft_baseline"] = vendor_fft_figures(util, np, torch, dev, value=result["value"])
         except Exception as e:
             result["vendor_fft_baseline"] = {"error": repr(e)}
+    if dumped is not None:
+        write_outputs(np, dumped, args.dump_outputs, "_rank%d" % rank if world > 1 else "")
     if rank == 0:
         # RCCL prints a version banner through C stdio, which would otherwise be flushed after
         # Python's output at exit: flush it first so that the JSON line is the LAST line of stdout

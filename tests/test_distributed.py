@@ -220,6 +220,43 @@ def _bench(args, timeout=900):
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(tmp_path, oracle):
+    """a plain run prints the headline and nothing that needs passes of its own (--full adds them); --dump-outputs writes the
+    maps of the last timed step -- whole for cfg1, the same in a second run, the oracle's maps -- and a seeded sample of larger
+    maps (cfg2) whose values sit where its positions say"""
+    steps = ["--steps", "3", "--warmup", "1"]
+    a = _bench(["--config", "cfg1"] + steps + ["--dump-outputs", str(tmp_path / "a")])
+    assert a["steps"] == 3 and a["ms_per_step"] > 0 and a["dtype"] == "f32" and a["higher_is_better"] is True
+    assert a["metric"] == "Gpixel-filters/s (padded FFT size)" and a["unit"] == "Gpixel-filters/s"
+    assert not {"cpu_baseline", "roofline", "kernels", "check_ok", "host_output"} & set(a)
+    b = _bench(["--config", "cfg1", "--full"] + steps + ["--dump-outputs", str(tmp_path / "b")])
+    assert b["check_ok"] and {"cpu_baseline", "roofline", "kernels"} <= set(b)
+    maps = np.load(str(tmp_path / "a" / "maps.npy"))
+    assert maps.dtype == np.float32 and maps.shape == (1, 288, 288)
+    assert util.rel_err(np.load(str(tmp_path / "b" / "maps.npy")), maps) < 1e-6
+    sums = np.load(str(tmp_path / "a" / "map_sums.npy"))
+    assert sums.dtype == np.float64 and abs(sums[0] - maps[0].sum(dtype=np.float64)) <= 1e-5 * abs(sums[0])
+    img, _ = util.synth(1, 256, 256, 1, 31, 31, 0)                 # bench.py's cfg1 inputs
+    k = np.random.default_rng(5678 + 1).random((31, 31, 1), dtype=np.float32)
+    assert util.rel_err(maps[0].T, oracle.conv_fft(img, 31, 31, [k])[0]) < 1e-4
+    # cfg2: 16 maps of 1088 x 1088 -> a sample; map 0's sampled values against the oracle
+    _bench(["--config", "cfg2"] + steps + ["--dump-outputs", str(tmp_path / "c")])
+    assert sorted(os.listdir(str(tmp_path / "c"))) == ["map_sums.npy", "maps_sample.npy", "maps_sample_index.npy"]
+    vals = np.load(str(tmp_path / "c" / "maps_sample.npy"))
+    idx = np.load(str(tmp_path / "c" / "maps_sample_index.npy"))
+    assert vals.dtype == np.float32 and idx.dtype == np.float64 and vals.shape == idx.shape and vals.size > 1000
+    assert sum(os.path.getsize(str(tmp_path / "c" / f)) for f in os.listdir(str(tmp_path / "c"))) <= 64 << 20
+    img, _ = util.synth(2, 1024, 1024, 1, 63, 63, 0)
+    k = np.random.default_rng(5678 + 2).random((63, 63, 1), dtype=np.float32)
+    ref = oracle.conv_fft(img, 63, 63, [k])[0]                     # fft_h x fft_w; the dump is [map][w][h]
+    i = idx.astype(np.int64)
+    first = i < ref.size
+    w, h = np.divmod(i[first], ref.shape[0])
+    assert first.sum() > 10
+    assert np.abs(vals[first] - ref[h, w]).max() / np.abs(ref).max() < 1e-4
+
+
+@pytest.mark.gpu
 def test_bench_streamed_check_reads_the_last_image_odd_images_even_steps():
     """(advisor, round 2) 3 images per rank and an even step count: the last image of the timed region sits in the
     OTHER device buffer than after one step; the self-check has to follow it"""

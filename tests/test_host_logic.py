@@ -445,6 +445,17 @@ def test_bench_counts_distinct_devices_by_pci_id_then_by_index():
     assert bench.count_distinct_devices(two_hosts) == (2, "pci_bus_id")
 
 
+def test_bench_offers_full_and_dump_outputs_and_refuses_zero_steps():
+    """bench.py --full (everything beside the headline) and --dump-outputs DIR exist; --steps sets the timed steps, so 0 is
+    refused before anything starts"""
+    import sys
+    bench = os.path.join(util.ROOT, "bench.py")
+    r = subprocess.run([sys.executable, bench, "--help"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+    r = subprocess.run([sys.executable, bench, "--steps", "0"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps" in r.stderr
+
+
 def test_committed_bench_line_keeps_the_contract():
     """the newest committed bench line (profiles/r<NN>z_cfg3_bench.json, written by tools/profile_round.sh on the GPU box) carries
     every key the driver's contract names, the roofline and the CPU baseline objects, and numbers that are consistent with

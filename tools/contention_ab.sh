@@ -8,7 +8,7 @@
 # usage (through gpurun, from the repo root): bash tools/contention_ab.sh > gpurun_out/<tag>_contention_ab.txt
 STEPS=${STEPS:-10}
 run() {   # cfg-args, dynamic, contend
-  python3 bench.py $1 --overlap --no-cpu-baseline --no-extras --tune-placement 0 --steps $STEPS --warmup 3 --dynamic-tiles $2 ${3:+--contend $3} 2>/dev/null | tail -1 | python3 -c "
+  python3 bench.py --full $1 --overlap --no-cpu-baseline --no-extras --tune-placement 0 --steps $STEPS --warmup 3 --dynamic-tiles $2 ${3:+--contend $3} 2>/dev/null | tail -1 | python3 -c "
 import sys,json
 j=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=j['kernels']; c=j['config'].get('contention') or {}

@@ -5,8 +5,9 @@ TAG=${TAG:-r05z}
 STEPS=20 bash tools/all_cfgs.sh > gpurun_out/${TAG}_all_configs.txt 2>&1; cat gpurun_out/${TAG}_all_configs.txt
 # the denominator of the N > 1 strong-scaling line: the same workload (cfg4, 1024 filters) on ONE GPU, from THIS library (bench.py
 # stamps it with the library's hash and the N > 1 line says whether it matches: same_workload_1gpu.is_of_this_binary)
-python bench.py --config cfg4 --no-cpu-baseline --no-extras --steps 10 --warmup 3 > gpurun_out/${TAG}_cfg4_1024_filters_1gpu_denominator.json 2> gpurun_out/${TAG}_cfg4_denominator.err; echo "denominator rc $?"
-for c in cfg3f4 mid512 hd720 mid2900 big6000 big8192; do python bench.py --config $c --no-cpu-baseline --no-extras --steps 10 --warmup 3 --check 2>/dev/null | tail -1 | python -c "
+# (written straight into profiles/, where bench.py --full looks for it)
+python bench.py --full --config cfg4 --no-cpu-baseline --no-extras --steps 10 --warmup 3 > profiles/${TAG}_cfg4_1024_filters_1gpu_denominator.json; echo "denominator rc $?"
+for c in cfg3f4 mid512 hd720 mid2900 big6000 big8192; do python bench.py --full --config $c --no-cpu-baseline --no-extras --steps 10 --warmup 3 --check 2>/dev/null | tail -1 | python -c "
 import sys,json
 j=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=j['kernels']

@@ -2,7 +2,7 @@
 # first half has already run on the final library.  usage: TAG=r05z bash tools/final_session_2b.sh
 set -o pipefail
 TAG=${TAG:-r05z}
-for c in cfg3f4 mid512 hd720 mid2900 big6000 big8192; do python bench.py --config $c --no-cpu-baseline --no-extras --steps 10 --warmup 3 --check 2>/dev/null | tail -1 | python -c "
+for c in cfg3f4 mid512 hd720 mid2900 big6000 big8192; do python bench.py --full --config $c --no-cpu-baseline --no-extras --steps 10 --warmup 3 --check 2>/dev/null | tail -1 | python -c "
 import sys,json
 j=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=j['kernels']

@@ -8,7 +8,7 @@ FFTCONV_LIB=$AB/cpad.so timeout -k 10 300 python -m pytest tests/test_fast_paths
 SHAPES="${SHAPES:-4096 4096 127 64;4096 4096 63 128}" REPS=${REPS:-4} bash tools/config_search_run.sh cnopad cpad > $OUT/ab.txt 2>&1
 cat $OUT/ab.txt
 for v in cnopad cpad; do
-  FFTCONV_LIB=$AB/$v.so rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_INSTS_LDS --output-format csv -d $OUT/pmc_$v -o p -- python3 bench.py --steps 1 --warmup 1 --no-clock-warm --no-cpu-baseline --no-extras > /dev/null 2> $OUT/pmc_$v.err || echo "pmc $v failed"
+  FFTCONV_LIB=$AB/$v.so rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_INSTS_LDS --output-format csv -d $OUT/pmc_$v -o p -- python3 bench.py --full --steps 1 --warmup 1 --no-clock-warm --no-cpu-baseline --no-extras > /dev/null 2> $OUT/pmc_$v.err || echo "pmc $v failed"
   echo "== $v"; python3 tools/pmc_summary.py $(find $OUT/pmc_$v -name "*counter_collection.csv") | grep -A4 "k_fast_cols grid"
   find $OUT/pmc_$v -name "*.csv" -size +1M -delete; find $OUT/pmc_$v -name "*.db" -delete
 done 2>&1 | tee $OUT/counters.txt

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/r05v; mkdir -p $OUT
 cp cuda-fft-convolution_amd/libfftconv.so cuda-fft-convolution_amd/ab/new.so
 for rep in 1 2 3; do for v in base new; do
-  FFTCONV_LIB=$PWD/cuda-fft-convolution_amd/ab/$v.so python bench.py --no-cpu-baseline --no-extras 2> $OUT/${v}_$rep.err | tail -1 > $OUT/${v}_$rep.json
+  FFTCONV_LIB=$PWD/cuda-fft-convolution_amd/ab/$v.so python bench.py --full --no-cpu-baseline --no-extras 2> $OUT/${v}_$rep.err | tail -1 > $OUT/${v}_$rep.json
   python - <<PY
 import json
 j=json.loads(open('$OUT/${v}_$rep.json').read().strip().splitlines()[-1]); r=j['roofline']

@@ -3,7 +3,7 @@ CFG=$1; shift
 OUT=gpurun_out/trace_$CFG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o t -- python3 bench.py --config $CFG --steps 20 --warmup 3 --no-cpu-baseline "$@" > $OUT/bench.json 2> $OUT/err.txt
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o t -- python3 bench.py --full --config $CFG --steps 20 --warmup 3 --no-cpu-baseline "$@" > $OUT/bench.json 2> $OUT/err.txt
 find $OUT -name "*.db" -delete
 python3 - <<PY
 import csv,glob,json
