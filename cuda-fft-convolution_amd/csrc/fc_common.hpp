@@ -281,10 +281,21 @@ struct StageDesc {
 };
 
 struct FftDesc {
-    int L;   // transform length = product of radices
-    int ns;  // number of stages
+    int L;   // transform length (logical: what the caller's sequences hold, in and out)
+    int ns;  // number of stages (of the work length when bs_work > 0)
     StageDesc st[FC_MAX_STAGES];
+    // Bluestein (chirp-z) form for a length L that does not factor into the radices (planner.hpp:
+    // make_plan1d_bluestein): the stages are those of a supported work length bs_work >= 2L - 1, and the
+    // plan's table holds, after the stage twiddles, the chirp w[n] = exp(-i pi n^2 / L) (L entries at
+    // bs_chirp_off) and the filter spectrum DFT_{bs_work}(conj w[|n|]) / bs_work (bs_work entries at
+    // bs_filt_off, in the work transform's digit-reversed order).  bs_work = 0: a direct transform.
+    int bs_work;
+    int bs_chirp_off;
+    int bs_filt_off;
 };
+
+// LDS elements one sequence of the transform occupies while it runs
+FC_HD int fft_work_length(const FftDesc& d) { return d.bs_work > 0 ? d.bs_work : d.L; }
 
 // Entry of the real<->half-complex pair table (see kernels_body.hpp).
 struct alignas(16) PairEntry {

@@ -91,22 +91,81 @@ FC_HD void stage_dispatch(const Ctx& ctx, c32* buf, int pitch, int nseq, int L, 
     }
 }
 
-// All stages, forward.  Ends with a barrier.
+// All stages of a direct transform of length L, forward / inverse.  Each ends with a barrier.
 template <class Ctx>
-FC_HD void fft_forward(const Ctx& ctx, c32* buf, int pitch, int nseq, const FftDesc& d, const c32* tw) {
+FC_HD void fft_stages_forward(const Ctx& ctx, c32* buf, int pitch, int nseq, int L, const FftDesc& d, const c32* tw) {
     for (int t = 0; t < d.ns; t++) {
-        stage_dispatch<-1>(ctx, buf, pitch, nseq, d.L, d.st[t], tw);
+        stage_dispatch<-1>(ctx, buf, pitch, nseq, L, d.st[t], tw);
+        ctx.sync();
+    }
+}
+template <class Ctx>
+FC_HD void fft_stages_inverse(const Ctx& ctx, c32* buf, int pitch, int nseq, int L, const FftDesc& d, const c32* tw) {
+    for (int t = d.ns - 1; t >= 0; t--) {
+        stage_dispatch<+1>(ctx, buf, pitch, nseq, L, d.st[t], tw);
         ctx.sync();
     }
 }
 
-// All stages, inverse (unnormalised).  Ends with a barrier.
-template <class Ctx>
-FC_HD void fft_inverse(const Ctx& ctx, c32* buf, int pitch, int nseq, const FftDesc& d, const c32* tw) {
-    for (int t = d.ns - 1; t >= 0; t--) {
-        stage_dispatch<+1>(ctx, buf, pitch, nseq, d.L, d.st[t], tw);
-        ctx.sync();
+// Bluestein (chirp-z) transform of length N = d.L over the work length Lb = d.bs_work (planner.hpp:
+// make_plan1d_bluestein), natural order in and out, in place in the first N elements of each sequence; the
+// sequence must have room for Lb elements (pitch >= Lb).  SGN < 0: forward DFT; SGN > 0: the unnormalised inverse,
+// the same computation conjugated (the filter is even, so conj(B) is the spectrum of the conjugated filter).
+//   1. a[n] = x[n] * w[n] for n < N, 0 in [N, Lb)      3. A *= B (digit-reversed order: B is stored that way)
+//   2. forward Lb-point transform                       4. inverse Lb-point transform
+//   5. X[k] = w[k] * a[k] for k < N
+// Each pointwise pass touches only the indices its thread owns and is followed by a barrier.  Ends with a barrier.
+template <int SGN, class Ctx>
+FC_HD void fft_bluestein(const Ctx& ctx, c32* buf, int pitch, int nseq, const FftDesc& d, const c32* tw) {
+    const int N = d.L, Lb = d.bs_work;
+    // (the chirp / filter addresses are formed where they are used: kept live across the stages, they cost spills)
+    for (int g = ctx.tid; g < nseq * Lb; g += ctx.nthreads) {
+        const c32* chirp = tw + d.bs_chirp_off;
+        int seq = 0, n = g;
+        if (nseq > 1) { seq = g / Lb; n = g - seq * Lb; }
+        c32* p = buf + seq * pitch + n;
+        if (n < N) *p = (SGN < 0) ? cmul(*p, chirp[n]) : cmulc(*p, chirp[n]);
+        else *p = mk(0.f, 0.f);
     }
+    ctx.sync();
+    fft_stages_forward(ctx, buf, pitch, nseq, Lb, d, tw);
+    for (int g = ctx.tid; g < nseq * Lb; g += ctx.nthreads) {
+        const c32* filt = tw + d.bs_filt_off;
+        int seq = 0, j = g;
+        if (nseq > 1) { seq = g / Lb; j = g - seq * Lb; }
+        c32* p = buf + seq * pitch + j;
+        *p = (SGN < 0) ? cmul(*p, filt[j]) : cmulc(*p, filt[j]);
+    }
+    ctx.sync();
+    fft_stages_inverse(ctx, buf, pitch, nseq, Lb, d, tw);
+    for (int g = ctx.tid; g < nseq * N; g += ctx.nthreads) {
+        const c32* chirp = tw + d.bs_chirp_off;
+        int seq = 0, k = g;
+        if (nseq > 1) { seq = g / N; k = g - seq * N; }
+        c32* p = buf + seq * pitch + k;
+        *p = (SGN < 0) ? cmul(*p, chirp[k]) : cmulc(*p, chirp[k]);
+    }
+    ctx.sync();
+}
+
+// BS: which forms the caller is built for.  -1 (default): both, chosen by d.bs_work at run time (tests/emu); 0 / 1: the
+// direct / Bluestein form only -- the HIP kernels are instantiated once per form (kernels.hip), so that the direct
+// kernels carry no Bluestein code: the two forms in one function cost the column kernels an occupancy step (VGPRs).
+template <int BS>
+FC_HD bool fft_is_bluestein(const FftDesc& d) { return BS < 0 ? d.bs_work > 0 : BS > 0; }
+
+// Forward transform (digit-reversed out; natural for a Bluestein plan).  Ends with a barrier.
+template <int BS = -1, class Ctx>
+FC_HD void fft_forward(const Ctx& ctx, c32* buf, int pitch, int nseq, const FftDesc& d, const c32* tw) {
+    if (fft_is_bluestein<BS>(d)) fft_bluestein<-1>(ctx, buf, pitch, nseq, d, tw);
+    else fft_stages_forward(ctx, buf, pitch, nseq, d.L, d, tw);
+}
+
+// Inverse transform (unnormalised; digit-reversed in, natural for a Bluestein plan).  Ends with a barrier.
+template <int BS = -1, class Ctx>
+FC_HD void fft_inverse(const Ctx& ctx, c32* buf, int pitch, int nseq, const FftDesc& d, const c32* tw) {
+    if (fft_is_bluestein<BS>(d)) fft_bluestein<+1>(ctx, buf, pitch, nseq, d, tw);
+    else fft_stages_inverse(ctx, buf, pitch, nseq, d.L, d, tw);
 }
 
 }  // namespace fc

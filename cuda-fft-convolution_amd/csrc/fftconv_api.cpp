@@ -36,15 +36,15 @@ std::mutex g_live_mutex;
 std::set<const fftconv_plan*> g_live_plans;
 
 int cols_threads(const Geometry& g) {
-    long work = (long)g.T_cols * g.M;
+    long work = (long)g.T_cols * g.work_m;   // (work lengths: a Bluestein direction runs on its longer work transform)
     if (work >= 4096) return 512;
     if (work >= 1024) return 256;
     if (work >= 256) return 128;
     return 64;
 }
 int rows_threads(const Geometry& g) {
-    if (g.Lw >= 2048) return 256;
-    if (g.Lw >= 512) return 128;
+    if (g.work_w >= 2048) return 256;
+    if (g.work_w >= 512) return 128;
     return 64;
 }
 
@@ -392,7 +392,13 @@ int fc::plan_create_internal(fftconv_plan** plan, int data_h, int data_w, int fe
         if (cyclic)
             (void)api_fail(FFTCONV_ERR_UNSUPPORTED_SIZE, "no specialised kernels for a %dx%d block transform with kernels up to %dx%d", data_h, data_w,
                        max_kernel_h, max_kernel_w);
-        else if (options_no_blockwise(options) || tune.exact_window)
+        else if (tune.exact_window)
+            (void)api_fail(FFTCONV_ERR_UNSUPPORTED_SIZE,
+                       "sizes %dx%dx%d with kernels up to %dx%d: exact_window needs transforms of the %dx%d window itself (complex lengths %d and %d, "
+                       "direct or by Bluestein), and their work lengths do not fit the single-pass LDS transform%s", data_h, data_w, feature_dim,
+                       max_kernel_h, max_kernel_w, fft_size16(data_h + max_kernel_h - 1), fft_size16(data_w + max_kernel_w - 1),
+                       fft_size16(data_h + max_kernel_h - 1) / 2, fft_size16(data_w + max_kernel_w - 1), tune.max_transform > 0 ? " within max_transform" : "");
+        else if (options_no_blockwise(options))
             (void)api_fail(FFTCONV_ERR_UNSUPPORTED_SIZE, "sizes %dx%dx%d with kernels up to %dx%d do not fit the single-pass LDS transform%s", data_h,
                        data_w, feature_dim, max_kernel_h, max_kernel_w, tune.max_transform > 0 ? " within max_transform" : "");
         else
@@ -560,8 +566,15 @@ int fftconv_plan_set_image(fftconv_plan* plan, const float* data, int location) 
     }
     FC_VERBOSE(p, "Using GPU : %d", p->gpu_id);                                                    // src/cudaConvolutionFFT.cu:87
     FC_VERBOSE(p, "Data size: h=%d, w=%d, f=%d", g.H, g.W, g.F);                                   // :100
-    FC_VERBOSE(p, "FFT size: h=%d, w=%d (internal transform %d x %d, %s column pass, %s row pass, %s intermediate)", g.fft_h, g.fft_w, g.Lh, g.Lw,   // :114
-               g.fast_fwd ? "specialised" : "generic", g.fast_rows.ok ? "specialised" : "generic", g.y_tiled() ? "tiled" : "row-major");
+    char chirp[96] = "";          // windows that do not factor into the radices: Bluestein transforms on longer work lengths
+    if (g.bluestein_h() || g.bluestein_w()) {
+        char hs[32] = "", ws[32] = "";
+        if (g.bluestein_h()) snprintf(hs, sizeof(hs), " h %d via %d", g.M, g.work_m);
+        if (g.bluestein_w()) snprintf(ws, sizeof(ws), " w %d via %d", g.Lw, g.work_w);
+        snprintf(chirp, sizeof(chirp), ", chirp-z passes:%s%s%s", hs, (hs[0] && ws[0]) ? "," : "", ws);
+    }
+    FC_VERBOSE(p, "FFT size: h=%d, w=%d (internal transform %d x %d, %s column pass, %s row pass, %s intermediate%s)", g.fft_h, g.fft_w, g.Lh, g.Lw,   // :114
+               g.fast_fwd ? "specialised" : "generic", g.fast_rows.ok ? "specialised" : "generic", g.y_tiled() ? "tiled" : "row-major", chirp);
     // (with the fast row kernel the w-pass stores the spectrum directly in that kernel's register order)
     if (int rc = p->ensure_spectrum()) return rc;
     c32* sgen = p->spec();
@@ -595,7 +608,7 @@ int fftconv_plan_set_image(fftconv_plan* plan, const float* data, int location) 
         HIP_TRY(launch_fast_rows_fwd(g.Lw, fast_rows_fwd_args(g, p->d, sgen), g.F * g.rows, p->stream));
     } else {
         RowsFwdArgs ra = image_rows_args(g, p->t, p->d, sgen);
-        HIP_TRY(launch_rows_fwd(ra, g.F * g.rows, rows_threads(g), (size_t)g.Lw * sizeof(c32), p->stream));
+        HIP_TRY(launch_rows_fwd(ra, g.F * g.rows, rows_threads(g), g.rows_fwd_lds_bytes(), p->stream));
     }
     if (int rc = p->prof_end()) return rc;
     if (location == FFTCONV_HOST && !image_pinned) HIP_TRY(hipStreamSynchronize(p->stream));

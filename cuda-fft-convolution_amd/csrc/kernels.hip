@@ -16,24 +16,29 @@ struct DevCtx {
 
 extern __shared__ __attribute__((aligned(16))) unsigned char fc_smem[];
 
+// BS = 1: the Bluestein form of the transforms (exact-window plans whose window does not factor), 0: direct
+template <int BS>
 __global__ void __launch_bounds__(512) k_cols_r2c(ColsR2CArgs a) {
     DevCtx ctx{(int)threadIdx.x, (int)blockDim.x};
-    cols_r2c_body(ctx, reinterpret_cast<c32*>(fc_smem), a, (int)blockIdx.x, (int)blockIdx.y);
+    cols_r2c_body<BS>(ctx, reinterpret_cast<c32*>(fc_smem), a, (int)blockIdx.x, (int)blockIdx.y);
 }
 
+template <int BS>
 __global__ void __launch_bounds__(512) k_rows_fwd(RowsFwdArgs a) {
     DevCtx ctx{(int)threadIdx.x, (int)blockDim.x};
-    rows_fwd_body(ctx, reinterpret_cast<c32*>(fc_smem), a, (int)blockIdx.x);
+    rows_fwd_body<BS>(ctx, reinterpret_cast<c32*>(fc_smem), a, (int)blockIdx.x);
 }
 
+template <int BS>
 __global__ void __launch_bounds__(512) k_spectral_rows(SpectralRowsArgs a) {
     DevCtx ctx{(int)threadIdx.x, (int)blockDim.x};
-    spectral_rows_body(ctx, reinterpret_cast<c32*>(fc_smem), a, (int)blockIdx.x, (int)blockIdx.y);
+    spectral_rows_body<BS>(ctx, reinterpret_cast<c32*>(fc_smem), a, (int)blockIdx.x, (int)blockIdx.y);
 }
 
+template <int BS>
 __global__ void __launch_bounds__(512) k_cols_c2r(ColsC2RArgs a) {
     DevCtx ctx{(int)threadIdx.x, (int)blockDim.x};
-    cols_c2r_body(ctx, reinterpret_cast<c32*>(fc_smem), a, (int)blockIdx.x, (int)blockIdx.y);
+    cols_c2r_body<BS>(ctx, reinterpret_cast<c32*>(fc_smem), a, (int)blockIdx.x, (int)blockIdx.y);
 }
 
 // Reverses every plane of `pe` floats: for a column-major kh x kw plane that is the flip along both
@@ -217,32 +222,39 @@ hipError_t launch_fast_cols_fwd_pair(int M, int T, const FastColsFwdArgs& image,
 
 hipError_t kernels_init() {
     const int lim = 160 * 1024;
-    hipError_t e;
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_cols_r2c), hipFuncAttributeMaxDynamicSharedMemorySize, lim)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_rows_fwd), hipFuncAttributeMaxDynamicSharedMemorySize, lim)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_spectral_rows), hipFuncAttributeMaxDynamicSharedMemorySize, lim)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_cols_c2r), hipFuncAttributeMaxDynamicSharedMemorySize, lim)) != hipSuccess) return e;
+    const void* generic[] = {reinterpret_cast<const void*>(k_cols_r2c<0>),      reinterpret_cast<const void*>(k_cols_r2c<1>),
+                             reinterpret_cast<const void*>(k_rows_fwd<0>),      reinterpret_cast<const void*>(k_rows_fwd<1>),
+                             reinterpret_cast<const void*>(k_spectral_rows<0>), reinterpret_cast<const void*>(k_spectral_rows<1>),
+                             reinterpret_cast<const void*>(k_cols_c2r<0>),      reinterpret_cast<const void*>(k_cols_c2r<1>)};
+    for (const void* k : generic) {
+        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
+        if (e != hipSuccess) return e;
+    }
     return hipSuccess;
 }
 
 hipError_t launch_cols_r2c(const ColsR2CArgs& a, int tiles, int planes, int threads, size_t lds_bytes, hipStream_t s) {
     if (tiles <= 0 || planes <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_cols_r2c, dim3(tiles, planes), dim3(threads), lds_bytes, s, a);
+    if (a.fd.bs_work > 0) hipLaunchKernelGGL(k_cols_r2c<1>, dim3(tiles, planes), dim3(threads), lds_bytes, s, a);
+    else hipLaunchKernelGGL(k_cols_r2c<0>, dim3(tiles, planes), dim3(threads), lds_bytes, s, a);
     return hipGetLastError();
 }
 hipError_t launch_rows_fwd(const RowsFwdArgs& a, int rows, int threads, size_t lds_bytes, hipStream_t s) {
     if (rows <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_rows_fwd, dim3(rows), dim3(threads), lds_bytes, s, a);
+    if (a.fd.bs_work > 0) hipLaunchKernelGGL(k_rows_fwd<1>, dim3(rows), dim3(threads), lds_bytes, s, a);
+    else hipLaunchKernelGGL(k_rows_fwd<0>, dim3(rows), dim3(threads), lds_bytes, s, a);
     return hipGetLastError();
 }
 hipError_t launch_spectral_rows(const SpectralRowsArgs& a, int rows, int kernels, int threads, size_t lds_bytes, hipStream_t s) {
     if (rows <= 0 || kernels <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_spectral_rows, dim3(rows, kernels), dim3(threads), lds_bytes, s, a);
+    if (a.fd.bs_work > 0) hipLaunchKernelGGL(k_spectral_rows<1>, dim3(rows, kernels), dim3(threads), lds_bytes, s, a);
+    else hipLaunchKernelGGL(k_spectral_rows<0>, dim3(rows, kernels), dim3(threads), lds_bytes, s, a);
     return hipGetLastError();
 }
 hipError_t launch_cols_c2r(const ColsC2RArgs& a, int tiles, int kernels, int threads, size_t lds_bytes, hipStream_t s) {
     if (tiles <= 0 || kernels <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_cols_c2r, dim3(tiles, kernels), dim3(threads), lds_bytes, s, a);
+    if (a.fd.bs_work > 0) hipLaunchKernelGGL(k_cols_c2r<1>, dim3(tiles, kernels), dim3(threads), lds_bytes, s, a);
+    else hipLaunchKernelGGL(k_cols_c2r<0>, dim3(tiles, kernels), dim3(threads), lds_bytes, s, a);
     return hipGetLastError();
 }
 

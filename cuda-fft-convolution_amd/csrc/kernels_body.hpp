@@ -15,7 +15,8 @@
 // w-passes and the h-passes consume exactly the order they produce.
 //
 // Each body is a template over a context {tid, nthreads, sync()}; kernels*.hip instantiate it
-// with the HIP thread/barrier, tests/emu with a sequential host context.
+// with the HIP thread/barrier, tests/emu with a sequential host context.  BS (fft_lds.hpp: fft_forward): -1 takes
+// the transform form (direct / Bluestein) from the plan at run time; the HIP kernels are instantiated per form.
 #pragma once
 #include "fc_common.hpp"
 #include "fft_lds.hpp"
@@ -38,14 +39,14 @@ struct ColsR2CArgs {
     int out_pitch;        // c32 between rows
     int M;                // complex transform length (Lh/2)
     int T;                // columns per workgroup
-    int lds_pitch;        // c32 per column in LDS (>= M+1)
+    int lds_pitch;        // c32 per column in LDS (>= M+1, and >= the Bluestein work length)
     FftDesc fd;           // M-point transform
     const c32* tw;
     const PairEntry* pairs;
     int npairs;
 };
 
-template <class Ctx>
+template <int BS = -1, class Ctx>
 FC_HD void cols_r2c_body(const Ctx& ctx, c32* lds, const ColsR2CArgs& a, int tile, int plane) {
     const int M = a.M, T = a.T, LP = a.lds_pitch;
     const int c0 = tile * T;
@@ -64,8 +65,10 @@ FC_HD void cols_r2c_body(const Ctx& ctx, c32* lds, const ColsR2CArgs& a, int til
         lds[t * LP + n] = mk(x0, x1);
     }
     ctx.sync();
-    fft_forward(ctx, lds, LP, T, a.fd, a.tw);
-    // split the packed transform into the spectrum of the real sequence, in place
+    fft_forward<BS>(ctx, lds, LP, T, a.fd, a.tw);
+    // split the packed transform into the spectrum of the real sequence, in place.  Slot M (the Nyquist bin) lies
+    // inside the work area of a Bluestein transform (fft_lds.hpp: fft_bluestein, [M, L') is scratch there): safe
+    // only because this pass runs after the forward transform is over -- keep it that way.
     for (int idx = ctx.tid; idx < T * a.npairs; idx += ctx.nthreads) {
         int t = idx / a.npairs, p = idx - t * a.npairs;
         c32* z = lds + t * LP;
@@ -110,13 +113,13 @@ struct RowsFwdArgs {
                          // (the fast row kernel's register order, fast_rows.hpp); nullptr = identity
 };
 
-template <class Ctx>
+template <int BS = -1, class Ctx>
 FC_HD void rows_fwd_body(const Ctx& ctx, c32* lds, const RowsFwdArgs& a, int row) {
     const int L = a.fd.L;
     c32* g = a.S + (size_t)row * a.pitch;
     for (int x = ctx.tid; x < L; x += ctx.nthreads) lds[x] = (x < a.nvalid) ? g[x] : mk(0.f, 0.f);
     ctx.sync();
-    fft_forward(ctx, lds, L, 1, a.fd, a.tw);
+    fft_forward<BS>(ctx, lds, L, 1, a.fd, a.tw);
     if (a.out_map) {
         for (int x = ctx.tid; x < L; x += ctx.nthreads) g[x] = scale(lds[a.out_map[x]], a.scale);
     } else {
@@ -148,33 +151,39 @@ struct SpectralRowsArgs {
     int F;
     FftDesc fd;          // Lw-point transform
     const c32* tw;
+    int acc_in_y;        // F > 1: the feature sum accumulates in this kernel's row of Y (global memory) instead of
+                         // LDS -- Bluestein rows whose work buffer and accumulator do not fit the LDS together
 };
 
-// lds: L c32 (F == 1) or 2L c32 (F > 1: second half accumulates over features)
-template <class Ctx>
+// lds: the work buffer (fft_work_length c32: Lw, or the Bluestein work length), for F > 1 followed by an Lw-c32
+// accumulator of the feature sum unless acc_in_y.  The last feature's product is summed into the work buffer, and
+// the inverse transform runs there.
+template <int BS = -1, class Ctx>
 FC_HD void spectral_rows_body(const Ctx& ctx, c32* lds, const SpectralRowsArgs& a, int row, int kernel) {
     const int L = a.fd.L;
     c32* buf = lds;
-    c32* acc = lds + L;
+    c32* yrow = a.Y + (size_t)kernel * a.y_kernel_stride + (size_t)row * a.y_pitch;
+    // (in Y: every thread reads back only the elements it wrote itself, and the row is overwritten by the store below)
+    c32* acc = a.acc_in_y ? yrow : lds + fft_work_length(a.fd);
     for (int f = 0; f < a.F; f++) {
         const c32* arow = a.A + (size_t)kernel * a.a_kernel_stride + (size_t)f * a.a_feat_stride + (size_t)row * a.a_pitch;
         const c32* srow = a.S + (size_t)f * a.s_feat_stride + (size_t)row * a.s_pitch;
         for (int x = ctx.tid; x < L; x += ctx.nthreads) buf[x] = (x < a.kw) ? arow[x] : mk(0.f, 0.f);
         ctx.sync();
-        fft_forward(ctx, buf, L, 1, a.fd, a.tw);
+        fft_forward<BS>(ctx, buf, L, 1, a.fd, a.tw);
         if (a.F == 1) {
             for (int x = ctx.tid; x < L; x += ctx.nthreads) buf[x] = cmul(buf[x], srow[x]);
         } else if (f == 0) {
             for (int x = ctx.tid; x < L; x += ctx.nthreads) acc[x] = cmul(buf[x], srow[x]);
-        } else {
+        } else if (f < a.F - 1) {
             for (int x = ctx.tid; x < L; x += ctx.nthreads) acc[x] = acc[x] + cmul(buf[x], srow[x]);
+        } else {
+            for (int x = ctx.tid; x < L; x += ctx.nthreads) buf[x] = acc[x] + cmul(buf[x], srow[x]);
         }
         ctx.sync();
     }
-    c32* res = (a.F == 1) ? buf : acc;
-    fft_inverse(ctx, res, L, 1, a.fd, a.tw);
-    c32* yrow = a.Y + (size_t)kernel * a.y_kernel_stride + (size_t)row * a.y_pitch;
-    for (int x = ctx.tid; x < a.wout; x += ctx.nthreads) yrow[x] = res[x];
+    fft_inverse<BS>(ctx, buf, L, 1, a.fd, a.tw);
+    for (int x = ctx.tid; x < a.wout; x += ctx.nthreads) yrow[x] = buf[x];
 }
 
 // ---------------------------------------------------------------------------------------
@@ -192,14 +201,14 @@ struct ColsC2RArgs {
     int fft_h, fft_w;    // output window (reference's ceil16 sizes)
     int M;               // Lh/2
     int T;
-    int lds_pitch;
+    int lds_pitch;       // (>= M+1, and >= the Bluestein work length)
     FftDesc fd;          // M-point transform
     const c32* tw;
     const PairEntry* pairs;
     int npairs;
 };
 
-template <class Ctx>
+template <int BS = -1, class Ctx>
 FC_HD void cols_c2r_body(const Ctx& ctx, c32* lds, const ColsC2RArgs& a, int tile, int kernel) {
     const int M = a.M, T = a.T, LP = a.lds_pitch;
     const int w0 = tile * T;
@@ -232,7 +241,8 @@ FC_HD void cols_c2r_body(const Ctx& ctx, c32* lds, const ColsC2RArgs& a, int til
         }
     }
     ctx.sync();
-    fft_inverse(ctx, lds, LP, T, a.fd, a.tw);
+    // (the merge above reads slot M, which a Bluestein transform uses as scratch: it is over before the inverse starts)
+    fft_inverse<BS>(ctx, lds, LP, T, a.fd, a.tw);
     // store: out[w][2n], out[w][2n+1] = re, im of z[n]; zero-fill up to fft_h
     float* out = a.out + (size_t)kernel * a.out_kernel_stride;
     const int half = a.fft_h / 2;  // fft_h is a multiple of 16

@@ -11,8 +11,6 @@
 
 namespace fc {
 
-constexpr size_t FC_LDS_BUDGET = 160 * 1024;  // bytes of LDS one workgroup may claim (gfx950 CU)
-
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 // Choices fixed at plan creation (include/fftconv.h: fftconv_plan_options).  The product reads no
@@ -28,7 +26,8 @@ struct PlanTuning {
     // to the block-wise path of the one-shot entry
     int max_transform = 0;
     // transform lengths must equal the ceil16 window (the reference's circular modulus; needed to
-    // exchange spectra in the reference's order); unsupported windows then fail
+    // exchange spectra in the reference's order); a window that does not factor into the radices runs
+    // Bluestein transforms on the generic kernels, one whose work length does not fit the LDS fails
     bool exact_window = false;
     // the block plan of an overlap-save block-wise plan (fftconv_api.cpp): H x W IS the transform (a block of the image with
     // its history rows / columns), the result is the circular convolution modulo H x W, and the caller stores the part of
@@ -48,6 +47,8 @@ struct Geometry {
     int s_pitch = 0;           // c32 per image-spectrum row
     int y_pitch = 0;           // c32 per intermediate row
     int wout = 0;              // columns of Y consumed by the output pass: min(Lw, fft_w)
+    int work_m = 0, work_w = 0; // complex lengths the h / w transforms run on: M / Lw, or their Bluestein work lengths
+    bool acc_in_y = false;     // generic spectral rows, F > 1: the feature sum accumulates in Y (SpectralRowsArgs::acc_in_y)
     int lds_pitch = 0;         // c32 per LDS-resident column
     int T_cols = 1;            // columns per workgroup in the h-passes
     bool exact_window = false; // Lh == fft_h && Lw == fft_w: circular modulus equals the reference's
@@ -102,6 +103,11 @@ struct Geometry {
         return y_tiled() ? (size_t)(fft_w / y_tile_w) * tile_rows() * y_tile_w : (size_t)rows * y_pitch;
     }
     size_t map_elems() const { return (size_t)fft_h * fft_w; }
+    bool bluestein_h() const { return work_m != M; }
+    bool bluestein_w() const { return work_w != Lw; }
+    // dynamic LDS of the generic row kernels: the image's forward rows, the spectral rows (+ the accumulator)
+    size_t rows_fwd_lds_bytes() const { return (size_t)work_w * sizeof(c32); }
+    size_t rows_lds_bytes() const { return ((size_t)work_w + (F > 1 && !acc_in_y ? Lw : 0)) * sizeof(c32); }
 };
 
 struct Tables {
@@ -132,8 +138,12 @@ inline bool make_geometry(Geometry& g, Tables& t, int H, int W, int F, int max_k
     // (max_transform caps the search: a cheaper length above it must not turn a size that fits into one that does not)
     g.Lh = choose_length(H + max_kh - 1, true, g.fft_h, prefs, tune.max_transform);
     g.Lw = choose_length(W + max_kw - 1, false, g.fft_w, prefs, tune.max_transform);
-    if (tune.exact_window || tune.cyclic) {
+    if (tune.cyclic) {
         if (!length_supported(g.fft_h / 2) || !length_supported(g.fft_w)) return false;
+        g.Lh = g.fft_h;
+        g.Lw = g.fft_w;
+    } else if (tune.exact_window) {   // windows that do not factor: Bluestein transforms (make_plan1d_bluestein)
+        if (!length_transformable(g.fft_h / 2) || !length_transformable(g.fft_w)) return false;
         g.Lh = g.fft_h;
         g.Lw = g.fft_w;
     }
@@ -144,15 +154,19 @@ inline bool make_geometry(Geometry& g, Tables& t, int H, int W, int F, int max_k
     g.s_pitch = round_up(g.Lw, 8);
     g.wout = std::min(g.Lw, g.fft_w);
     g.y_pitch = round_up(g.wout, 8);
-    g.lds_pitch = lds_col_pitch(g.M);
+    g.work_m = length_supported(g.M) ? g.M : bluestein_work_length(g.M);
+    g.work_w = length_supported(g.Lw) ? g.Lw : bluestein_work_length(g.Lw);
+    if (g.work_m < 1 || g.work_w < 1) return false;
+    g.lds_pitch = lds_col_pitch(std::max(g.M, g.work_m - 1));   // (>= M + 1 and >= the work length)
     g.T_cols = 8;
     while (g.T_cols > 1 && (size_t)g.T_cols * g.lds_pitch * sizeof(c32) > FC_LDS_BUDGET) g.T_cols /= 2;
     if ((size_t)g.T_cols * g.lds_pitch * sizeof(c32) > FC_LDS_BUDGET) return false;
-    size_t row_lds = (size_t)g.Lw * sizeof(c32) * (F > 1 ? 2 : 1);
-    if (row_lds > FC_LDS_BUDGET) return false;
+    // (a Bluestein row whose accumulator does not fit beside its work buffer sums the features in Y instead)
+    g.acc_in_y = F > 1 && g.bluestein_w() && g.rows_lds_bytes() > FC_LDS_BUDGET;
+    if (g.rows_lds_bytes() > FC_LDS_BUDGET) return false;
     g.exact_window = (g.Lh == g.fft_h && g.Lw == g.fft_w);
-    t.pm = make_plan1d(g.M);
-    t.pw = make_plan1d(g.Lw);
+    t.pm = g.bluestein_h() ? make_plan1d_bluestein(g.M, g.work_m) : make_plan1d(g.M);
+    t.pw = g.bluestein_w() ? make_plan1d_bluestein(g.Lw, g.work_w) : make_plan1d(g.Lw);
     t.pairs = make_pair_table(t.pm);
     g.fast_rows = allow_fast ? fast_rows_lookup(g.Lw, max_kw) : FastRowsInfo();
     if (g.fast_rows.ok) t.fr = make_fast_rows_tables(g.fast_rows, t.pw);
@@ -245,6 +259,7 @@ inline SpectralRowsArgs spectral_rows_args(const Geometry& g, const Tables& t, c
     a.S = S; a.s_feat_stride = (size_t)g.rows * g.s_pitch; a.s_pitch = g.s_pitch;
     a.Y = Y; a.y_kernel_stride = g.y_elems_per_kernel(); a.y_pitch = g.y_pitch; a.wout = g.wout;
     a.F = g.F; a.fd = t.pw.desc; a.tw = d.tw_w;
+    a.acc_in_y = g.acc_in_y ? 1 : 0;
     return a;
 }
 

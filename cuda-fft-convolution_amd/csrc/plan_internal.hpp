@@ -239,7 +239,7 @@ struct fftconv_plan {
     long prof_units[PK_COUNT] = {0, 0, 0, 0, 0};
 
     size_t cols_lds() const { return (size_t)g.T_cols * g.lds_pitch * sizeof(c32); }
-    size_t rows_lds() const { return (size_t)g.Lw * sizeof(c32) * (g.F > 1 ? 2 : 1); }
+    size_t rows_lds() const { return g.rows_lds_bytes(); }
 
     int prof_begin(int kind, long units) {
         prof_open = profile && ((profile_mask >> kind) & 1u);

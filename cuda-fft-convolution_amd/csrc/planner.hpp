@@ -11,12 +11,16 @@
 // cfg2 (window 1088) and cfg4 (window 4160) run on 1152 / 4224 and crop.
 #pragma once
 #include <cmath>
+#include <complex>
+#include <cstddef>
 #include <vector>
 
 #include "fc_common.hpp"
 #include "fft_lds.hpp"
 
 namespace fc {
+
+constexpr size_t FC_LDS_BUDGET = 160 * 1024;  // bytes of LDS one workgroup may claim (gfx950 CU)
 
 inline int fft_size16(int n) {  // src/cudaConvFFTData.h:96-102
     int mod = n / 16, rem = n % 16;
@@ -173,6 +177,86 @@ inline Plan1D make_plan1d_seq(int L, const std::vector<int>& radices) {
 }
 
 inline Plan1D make_plan1d(int L) { return make_plan1d_seq(L, factorize(L)); }
+
+// ---- Bluestein (chirp-z) transforms: any length N, for exact-window plans whose window does not factor -----------------
+//
+// X[k] = w[k] * sum_n (x[n] w[n]) conj(w[k - n]),  w[n] = exp(-i pi n^2 / N): a linear convolution of N chirped samples
+// with the chirp, run as a circular one of a supported work length L' >= 2N - 1 (fft_lds.hpp: fft_forward /
+// fft_inverse with FftDesc::bs_work > 0).  The inverse is the same computation conjugated.
+
+// Largest work length whose sequence fits the LDS budget in both generic passes: one column at the column pitch
+// (lds_col_pitch(L' - 1) == 2 mod 16, >= L') and one row of L' (20466 of the 20480 c32 of 160 KiB).
+constexpr int FC_BS_MAX_WORK = (int)(FC_LDS_BUDGET / 8) - 14;
+
+// Cheapest supported work length >= 2N - 1 within `cap` (-1 if none).
+inline int bluestein_work_length(int N, int cap = FC_BS_MAX_WORK) {
+    if (N < 2 || 2 * N - 1 > cap) return -1;
+    return choose_length(2 * N - 1, false, 0, LengthPrefs(), cap);
+}
+
+// Length N can be transformed: directly (length_supported) or by Bluestein within the LDS budget.
+inline bool length_transformable(int N, int cap = FC_BS_MAX_WORK) { return length_supported(N) || bluestein_work_length(N, cap) > 0; }
+
+// Forward DFT in double of a length whose prime factors are all small (host only: the Bluestein filter spectrum at
+// plan creation).  Recursive decimation in time over the smallest prime factor; root[j] = exp(-2 pi i j / n0), the
+// sub-transforms of length n use every (n0 / n)-th entry.
+inline void host_fft_rec(const std::complex<double>* in, size_t istride, int n, std::complex<double>* out,
+                         const std::vector<std::complex<double>>& root, int rstride) {
+    if (n == 1) { out[0] = in[0]; return; }
+    int p = 2;
+    while (n % p) p++;
+    const int m = n / p;
+    for (int r = 0; r < p; r++) host_fft_rec(in + r * istride, istride * p, m, out + (size_t)r * m, root, rstride * p);
+    std::vector<std::complex<double>> t(p), y((size_t)n);
+    for (int k = 0; k < m; k++)
+        for (int q = 0; q < p; q++) {
+            const int kk = k + q * m;
+            std::complex<double> s = 0.0;
+            for (int r = 0; r < p; r++) s += out[(size_t)r * m + k] * root[(size_t)((long long)r * kk % n) * rstride];
+            y[kk] = s;
+        }
+    for (int k = 0; k < n; k++) out[k] = y[k];
+}
+
+inline std::vector<std::complex<double>> host_fft(const std::vector<std::complex<double>>& x) {
+    const int n = (int)x.size();
+    std::vector<std::complex<double>> root(n), out(n);
+    for (int j = 0; j < n; j++) root[j] = std::polar(1.0, -2.0 * M_PI * (double)j / (double)n);
+    if (n > 0) host_fft_rec(x.data(), 1, n, out.data(), root, 1);
+    return out;
+}
+
+// N-point plan by Bluestein over the work length Lb (bluestein_work_length): natural order in and out (pos is the
+// identity), so the spectrum rows / columns of such a direction are in natural order.  The chirp and the filter are
+// appended to the stage twiddles of the Lb-point plan: one table per direction, uploaded as before.
+inline Plan1D make_plan1d_bluestein(int N, int Lb) {
+    Plan1D p = make_plan1d(Lb);
+    p.L = N;
+    p.desc.L = N;
+    p.desc.bs_work = Lb;
+    std::vector<std::complex<double>> w(N);
+    for (int n = 0; n < N; n++) {   // n^2 mod 2N in 64-bit integers: exp(-i pi n^2 / N) has period 2N in n^2
+        const long long q = (long long)n * n % (2LL * N);
+        w[n] = std::polar(1.0, -M_PI * (double)q / (double)N);
+    }
+    p.desc.bs_chirp_off = (int)p.tw.size();
+    for (int n = 0; n < N; n++) p.tw.push_back(mk((float)w[n].real(), (float)w[n].imag()));
+    std::vector<std::complex<double>> b(Lb, 0.0);   // conj w[|n|] for -N < n < N, wrapped mod Lb
+    for (int n = 0; n < N; n++) {
+        b[n] = std::conj(w[n]);
+        if (n) b[Lb - n] = std::conj(w[n]);
+    }
+    const std::vector<std::complex<double>> B = host_fft(b);
+    p.desc.bs_filt_off = (int)p.tw.size();
+    p.tw.resize(p.tw.size() + Lb);
+    for (int k = 0; k < Lb; k++) {   // at the positions where the Lb-point forward transform leaves bin k
+        const std::complex<double> v = B[k] / (double)Lb;
+        p.tw[p.desc.bs_filt_off + p.pos[k]] = mk((float)v.real(), (float)v.imag());
+    }
+    p.pos.resize(N);
+    for (int k = 0; k < N; k++) p.pos[k] = k;
+    return p;
+}
 
 // Pair table for the real <-> half-complex conversion around a complex transform of length M
 // (real length N = 2M).  Entry 0 is the DC/Nyquist item (a = pos(0), b = M: the extra slot);

@@ -8,8 +8,9 @@
 // this gateway does the same: the spectrum is exported in cuFFT's [f][FFT_W][FFT_H/2+1] order
 // (fftconv_plan_export_spectrum) into a fresh gpuArray that MATLAB owns -- it can be inspected,
 // edited, saved, and handed to cudaConvFFTData, exactly like the reference's.
-// Alternative form (always available, and the fallback where the window has no transform of its own
-// size): the spectrum stays inside an engine plan and `fftData` is an opaque uint64 handle to it,
+// Alternative form (always available, and the fallback where the window is too large for a transform of
+// its own size -- beyond the LDS; every ceil16 window up to 8448 has one, by Bluestein where it does not
+// factor into the radices): the spectrum stays inside an engine plan and `fftData` is an opaque uint64 handle to it,
 // also accepted by cudaConvFFTData -- cheaper when the same image meets many kernel cells (no
 // reordering per call): cudaFFTData(data, kH, kW, gpuId, 1).
 // Extension: cudaFFTData(fftData) with a single uint64 argument releases a handle early; handles
@@ -85,7 +86,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             return;
         }
         if (rc != FFTCONV_ERR_UNSUPPORTED_SIZE) mexErrMsgIdAndTxt(FFTCONV_MEX_ERROR_ID, "%s", fftconv_last_error());
-        // the window itself has no supported transform: fall through to the handle form
+        // the window is too large for a transform of its own size: fall through to the handle form
     }
 #else
     (void)as_handle;

@@ -199,8 +199,12 @@ typedef struct fftconv_plan_options {
                          *    with block transforms of at most this size (see `blockwise`) */
     int exact_window;   /* 1: the transform lengths must be the ceil16 window FFT_H x FFT_W itself (the
                          *    reference's circular modulus, plan_info.exact_window = 1) -- what
-                         *    fftconv_plan_export_spectrum / _import_spectrum need; creation fails with
-                         *    FFTCONV_ERR_UNSUPPORTED_SIZE when the window has a prime factor above 17 */
+                         *    fftconv_plan_export_spectrum / _import_spectrum need.  Any window works
+                         *    whose transforms fit the LDS, every ceil16 window up to 8448 included: a
+                         *    window length (FFT_W, or FFT_H / 2 for the real h transform) with a prime
+                         *    factor above 17 runs Bluestein (chirp-z) transforms of a work length
+                         *    >= 2 x that length on the generic kernels (slower than the specialised
+                         *    ones).  Larger windows fail with FFTCONV_ERR_UNSUPPORTED_SIZE. */
     int blockwise;      /* 0 (default): the plan convolves block-wise where that is needed or faster -- padded sizes beyond one
                          *    LDS-resident transform pass (about 20 000 samples along w) or beyond max_transform, and sizes whose
                          *    one-pass transform would run on the slower long-transform kernels (from about 4900 x 4900 with
