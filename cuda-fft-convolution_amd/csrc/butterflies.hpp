@@ -3,10 +3,18 @@
 // Dft<R, SGN>::run(v) replaces v[0..R) by its DFT with kernel exp(SGN*2*pi*i*j*k/R), natural
 // order in and out (SGN = -1 forward, +1 unnormalised inverse).  All indices are compile-time
 // so the arrays live in VGPRs.  Odd primes use the symmetric-pair form (O(R^2/2) FMAs, fine up
-// to 17 for an HBM-bound transform); composites are built by Cooley-Tukey in registers.
+// to 17 for an HBM-bound transform); composites with coprime factors (6, 10, 12, 14, 18, 20, 22,
+// 24, 26, ...) use the prime-factor algorithm, which needs no twiddles between its two stages;
+// prime powers (4, 8, 16, 9, ...) are built by Cooley-Tukey in registers.
 #pragma once
+#include <type_traits>
 #include "dft_consts.hpp"
 #include "fc_common.hpp"
+
+// FC_DFT_PFA = 0: every composite by Cooley-Tukey (the form before the prime-factor butterflies; A/B builds)
+#ifndef FC_DFT_PFA
+#define FC_DFT_PFA 1
+#endif
 
 namespace fc {
 
@@ -231,14 +239,104 @@ struct DftCTnz {
     }
 };
 
+// Prime-factor (Good-Thomas) form of R = A*B, gcd(A, B) = 1.  Input map n = CRT(a, b) (n = a mod A, n = b mod B), output
+// map k = (ka*B + kb*A) mod R.  Then w_R^{nk} = w_A^{a ka} w_B^{b kb}: a 2-D DFT of A-point transforms over a and B-point
+// transforms over b with no twiddles between them and the plain roots of A and B inside.  Both maps are compile-time
+// register renamings.  This way round (not a Ruritanian input map) an input n < B sits at b = n, which the pruned form uses.
+template <int A, int B, int SGN>
+struct DftPFA {
+    static constexpr int R = A * B;
+    static constexpr int in_idx(int a, int b) {
+        int n = 0;
+        while (n % A != a || n % B != b) ++n;
+        return n;
+    }
+    static constexpr int out_idx(int ka, int kb) { return (ka * B + kb * A) % R; }
+
+    static FC_HD void run(c32 (&v)[R]) {
+        c32 y[R];   // y[ka * B + b]: the A-point transforms
+        static_for<0, B>([&](auto b_) {
+            constexpr int b = decltype(b_)::value;
+            c32 t[A];
+            static_for<0, A>([&](auto a_) {
+                constexpr int a = decltype(a_)::value, n = in_idx(a, b);
+                t[a] = v[n];
+            });
+            Dft<A, SGN>::run(t);
+            static_for<0, A>([&](auto k_) {
+                constexpr int k = decltype(k_)::value;
+                y[k * B + b] = t[k];
+            });
+        });
+        second_stage<B>(v, y);
+    }
+
+    // v[NZ..R) zero, NZ <= B: A-point transform b has the one input n = b (a = b mod A) for b < NZ and none for b >= NZ, so
+    // its outputs are x * w_A^{a k} (copies when a = 0), and the B-point transforms see non-zero inputs only at b < NZ.
+    template <int NZ>
+    static FC_HD void run_nz(c32 (&v)[R]) {
+        static_assert(NZ >= 1 && NZ <= B, "pruned prime-factor form: the non-zero inputs must lie in [0, B)");
+        c32 y[R];
+        static_for<0, NZ>([&](auto b_) {
+            constexpr int b = decltype(b_)::value;
+            const c32 x = v[b];
+            static_for<0, A>([&](auto k_) {
+                constexpr int k = decltype(k_)::value;
+                y[k * B + b] = mul_root<A, (b % A) * k, SGN>(x);
+            });
+        });
+        second_stage<NZ>(v, y);
+    }
+
+  private:
+    // the B-point transforms over y[ka * B + b], b < NZ (the rest structural zeros), to v in output order
+    template <int NZ>
+    static FC_HD void second_stage(c32 (&v)[R], const c32 (&y)[R]) {
+        static_for<0, A>([&](auto ka_) {
+            constexpr int ka = decltype(ka_)::value;
+            c32 t[B];
+            static_for<0, B>([&](auto b_) {
+                constexpr int b = decltype(b_)::value;
+                if constexpr (b < NZ) t[b] = y[ka * B + b];
+                else t[b] = mk(0.f, 0.f);
+            });
+            if constexpr (NZ < B) Dft<B, SGN>::template run_nz<NZ>(t);
+            else Dft<B, SGN>::run(t);
+            static_for<0, B>([&](auto kb_) {
+                constexpr int kb = decltype(kb_)::value, k = out_idx(ka, kb);
+                v[k] = t[kb];
+            });
+        });
+    }
+};
+
+constexpr int gcd_c(int a, int b) { return b == 0 ? a : gcd_c(b, a % b); }
+// The first factor A of the prime-factor split of r: the smaller of (the power of r's smallest prime in r, the rest),
+// 0 for a prime power.  The smaller factor first puts the larger one in the second stage, where the pruned form
+// (run_nz: NZ <= B) applies.  Radices with three or more distinct primes split the same way (the composite factor is
+// then a prime-factor form itself).
+constexpr int pfa_first(int r) {
+    int p = 2;
+    while (r % p != 0) ++p;
+    int q = 1;
+    while (r % (q * p) == 0) q *= p;
+    return q == r ? 0 : (q < r / q ? q : r / q);
+}
+
 template <int R, int SGN>
 struct Dft<R, SGN, std::enable_if_t<(R > 4) && !is_prime(R)>> {
     static constexpr int F1 = smallest_factor(R), F2 = R / smallest_factor(R);
-    static FC_HD void run(c32 (&v)[R]) { DftCT<F1, F2, SGN>::run(v); }
+    static constexpr int PA = FC_DFT_PFA ? pfa_first(R) : 0, PB = PA ? R / PA : 0;
+    static_assert(PA == 0 || gcd_c(PA, PB) == 1, "prime-factor split needs coprime factors");
+    static FC_HD void run(c32 (&v)[R]) {
+        if constexpr (PA > 0) DftPFA<PA, PB, SGN>::run(v);
+        else DftCT<F1, F2, SGN>::run(v);
+    }
     template <int NZ>
     static FC_HD void run_nz(c32 (&v)[R]) {
-        if constexpr (NZ >= 1 && NZ <= F2) DftCTnz<F1, F2, SGN, NZ>::run(v);
-        else DftCT<F1, F2, SGN>::run(v);
+        if constexpr (PA > 0 && NZ >= 1 && NZ <= PB) DftPFA<PA, PB, SGN>::template run_nz<NZ>(v);
+        else if constexpr (NZ >= 1 && NZ <= F2) DftCTnz<F1, F2, SGN, NZ>::run(v);
+        else run(v);
     }
 };
 
