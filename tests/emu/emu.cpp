@@ -75,6 +75,28 @@ int emu_image_spectrum(const float* data, int H, int W, int F, int max_kh, int m
     return 0;
 }
 
+// The image spectrum in the reference's order (what fftconv_plan_export_spectrum returns for an exact_window plan):
+// complex [F][FFT_W][FFT_H/2+1], unnormalised -- the plan's natural-order tables applied as k_spectrum_reorder applies them.
+int emu_export_spectrum(const float* data, int H, int W, int F, int max_kh, int max_kw, float* nat_out) {
+    Geometry g;
+    Tables t;
+    if (!make_geometry(g, t, H, W, F, max_kh, max_kw, g_tune)) return -1;
+    if (!g.exact_window) return -10;
+    std::vector<float> spec(2 * g.spectrum_elems());
+    if (int rc = emu_image_spectrum(data, H, W, F, max_kh, max_kw, spec.data())) return rc;
+    const c32* S = reinterpret_cast<const c32*>(spec.data());
+    c32* nat = reinterpret_cast<c32*>(nat_out);
+    const float norm = (float)((double)g.Lh * (double)g.Lw);
+    const size_t s_plane = (size_t)g.rows * g.s_pitch;
+    for (int f = 0; f < F; f++)
+        for (int x = 0; x < g.fft_w; x++)
+            for (int y = 0; y < g.rows; y++) {
+                const c32 v = S[f * s_plane + t.nat_col_of[x] + (size_t)t.nat_row_of[y] * g.s_pitch];
+                nat[((size_t)f * g.fft_w + x) * g.rows + y] = mk(norm * v.x, norm * v.y);
+            }
+    return 0;
+}
+
 // Per-kernel loop from a given spectrum (what fftconv_plan_convolve does).
 int emu_convolve_spectrum(const float* spec, int H, int W, int F, int max_kh, int max_kw, int n_kernel,
                           const float* const* kernels, const int* kh, const int* kw, float* const* out) {

@@ -152,3 +152,59 @@ def synth(cfg_seed, H, W, F, kh, kw, n):
     img = np.random.default_rng(1234 + cfg_seed).random((H, W, F), dtype=np.float32)
     ks = [np.random.default_rng(5678 + cfg_seed + k).random((kh, kw, F), dtype=np.float32) for k in range(n)]
     return np.asfortranarray(img), [np.asfortranarray(k) for k in ks]
+
+
+def accuracy(out, ref):
+    """(max-normalised, L2-relative, spectral) error of a map against its float64 reference:
+    max|e| / max|ref|, ||e||_2 / ||ref||_2 and max_k |FFT(e)_k| / rms_k |FFT(ref)_k|.  The last is the largest error of
+    any one frequency bin against a typical bin of the reference (rms_k |FFT(ref)_k| = ||ref||_2 by Parseval): the metric
+    that sees a wrong twiddle or a misplaced output bin, which max / L2 norms of a map dilute over all its bins."""
+    r = np.asarray(ref, dtype=np.float64)
+    e = np.asarray(out, dtype=np.float64) - r
+    nr = max(float(np.sqrt(np.sum(r * r))), 1e-300)
+    return (float(np.abs(e).max() / max(np.abs(r).max(), 1e-300)),
+            float(np.sqrt(np.sum(e * e)) / nr),
+            float(np.abs(np.fft.rfft2(e)).max() / nr))
+
+
+def normal_inputs(shape, seed):
+    """zero-mean inputs for the accuracy budgets: image and kernels standard normal, so no DC bin dominates the maps.
+    shape = (H, W, F, kh, kw, n); with n > 1 the second kernel is a ragged cell (shorter and narrower than the maximum)."""
+    H, W, F, kh, kw, n = shape
+    rng = np.random.default_rng(seed)
+    data = np.asfortranarray(rng.standard_normal((H, W, F), dtype=np.float32))
+    ks = [rng.standard_normal((kh, kw, F), dtype=np.float32) for _ in range(n)]
+    if n > 1:
+        ks[1] = rng.standard_normal((max(1, kh - 1), max(1, kw // 4), F), dtype=np.float32)
+    return data, [np.asfortranarray(k) for k in ks]
+
+
+# Accuracy budgets: bars for accuracy() = (max-normalised, L2-relative, spectral) of an fp32 map against its float64 reference
+# on normal_inputs.  Each bar is at most 4x the worst value of its class measured on the clean tree through the host emulator
+# (tests/emu, the kernel bodies under g++); tests/test_accuracy_host.py and test_accuracy_gpu.py apply them, one set for both:
+# the MI355X's worst value of each class and metric (test_accuracy_gpu.py, quoted per class below) is at most 1.1x the emulator's.
+# Direct transforms (every prime factor <= 17; generic and specialised kernels, every length of fast_paths.hpp along h and w,
+# path modes 0 / 1 / 2, F = 1 / 3, 2-D maps up to 2112 x 2112): worst 8.1e-7 max-normalised (16 x 8448 rows, F = 3), 5.0e-7
+# L2 and 4.2e-6 spectral (1088 x 1088 on the native-window kernels).  The R1 = 16 row configurations (2560, 3072, 5632, 6144,
+# 7680, 8448) sit at about 1.5x the L2 of the R1 = 8 ones (4e-7 against 2.8e-7): their stage-1 power chains reach w^15.
+# MI355X: 5.3e-7 max-normalised, 4.9e-7 L2, 3.3e-6 spectral, all at 1088 x 1088.
+BUDGET_DIRECT = (3e-6, 1.5e-6, 1.2e-5)
+# Bluestein (chirp-z) windows, exact_window plans (304, 592, 1712, 8368 along h and w; 304 x 368, 1712 x 1712): worst 6.0e-7
+# max-normalised, 6.0e-7 L2, 4.9e-6 spectral, all at 1712 x 1712.  About 1.2x direct lengths of the same size: the work
+# transforms are >= 2N - 1 points long, in fp32.  MI355X: 6.1e-7 / 5.7e-7 / 5.0e-6, at 1712 x 1712.
+BUDGET_BLUESTEIN = (2e-6, 1.6e-6, 1.5e-5)
+# Full 2-D maps on the long specialised configurations: 4224^2 (4096^2, 127^2 kernels) 4.5e-7 / 3.9e-7 / 3.3e-6, 6144^2
+# (6000^2, 63^2) 6.8e-7 / 5.4e-7 / 4.8e-6, 8448^2 (8192^2, 127^2) 6.9e-7 / 5.0e-7 / 5.0e-6.  MI355X: 4224^2 4.5e-7 / 3.7e-7 /
+# 3.9e-6, 6144^2 7.1e-7 / 5.3e-7 / 5.2e-6, 8448^2 6.2e-7 / 4.7e-7 / 4.0e-6 (default plan at 8192^2: 6.7e-7 / 5.0e-7 / 4.9e-6).
+BUDGET_LARGE = (2.5e-6, 2e-6, 2e-5)
+# The image spectrum of an exact_window plan in the reference's order against numpy.fft.rfft2 in float64, per bin:
+# max_k |S_k - ref_k| / rms_k |ref_k|.  Worst 1.4e-6 (1088 x 1088 on the native-window kernels), Bluestein 1.3e-6 (1712 x 1712);
+# MI355X 1.35e-6 and 1.39e-6.
+BUDGET_SPECTRUM_BIN = 5e-6
+
+
+def spectrum_bin_error(got, want):
+    """max_k |got_k - want_k| / rms_k |want_k| over complex spectra: the worst bin against a typical one"""
+    want = np.asarray(want, dtype=np.complex128)
+    e = np.asarray(got, dtype=np.complex128) - want
+    return float(np.abs(e).max() / max(float(np.sqrt(np.mean(np.abs(want) ** 2))), 1e-300))
