@@ -7,6 +7,7 @@
 // in the CPU-only test tier.  It is NOT part of the product: libfftconv.so has no CPU path and
 // never links or loads this file.
 #include <cstdio>
+#include <algorithm>
 #include <cstring>
 #include <vector>
 
@@ -112,53 +113,69 @@ int emu_convolve_spectrum(const float* spec, int H, int W, int F, int max_kh, in
     HostCtx ctx;
     std::vector<c32> lds(FC_LDS_BUDGET / sizeof(c32));
     const c32* S = reinterpret_cast<const c32*>(spec);
-    std::vector<c32> Y(g.y_elems_per_kernel());
-    for (int k = 0; k < n_kernel; k++) {
-        if (kh[k] < 1 || kw[k] < 1 || kh[k] > g.fft_h || kw[k] > g.fft_w) return -2;
-        if ((kh[k] > max_kh || kw[k] > max_kw) && !(g.exact_window && kh[k] <= g.Lh && kw[k] <= g.Lw)) return -3;
-        std::vector<c32> A((size_t)F * g.rows * a_pitch_for(kw[k]));
-        for (auto& v : A) v = mk(1e30f, -1e30f);
-        for (auto& v : Y) v = mk(1e30f, -1e30f);
-        if (g.fast_fwd) {
-            d.fc_tw1 = t.fcl.tw1.data(); d.fc_tw2 = t.fcl.tw2.data(); d.fc_pairs = t.fcl.pairs.data();
-            FastColsFwdArgs fa = fast_cols_fwd_args(g, d, kernels[k], (size_t)kh[k] * kw[k], kh[k], kh[k], kw[k], F, A.data(),
-                                                    (size_t)g.rows * a_pitch_for(kw[k]), a_pitch_for(kw[k]), true);
-            EmuFastColsFwd run{fa, lds.data(), 2};
-            if (!run_fast_cols_fwd(g.M, g.fast_cols.T, fast_cols_fwd_pruned_ok(g.fast_cols, kh[k]), run)) return -8;
-        } else {
-            ColsR2CArgs ka = kernel_cols_args(g, t, d, kernels[k], kh[k], kw[k], A.data());
-            for (int plane = 0; plane < F; plane++)
-                for (int tile = 0; tile < tiles_for(kw[k], g.T_cols); tile++) cols_r2c_body(ctx, lds.data(), ka, tile, plane);
+    const size_t y_elems = g.y_elems_per_kernel();
+    // groups of consecutive kernels of equal size, as fftconv_plan_convolve: one column-spectrum buffer A and one
+    // intermediate Y per group, and ONE row launch over the group (distinct kernels at their strides)
+    int k0 = 0;
+    while (k0 < n_kernel) {
+        int k1 = k0 + 1;
+        while (k1 < n_kernel && kh[k1] == kh[k0] && kw[k1] == kw[k0]) k1++;
+        const int nk = k1 - k0, khk = kh[k0], kwk = kw[k0];
+        if (khk < 1 || kwk < 1 || khk > g.fft_h || kwk > g.fft_w) return -2;
+        if ((khk > max_kh || kwk > max_kw) && !(g.exact_window && khk <= g.Lh && kwk <= g.Lw)) return -3;
+        const size_t per_a = (size_t)F * g.rows * a_pitch_for(kwk);
+        std::vector<c32> A(per_a * nk, mk(1e30f, -1e30f));
+        std::vector<c32> Y(y_elems * nk, mk(1e30f, -1e30f));
+        for (int j = 0; j < nk; j++) {
+            c32* Aj = A.data() + per_a * j;
+            if (g.fast_fwd) {
+                d.fc_tw1 = t.fcl.tw1.data(); d.fc_tw2 = t.fcl.tw2.data(); d.fc_pairs = t.fcl.pairs.data();
+                FastColsFwdArgs fa = fast_cols_fwd_args(g, d, kernels[k0 + j], (size_t)khk * kwk, khk, khk, kwk, F, Aj,
+                                                        (size_t)g.rows * a_pitch_for(kwk), a_pitch_for(kwk), true);
+                EmuFastColsFwd run{fa, lds.data(), 2};
+                if (!run_fast_cols_fwd(g.M, g.fast_cols.T, fast_cols_fwd_pruned_ok(g.fast_cols, khk), run)) return -8;
+            } else {
+                ColsR2CArgs ka = kernel_cols_args(g, t, d, kernels[k0 + j], khk, kwk, Aj);
+                for (int plane = 0; plane < F; plane++)
+                    for (int tile = 0; tile < tiles_for(kwk, g.T_cols); tile++) cols_r2c_body(ctx, lds.data(), ka, tile, plane);
+            }
         }
         if (g.fast_cols.ok) d.fc_pair_row_of = t.fcl.pair_row_of.data();
         if (g.fast_rows.ok) {
-            if (kw[k] > g.fast_rows.max_kw) return -4;
+            if (kwk > g.fast_rows.max_kw) return -4;
             d.fr_tw1 = t.fr.tw1.data();
             d.fr_tw2 = t.fr.tw2.data();
-            FastRowsArgs fa = fast_rows_args(g, d, A.data(), kw[k], S, Y.data());
-            EmuFastRows run{fa, lds.data(), g.rows, (g.rows_multi_ok() && g.rows_group > 1) ? g.rows_group : 0};
-            if (!run_fast_rows(g.Lw, fast_rows_nz2(g, kw[k]), run)) return -5;
+            FastRowsArgs fa = fast_rows_args(g, d, A.data(), kwk, S, Y.data());
+            EmuFastRows run{fa, lds.data(), g.rows, (g.rows_multi_ok() && g.rows_group > 1) ? std::min(g.rows_group, nk) : 0, nk};
+            if (!run_fast_rows(g.Lw, fast_rows_nz2(g, kwk), run)) return -5;
         } else {
-            SpectralRowsArgs sa = spectral_rows_args(g, t, d, A.data(), kw[k], S, Y.data());
-            for (int r = 0; r < g.rows; r++) spectral_rows_body(ctx, lds.data(), sa, r, 0);
-        }
-        if (g.fast_cols.ok) {
-            d.fc_tw1 = t.fcl.tw1.data();
-            d.fc_tw2 = t.fcl.tw2.data();
-            d.fc_pairs = t.fcl.pairs.data();
-            d.fc_rowoff = t.fcl.rowoff.data();
-            FastColsArgs fa = fast_cols_args(g, d, Y.data(), out[k], 0, 1);
-            if (g_win.on) {
-                fa.h_lo = g_win.h_lo; fa.fft_h = g_win.h_hi; fa.w_first = g_win.w_first; fa.out_pitch = g_win.pitch;
-                fa.tiles_per_kernel = g_win.ncols / g.fast_cols.T; fa.ntiles = fa.tiles_per_kernel;
+            for (int j = 0; j < nk; j++) {
+                SpectralRowsArgs sa = spectral_rows_args(g, t, d, A.data() + per_a * j, kwk, S, Y.data() + y_elems * j);
+                for (int r = 0; r < g.rows; r++) spectral_rows_body(ctx, lds.data(), sa, r, 0);
             }
-            EmuFastCols run{fa, lds.data(), 3};   // 3 persistent workgroups share the tiles
-            if (!run_fast_cols(g.M, g.fast_cols.T, run)) return -6;
-        } else {
-            if (g_win.on) return -7;
-            ColsC2RArgs ca = cols_c2r_args(g, t, d, Y.data(), out[k], 0);
-            for (int tile = 0; tile < tiles_for(g.fft_w, g.T_cols); tile++) cols_c2r_body(ctx, lds.data(), ca, tile, 0);
         }
+        for (int j = 0; j < nk; j++) {
+            const c32* Yj = Y.data() + y_elems * j;
+            float* outj = out[k0 + j];
+            if (g.fast_cols.ok) {
+                d.fc_tw1 = t.fcl.tw1.data();
+                d.fc_tw2 = t.fcl.tw2.data();
+                d.fc_pairs = t.fcl.pairs.data();
+                d.fc_rowoff = t.fcl.rowoff.data();
+                FastColsArgs fa = fast_cols_args(g, d, Yj, outj, 0, 1);
+                if (g_win.on) {
+                    fa.h_lo = g_win.h_lo; fa.fft_h = g_win.h_hi; fa.w_first = g_win.w_first; fa.out_pitch = g_win.pitch;
+                    fa.tiles_per_kernel = g_win.ncols / g.fast_cols.T; fa.ntiles = fa.tiles_per_kernel;
+                }
+                EmuFastCols run{fa, lds.data(), 3};   // 3 persistent workgroups share the tiles
+                if (!run_fast_cols(g.M, g.fast_cols.T, run)) return -6;
+            } else {
+                if (g_win.on) return -7;
+                ColsC2RArgs ca = cols_c2r_args(g, t, d, Yj, outj, 0);
+                for (int tile = 0; tile < tiles_for(g.fft_w, g.T_cols); tile++) cols_c2r_body(ctx, lds.data(), ca, tile, 0);
+            }
+        }
+        k0 = k1;
     }
     return 0;
 }
@@ -216,6 +233,26 @@ int emu_uses_fast_rows(int H, int W, int F, int max_kh, int max_kw) {
     Tables t;
     if (!make_geometry(g, t, H, W, F, max_kh, max_kw, g_tune)) return -1;
     return (g.fast_rows.ok ? 1 : 0) | (g.fast_cols.ok ? 2 : 0);
+}
+
+// the plan's w direction: bit 0 a Bluestein row transform, bit 1 the feature sum kept in the intermediate (acc_in_y); -1 no plan
+int emu_plan_rows_form(int H, int W, int F, int max_kh, int max_kw) {
+    Geometry g;
+    Tables t;
+    if (!make_geometry(g, t, H, W, F, max_kh, max_kw, g_tune)) return -1;
+    return (g.bluestein_w() ? 1 : 0) | (g.acc_in_y ? 2 : 0);
+}
+
+// the specialised row configurations as compiled (fast_paths.hpp: FC_FAST_ROW_CONFIGS): (L, NZ2) of each, in the listed
+// order, into L[] / nz2[] (at most `max`); returns how many there are
+int emu_row_configs(int* L, int* nz2, int max) {
+    int n = 0;
+#define FC_X(LL, A, B, C, NTT, RP, NZ)    \
+    if (n < max) { L[n] = LL; nz2[n] = NZ; } \
+    n++;
+    FC_FAST_ROW_CONFIGS(FC_X)
+#undef FC_X
+    return n;
 }
 
 // the planner alone (no preference for lengths with specialised kernels)

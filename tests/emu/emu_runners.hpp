@@ -44,29 +44,30 @@ struct EmuFastRows {
     const FastRowsArgs& a;
     c32* lds;
     int rows;
-    int group = 0;   // > 1: multi-map body; the emulator holds one kernel at a time, so the walk
-                     // over `group` maps is emulated with the same kernel (strides 0): the loop,
-                     // the prefetch slot and the LDS reuse are exercised, the indexing is not
+    int group = 0;     // > 1: multi-map body, walks of `group` consecutive kernels per workgroup (the product's kernels_per_wg)
+    int kernels = 1;   // kernels of the launch: their column spectra at a.A + k * a_kernel_stride, their rows of the
+                       // intermediate at a.Y + k * y_kernel_stride (as a launch of the product: every workgroup walks
+                       // DISTINCT kernels, so the walk's indexing is exercised, the last walk partial where `group`
+                       // does not divide `kernels`)
     template <class Cfg, int NZ2>
     void go() {
-        {   // (always the walk over maps / (map, feature) pairs, as the product's launchers: a walk of one map where group <= 1)
-            const int group = this->group > 1 ? this->group : 1;
-            FastRowsArgs b = a;
-            b.a_kernel_stride = 0;
-            b.y_kernel_stride = 0;
+        // (always the walk over maps / (map, feature) pairs, as the product's launchers: walks of one map where group <= 1)
+        const int per_wg = group > 1 ? group : 1;
+        // (as the product's launcher: LINEAR is the only variant of a configuration whose m1 is a whole number of tiles)
+        constexpr bool ALWAYS_LINEAR = (2 * Cfg::m1) % FC_Y_TILE_W == 0;
+        const bool linear = ALWAYS_LINEAR || fast_rows_multi_linear(a, Cfg::L, Cfg::m1);
+        for (int kernel0 = 0; kernel0 < kernels; kernel0 += per_wg) {
+            const int nk = kernels - kernel0 < per_wg ? kernels - kernel0 : per_wg;
             for (int grp = 0; grp < (rows + Cfg::RPW - 1) / Cfg::RPW; grp++) {
                 for (int i = 0; i < Cfg::LDS_ELEMS; i++) lds[i] = mk(1e30f, -1e30f);
-                // (as the product's launcher: LINEAR is the only variant of a configuration whose m1 is a whole number of tiles)
-                constexpr bool ALWAYS_LINEAR = (2 * Cfg::m1) % FC_Y_TILE_W == 0;
-                const bool linear = ALWAYS_LINEAR || fast_rows_multi_linear(b, Cfg::L, Cfg::m1);
                 if (a.F > 1) {   // the walk over (map, feature) pairs
                     HostPhaseCtx<RowMultiState<Cfg, true>> ctx(Cfg::NT);
-                    if (linear) fast_rows_multi_body<Cfg, NZ2, true, true>(ctx, lds, b, grp, 0, group, rows);
-                    else if constexpr (!ALWAYS_LINEAR) fast_rows_multi_body<Cfg, NZ2, false, true>(ctx, lds, b, grp, 0, group, rows);
+                    if (linear) fast_rows_multi_body<Cfg, NZ2, true, true>(ctx, lds, a, grp, kernel0, nk, rows);
+                    else if constexpr (!ALWAYS_LINEAR) fast_rows_multi_body<Cfg, NZ2, false, true>(ctx, lds, a, grp, kernel0, nk, rows);
                 } else {
                     HostPhaseCtx<RowMultiState<Cfg>> ctx(Cfg::NT);
-                    if (linear) fast_rows_multi_body<Cfg, NZ2, true>(ctx, lds, b, grp, 0, group, rows);
-                    else if constexpr (!ALWAYS_LINEAR) fast_rows_multi_body<Cfg, NZ2, false>(ctx, lds, b, grp, 0, group, rows);
+                    if (linear) fast_rows_multi_body<Cfg, NZ2, true>(ctx, lds, a, grp, kernel0, nk, rows);
+                    else if constexpr (!ALWAYS_LINEAR) fast_rows_multi_body<Cfg, NZ2, false>(ctx, lds, a, grp, kernel0, nk, rows);
                 }
             }
         }

@@ -28,15 +28,17 @@ class _Child:
     out or takes the child down ends the child (killed, queued cases cancelled), and every later case fails at once: nothing
     more starts on the device after trouble."""
 
-    def __init__(self):
+    def __init__(self, cases=None):
+        """cases: the namespace the case functions are looked up in (a module's globals(); default: this module's)"""
         self.ex = concurrent.futures.ProcessPoolExecutor(max_workers=1, mp_context=multiprocessing.get_context("spawn"))
+        self.cases = globals() if cases is None else cases
         self.gone = None
 
     def __call__(self, name, *args):
         if self.gone:
             pytest.fail("the child process was stopped after %s" % self.gone)
         try:
-            return self.ex.submit(globals()[name], *args).result(timeout=CASE_TIMEOUT_S)
+            return self.ex.submit(self.cases[name], *args).result(timeout=CASE_TIMEOUT_S)
         except (concurrent.futures.TimeoutError, concurrent.futures.process.BrokenProcessPool) as e:
             self.gone = "%s in %s%s" % (type(e).__name__, name, args)
             self.kill()

@@ -4,7 +4,8 @@ inputs, measured three ways (util.accuracy: max-normalised, L2-relative, spectra
 The parity tests elsewhere compare max|error| / max|reference| on U[0,1) inputs, where a map is mostly its DC bin; a wrong
 twiddle, a misplaced output bin or a lost digit in one stage hides under that.  Here every transform length of the
 specialised tables runs along h and along w (path modes 0 / 1 / 2, F = 1 / 3), the Bluestein windows and the native 1088 /
-4160 windows run as exact_window plans, the plan variants run on 2-D maps, and the exported spectrum is checked bin by bin."""
+4160 windows run as exact_window plans, the plan variants run on 2-D maps, the multi-map row kernel walks distinct kernels at
+F = 1, 32 and 256, and the exported spectrum is checked bin by bin."""
 import ctypes
 import os
 import re
@@ -134,16 +135,49 @@ def test_two_dimensional_variants(emu, oracle, case):
     data, ks = util.normal_inputs(shape, sum(shape))
     if shape not in _REFS:
         _REFS[shape] = oracle.conv_fft(data, kh, kw, ks, f64=True)
+    refs = _REFS[shape]
+    if group > 1:     # walks of `group` maps over distinct kernels: three more full-size kernels after the first (4 = 3 + 1)
+        rng = np.random.default_rng(sum(shape) + 1)
+        extra = [np.asfortranarray(rng.standard_normal((kh, kw, F), dtype=np.float32)) for _ in range(3)]
+        if (shape, "walk") not in _REFS:
+            _REFS[(shape, "walk")] = oracle.conv_fft(data, kh, kw, extra, f64=True)
+        ks = ks[:1] + extra + ks[1:]
+        refs = refs[:1] + _REFS[(shape, "walk")] + refs[1:]
     emu.emu_set_tuning(mode, group)
     emu.emu_set_dynamic_tiles(opts.get("dynamic", 0))
     emu.emu_set_exact_window(opts.get("exact", 0))
     try:
         assert emu.emu_uses_fast_rows(H, W, F, kh, kw) == (0 if mode == 0 else 3)
-        check(util.BUDGET_DIRECT, emu_conv(emu, data, kh, kw, ks), _REFS[shape], name)
+        got = emu_conv(emu, data, kh, kw, ks)
+        assert len(got) == len(refs)
+        check(util.BUDGET_DIRECT, got, refs, name)
     finally:
         emu.emu_set_tuning(2, -1)
         emu.emu_set_dynamic_tiles(0)
         emu.emu_set_exact_window(0)
+
+
+# Multi-map walks over DISTINCT kernels: the emulator's row launch walks the equal-size kernels of a group at their real strides
+# (a_kernel_stride, y_kernel_stride), as the product's launch does.  Five kernels of one size walked 2 or 3 at a time (the last
+# walk partial) and a ragged one, exact_window plans 48 x L; F = 1, 32 and 256 (the feature sum over many planes).
+WALK_CASES = [(1, 3, 576), (32, 2, 288), (32, 3, 1152), (256, 3, 288), (256, 2, 384)]
+
+
+@pytest.mark.parametrize("F,walk,L", WALK_CASES, ids=["F%d-walk%d-L%d" % c for c in WALK_CASES])
+def test_walks_over_distinct_kernels(emu, F, walk, L):
+    H, W, kh, kw = 40, L - 40 - 3, 5, 40
+    rng = np.random.default_rng(F * 1000 + L)
+    data = np.asfortranarray(rng.standard_normal((H, W, F), dtype=np.float32))
+    ks = [np.asfortranarray(rng.standard_normal(s + (F,), dtype=np.float32)) for s in [(kh, kw)] * 5 + [(kh - 1, kw // 4)]]
+    emu.emu_set_exact_window(1)
+    emu.emu_set_tuning(2, walk)
+    try:
+        assert plan_lengths(emu, H, W, F, kh, kw) == (48, L) and emu.emu_uses_fast_rows(H, W, F, kh, kw) & 1
+        got = emu_conv(emu, data, kh, kw, ks)
+    finally:
+        emu.emu_set_tuning(2, -1)
+        emu.emu_set_exact_window(0)
+    check(util.BUDGET_DIRECT, got, util.numpy_fft_conv(data, kh, kw, ks), (F, walk, L))
 
 
 @pytest.mark.parametrize("shape", [

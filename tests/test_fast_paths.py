@@ -156,10 +156,13 @@ def test_emulated_fast_kernels_other_configs(emu, oracle, tuned, shape, mode):
                                    (300, 4096, 2, 20, 63, 1), (250, 280, 3, 9, 9, 2), (540, 500, 5, 37, 40, 1), (200, 2048, 2, 9, 63, 1)])
 def test_emulated_multi_map_row_kernel(emu, oracle, tuned, shape):
     """fast_rows_multi.hpp (several maps per workgroup): the walk, its prefetch slot and the LDS reuse
-    through the emulator (which repeats one kernel; distinct kernels per walk are a GPU test)"""
+    through the emulator, which walks the equal-size kernels of a launch as the product does: four full-size kernels
+    (walks of 3 over distinct kernels, 3 + 1) ahead of the shape's ragged cell, if it has one"""
     tuned((2, 3))
     H, W, F, kh, kw, n = shape
     data, ks = make_inputs(shape, 43)
+    rng = np.random.default_rng(44)
+    ks = ks[:1] + [rng.random((kh, kw, F), dtype=np.float32) for _ in range(3)] + ks[1:]
     rc, got = emu_conv(emu, data, kh, kw, ks)
     assert rc == 0
     for g, r in zip(got, oracle.conv_fft(data, kh, kw, ks)):
