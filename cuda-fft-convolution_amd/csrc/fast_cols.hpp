@@ -29,7 +29,7 @@ namespace fc {
 // the threads of odd blocks take their runs rotated by `rot` (the assignment of runs to threads is free: a stage-3 butterfly
 // works in place).  Both per configuration from tools/lds_bank_model.py, which counts the LDS cycles of every access of a tile
 // with the bank rules of the hardware (SQ_LDS_BANK_CONFLICT of the cfg3 kernel: model 27.4 %, measured 29.2 % of the LDS
-// cycles without the pad; model 6 % with it).  FC_COLS_NO_BLOCK_PAD = 1 (diagnostic builds): the dense image.
+// cycles without the pad; model 6 % with it).
 // X(M, R1, R2, R3, T, pad, rot): from `tools/lds_bank_model.py --search` (it lists a pad for every configuration of fast_paths.hpp:
 // 7-35 % fewer modelled LDS cycles per tile).  Only the configurations whose output kernel MEASURED faster on the padded image are
 // listed -- the kernel is bound by its memory stream, not by the LDS array, and a larger image is not free (same-box A/Bs of 4-6
@@ -45,7 +45,6 @@ namespace fc {
 
 struct ColLayout { int pad, rot; };
 constexpr ColLayout col_layout(int M, int R1, int R2, int R3, int T) {
-    if (FC_COLS_NO_BLOCK_PAD) return {0, 0};
 #define FC_X(MM, A, B, C, TT, PP, RR) \
     if (M == MM && R1 == A && R2 == B && R3 == C && T == TT) return {PP, RR};
     FC_COL_LAYOUTS(FC_X)
@@ -210,7 +209,7 @@ struct ColPairState {
 // 2468 -> 2202 us per 32 maps, M = 2560 1668 -> 1568; for R3 = 22 / 24 the NB3 form is 1-4 % slower than the 8 x 8 one.
 template <class C>
 FC_HD int pair_of_unit(int u) {
-    if constexpr (C::T == 4 && FC_COLS_PAIR_TRANSPOSE) {
+    if constexpr (C::T == 4) {
         constexpr int NP = C::M / 2 + 1, SB = 8 * C::NB3;
         constexpr int FULL = ((2 * C::R3) % 32 == 0) ? (NP / SB) * SB : 0;
         if (u < FULL) {
@@ -218,7 +217,7 @@ FC_HD int pair_of_unit(int u) {
             return sb * SB + (i & 7) * C::NB3 + (i >> 3);
         }
         return ((u | 63) < NP) ? ((u & ~63) | ((u & 7) << 3) | ((u >> 3) & 7)) : u;
-    } else if constexpr (C::T == 8 && FC_COLS_PAIR_TRANSPOSE >= 2 && (2 * C::m1) % 32 == 0) {
+    } else if constexpr (C::T == 8 && (2 * C::m1) % 32 == 0) {
         // 8-column tiles: 4 pairs x 4 column pairs per access group; where consecutive pairs collide on one bank (m1 cells a
         // multiple of the 32 banks: M = 2304, 2112 as 6.16.22, 1920, 1536, 1408, 1280) the 4 pairs of a group are taken NB3 apart
         constexpr int NP = C::M / 2 + 1, SB = 4 * C::NB3, FULL = (NP / SB) * SB;
@@ -312,9 +311,10 @@ FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int
     const int first_tile = dyn ? FC_UNIFORM(qs[1]) : tile_of(0);
     [[maybe_unused]] int cur_lo = cols_lo(0), cur_hi = cols_hi(0), nxt_lo = 0, nxt_hi = T;
 
-    // part: 0 = the whole gather; 1 / 2 (mode 3) = its first / second half of rounds -- a CU cannot
-    // keep a whole tile (135 KB) of loads in flight, so issuing it in one go stalls the waves in
-    // the issue itself; the second half is issued one phase later, while the first drains
+    // part: 0 = the whole gather (the first tile; every tile of the row-major intermediate); 1 / 2 / 3 = its first / second / last
+    // third of rounds, issued at the start of the tile, after stage 3 and ahead of the last round of stage 2 -- a CU cannot
+    // keep a whole tile (135 KB) of loads in flight, so issuing it in one go stalls the waves in the issue itself; each third
+    // is issued while the one before drains (in one go / halves / thirds: 28.3 / 27.4 / 27.2 us per map)
     auto issue_gather = [&](int t, State& st, int tile, auto part_, [[maybe_unused]] int c_lo, [[maybe_unused]] int c_hi) {
         constexpr int part = decltype(part_)::value;
         const int kernel = tile / g.tiles_per_kernel;
@@ -322,10 +322,8 @@ FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int
         if constexpr (PLAND) {   // rows 2p, 2p+1 = bins (p, M-p); one thread takes both for two columns
             const int tw = 1 << g.y_tile_shift;
             const c32* Yt = g.Y + (size_t)kernel * g.y_kernel_stride + (size_t)(w0 >> g.y_tile_shift) * g.y_tile_elems + (w0 & (tw - 1));
-            // parts: FC_COLS_SPLIT_GATHER == 1: halves (1, 2); == 2: thirds (1, 2, 3)
-            constexpr int NP = (FC_COLS_SPLIT_GATHER == 2) ? 3 : 2;
-            constexpr int RB = (part == 0) ? 0 : (State::RNDU * (part - 1) + NP - 1) / NP;
-            constexpr int RE = (part == 0) ? State::RNDU : (part == NP ? State::RNDU : (State::RNDU * part + NP - 1) / NP);
+            constexpr int RB = (part == 0) ? 0 : (State::RNDU * (part - 1) + 2) / 3;
+            constexpr int RE = (part == 0) ? State::RNDU : (State::RNDU * part + 2) / 3;
             static_for<RB, RE>([&](auto r_) {
                 constexpr int r = decltype(r_)::value;
                 const int e = t + NT * r;
@@ -362,17 +360,7 @@ FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int
                     const int pa = (int)(pp & 0xffffu), pb = (int)(pp >> 16);
                     c32* z0 = lds + (2 * t2) * LP;
                     c32* z1 = z0 + LP;
-                    c32x2 xa = st.pa[r], xb = st.pb[r];
-#if (FC_COLS_DBG & 32) && defined(__HIP_DEVICE_COMPILE__)
-                    // timing experiment: the arithmetic an inverse radix-8 w-stage would add while landing
-                    // (about 21 packed operations per unit of two rows x two columns)
-                    for (int dd = 0; dd < 5; dd++) {
-                        asm volatile("v_pk_fma_f32 %0, %0, %1, %2" : "+v"(xa.a) : "v"(xb.a), "v"(xa.b));
-                        asm volatile("v_pk_fma_f32 %0, %0, %1, %2" : "+v"(xa.b) : "v"(xb.b), "v"(xa.a));
-                        asm volatile("v_pk_fma_f32 %0, %0, %1, %2" : "+v"(xb.a) : "v"(xa.a), "v"(xb.b));
-                        asm volatile("v_pk_fma_f32 %0, %0, %1, %2" : "+v"(xb.b) : "v"(xa.b), "v"(xb.a));
-                    }
-#endif
+                    const c32x2 xa = st.pa[r], xb = st.pb[r];
                     if (k == 0) {                     // DC + Nyquist -> packed bin 0
                         z0[pa] = mk(xa.a.x + xb.a.x, xa.a.x - xb.a.x);
                         z1[pa] = mk(xa.b.x + xb.b.x, xa.b.x - xb.b.x);
@@ -459,7 +447,7 @@ FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int
         // C1: issue the next tile's gather (lands after C4), then merge the half spectrum of
         // this tile into the packed complex sequence, in place (table driven)
         if constexpr (PLAND) ctx.phase_nosync([&](int t, State& st) {
-            if (next < n_total) issue_gather(t, st, next, IC<(PLAND && FC_COLS_SPLIT_GATHER) ? 1 : 0>{}, nxt_lo, nxt_hi);
+            if (next < n_total) issue_gather(t, st, next, IC<1>{}, nxt_lo, nxt_hi);
         });
         else ctx.phase([&](int t, State& st) {
             if (next < n_total) issue_gather(t, st, next, IC<0>{}, nxt_lo, nxt_hi);
@@ -519,14 +507,15 @@ FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int
         });
 
         FC_COLS_STAMP(2);
-        if constexpr (PLAND && FC_COLS_SPLIT_GATHER) ctx.phase_nosync([&](int t, State& st) {
+        // second third of the next tile's gather
+        if constexpr (PLAND) ctx.phase_nosync([&](int t, State& st) {
             if (next < n_total) issue_gather(t, st, next, IC<2>{}, nxt_lo, nxt_hi);
         });
         // C3: inverse stage 2 (radix R2, sub-length R3)
         ctx.template phase_dbg<(FC_COLS_DBG & 2) != 0>([&](int t, [[maybe_unused]] State& st) {
             static_for<0, C::RND2>([&](auto r_) {
                 constexpr int r = decltype(r_)::value;
-                if constexpr (PLAND && FC_COLS_SPLIT_GATHER == 2 && r == C::RND2 - 1) {   // last third of the gather: ahead of the last round
+                if constexpr (PLAND && r == C::RND2 - 1) {   // last third of the gather: ahead of the last round
                     if (next < n_total) issue_gather(t, st, next, IC<3>{}, nxt_lo, nxt_hi);
                 }
                 const int idx = t + NT * r;
@@ -557,11 +546,9 @@ FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int
         const int pair_lo = g.h_lo >> 1;                                 // complex pairs [pair_lo, pair_lo + nout) of a column are stored
         const unsigned nout = (unsigned)((g.fft_h - g.h_lo) >> 1);
         ctx.phase([&](int t, [[maybe_unused]] State& st) {
-#if !FC_COLS_NO_PREWAIT
             // the next tile's gather (issued in C1) has had two stages to arrive: take it off the
             // memory counter now, so that landing it does not wait for the stores below
             FC_WAIT_VMEM();
-#endif
             FC_COLS_STAMP(4);
             if constexpr (dyn) {
                 if (next < n_total && t == 0) {   // the tile after next: the ticket requested in C1, or another XCD's

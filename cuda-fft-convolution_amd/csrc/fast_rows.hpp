@@ -37,8 +37,8 @@ struct RowCfg {
     // consecutive cells) and then jump to the next block: with S1 = m1 that jump is a multiple of all 32 banks for most lengths
     // (528 cells at 4224 = 1056 dwords) and the lanes on both sides of it collide -- a quarter of the kernel's LDS cycles were
     // bank-conflict cycles (SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE, profiles/r05s_*).  S1 = R3 (mod 16) continues the bank
-    // sequence across the jump.  FC_ROWS_NO_BLOCK_PAD = 1 (diagnostic builds) restores S1 = m1.
-    static constexpr int PAD1 = FC_ROWS_NO_BLOCK_PAD ? 0 : ((R3 - m1 % 16) % 16 + 16) % 16;
+    // sequence across the jump.
+    static constexpr int PAD1 = ((R3 - m1 % 16) % 16 + 16) % 16;
     static constexpr int S1 = m1 + PAD1;     // LDS distance of two stage-1 blocks
     static constexpr int LR = R1 * S1;       // LDS cells of one row
     static constexpr int NB1 = m1;           // butterflies per stage and row

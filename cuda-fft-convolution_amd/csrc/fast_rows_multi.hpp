@@ -50,7 +50,6 @@ FC_HD void fast_rows_multi_body(Ctx& ctx, c32* lds, const FastRowsArgs& g, int g
     const int kw = g.kw;
     const int row0 = group * RPW;
     const bool tiled = g.y_row_of != nullptr;
-    constexpr bool FOLD = !(FC_ROWS_NO_FOLD);
 
     auto load_x = [&](int t, State& st, int kernel, int f) {
         const c32* abase = g.A + (size_t)kernel * g.a_kernel_stride + (MULTIF ? (size_t)f * g.a_feat_stride : 0);
@@ -62,6 +61,21 @@ FC_HD void fast_rows_multi_body(Ctx& ctx, c32* lds, const FastRowsArgs& g, int g
             const int row = row0 + rr;
             st.x[r] = (rr < RPW && row < rows && j < kw) ? abase[(size_t)row * g.a_pitch + j] : mk(0.f, 0.f);
         });
+    };
+    // MULTIF, P3: register pairs [H0, H1) of feature f's image-spectrum row for stage-3 butterfly q of row rr (zeros past the last row)
+    auto load_s = [&](State& st, int f, int rr, int q, auto h0_, auto h1_) {
+        constexpr int H0 = decltype(h0_)::value, H1 = decltype(h1_)::value;
+        if (row0 + rr < rows) {
+            const c32* srow = g.S + (size_t)f * g.s_feat_stride + (size_t)(row0 + rr) * g.s_pitch;
+            static_for<H0, H1>([&](auto h_) {
+                constexpr int h = decltype(h_)::value;
+                c32x2 w = *reinterpret_cast<const c32x2*>(srow + (size_t)(h * C::NB3 + q) * 2);
+                st.s[2 * h] = w.a;
+                st.s[2 * h + 1] = w.b;
+            });
+        } else {
+            static_for<2 * H0, 2 * H1>([&](auto a_) { st.s[decltype(a_)::value] = mk(0.f, 0.f); });
+        }
     };
 
     // once per workgroup: stage-2 twiddles into LDS, first kernel row, image-spectrum row
@@ -100,13 +114,13 @@ FC_HD void fast_rows_multi_body(Ctx& ctx, c32* lds, const FastRowsArgs& g, int g
         FC_ROWS_STAMP(0);
 
         // P1: forward stage 1, pruned (one non-zero input per butterfly) -- as a phase of its own
-        // only for the first map of the walk; for the others it is folded into the previous map's P5
-        // (FOLD): the thread that has just read the R1 LDS cells of butterfly j for the inverse
+        // only for the first map of the walk; for the others it is folded into the previous map's P5:
+        // the thread that has just read the R1 LDS cells of butterfly j for the inverse
         // stage 1 is the only one that ever touches them, so it writes the next map's stage-1
         // outputs into them right away, with the twiddle chain it has at hand -- one phase and one
         // barrier fewer per map
         for (int f = 0; f < nF; f++) {
-        if (!FOLD || m == 0 || f > 0) ctx.phase([&](int t, State& st) {
+        if (m == 0 || f > 0) ctx.phase([&](int t, State& st) {
             static_for<0, C::RND1>([&](auto r_) {
                 constexpr int r = decltype(r_)::value;
                 int u = t + NT * r;
@@ -164,29 +178,18 @@ FC_HD void fast_rows_multi_body(Ctx& ctx, c32* lds, const FastRowsArgs& g, int g
             if constexpr (MULTIF) FC_OPAQUE(t);
             const int rr = t / C::NB3, q = t - rr * C::NB3;
             if (rr < RPW) {
-                // MULTIF: this feature's image-spectrum row.  Only its first FC_MULTIF_S_EARLY register pairs are requested
+                // MULTIF: this feature's image-spectrum row.  Only its first S_EARLY register pairs are requested
                 // ahead of the forward butterfly, the rest right after it: with the whole row in flight beside the
                 // radix-22 butterfly (its in-register composite form needs ~70 registers of its own) and the feature
-                // sum, the kernel spilled 27-50 registers at L = 4224, differently in every translation unit, and a
-                // scratch reload shares the in-order memory counter with these very loads (59.7 -> 56.6 us per map at
-                // F = 4 with none early and no spills, profiles/r03i_f4_image_row_load_placement.txt)
-                // (configurations with several rows per workgroup or a stage 3 above radix 22 keep more per-thread state:
-                //  nothing early there)
-                constexpr int S_EARLY_CFG = (RPW > 1 || R3 > 22) ? 0 : FC_MULTIF_S_EARLY;
-                constexpr int S_EARLY = (S_EARLY_CFG < R3 / 2) ? S_EARLY_CFG : R3 / 2;
-                if constexpr (MULTIF && (0) < (S_EARLY)) {
-                    if (row0 + rr < rows) {
-                        const c32* srow = g.S + (size_t)f * g.s_feat_stride + (size_t)(row0 + rr) * g.s_pitch;
-                        static_for<(0), (S_EARLY)>([&](auto h_) {
-                            constexpr int h = decltype(h_)::value;
-                            c32x2 w = *reinterpret_cast<const c32x2*>(srow + (size_t)(h * C::NB3 + q) * 2);
-                            st.s[2 * h] = w.a;
-                            st.s[2 * h + 1] = w.b;
-                        });
-                    } else {
-                        static_for<2 * (0), 2 * (S_EARLY)>([&](auto a_) { st.s[decltype(a_)::value] = mk(0.f, 0.f); });
-                    }
-                }
+                // sum, the kernel spilled 27-50 registers at L = 4224 (all 11 pairs early, rounds 1-2), differently in
+                // every translation unit, and a scratch reload shares the in-order memory counter with these very loads
+                // (59.7 -> 56.6 us per map at F = 4 with none early and no spills).  0 / 4 / 8 pairs early: no spills, and
+                // 56.7 / 53.2 / 54.6 us per map at F = 4 on one box (profiles/r03i_f4_image_row_load_placement.txt).
+                // Configurations with several rows per workgroup or a stage 3 above radix 22 keep more per-thread state:
+                // nothing early there.
+                constexpr int S_EARLY_PAIRS = 4;
+                constexpr int S_EARLY = (RPW > 1 || R3 > 22) ? 0 : (S_EARLY_PAIRS < R3 / 2 ? S_EARLY_PAIRS : R3 / 2);
+                if constexpr (MULTIF && 0 < S_EARLY) load_s(st, f, rr, q, IC<0>{}, IC<S_EARLY>{});
                 c32* p = lds + rr * LR + (q / R2) * S1 + (q % R2) * R3;     // run c of stage-1 block c1: q = c1 * R2 + c
                 c32 v[R3];
                 static_for<0, R3 / 2>([&](auto h_) {
@@ -212,19 +215,7 @@ FC_HD void fast_rows_multi_body(Ctx& ctx, c32* lds, const FastRowsArgs& g, int g
                     FC_SCHED_FENCE();
                 }
                 Dft<R3, -1>::run(v);
-                if constexpr (MULTIF && (S_EARLY) < (R3 / 2)) {
-                    if (row0 + rr < rows) {
-                        const c32* srow = g.S + (size_t)f * g.s_feat_stride + (size_t)(row0 + rr) * g.s_pitch;
-                        static_for<(S_EARLY), (R3 / 2)>([&](auto h_) {
-                            constexpr int h = decltype(h_)::value;
-                            c32x2 w = *reinterpret_cast<const c32x2*>(srow + (size_t)(h * C::NB3 + q) * 2);
-                            st.s[2 * h] = w.a;
-                            st.s[2 * h + 1] = w.b;
-                        });
-                    } else {
-                        static_for<2 * (S_EARLY), 2 * (R3 / 2)>([&](auto a_) { st.s[decltype(a_)::value] = mk(0.f, 0.f); });
-                    }
-                }
+                if constexpr (MULTIF && S_EARLY < R3 / 2) load_s(st, f, rr, q, IC<S_EARLY>{}, IC<R3 / 2>{});
                 if constexpr (!MULTIF) {
                     static_for<0, R3>([&](auto a_) {
                         constexpr int a = decltype(a_)::value;
@@ -318,7 +309,7 @@ FC_HD void fast_rows_multi_body(Ctx& ctx, c32* lds, const FastRowsArgs& g, int g
                         c32 v[R1];
                         if constexpr (FC_ROWSM_DBG & 1) {
                             static_for<0, R1>([&](auto c_) { v[decltype(c_)::value] = st.s[decltype(c_)::value]; });
-                            if (FOLD && m + 1 < nk && j < kw) power_chain<R1>(st.w1[r], p);
+                            if (m + 1 < nk && j < kw) power_chain<R1>(st.w1[r], p);
                         } else {
                         power_chain<R1>(st.w1[r], p);
                         v[0] = buf[j];
@@ -349,7 +340,7 @@ FC_HD void fast_rows_multi_body(Ctx& ctx, c32* lds, const FastRowsArgs& g, int g
                                 if (j + a * m1 < g.wout) FC_ROWSM_STORE(reinterpret_cast<c32*>(yb + (size_t)(base + (unsigned)(a / SA) * stride_b)), v[a]);
                             });
                         }
-                        if (FOLD && m + 1 < nk && j < kw) {   // forward stage 1 of the next map into the cells just read
+                        if (m + 1 < nk && j < kw) {   // forward stage 1 of the next map into the cells just read
                             c32* wbuf = lds + rr * LR;
                             wbuf[j] = st.x[r];
                             static_for<1, R1>([&](auto c_) {
@@ -387,7 +378,7 @@ FC_HD void fast_rows_multi_body(Ctx& ctx, c32* lds, const FastRowsArgs& g, int g
                             else FC_ROWSM_STORE(&yrow[w], v[a]);
                         }
                     });
-                    if (FOLD && m + 1 < nk && j < kw) {   // forward stage 1 of the next map into the cells just read
+                    if (m + 1 < nk && j < kw) {   // forward stage 1 of the next map into the cells just read
                         c32* wbuf = lds + rr * LR;
                         wbuf[j] = st.x[r];
                         static_for<1, R1>([&](auto c_) {

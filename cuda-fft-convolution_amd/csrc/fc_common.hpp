@@ -36,8 +36,8 @@
 #endif
 
 // Streaming store of one complex value: the intermediate and the maps are written once and not
-// re-read by this kernel (fc_instrument.hpp: FC_NT_STORES = 0 restores plain stores in diagnostic builds).
-#if defined(__HIP_DEVICE_COMPILE__) && FC_NT_STORES
+// re-read by this kernel.
+#if defined(__HIP_DEVICE_COMPILE__)
 #define FC_STREAM_STORE(ptr, val)                                                          \
     do {                                                                                   \
         const ::fc::c32 fc_v_ = (val);                                                     \
@@ -49,21 +49,12 @@
 #define FC_STREAM_STORE(ptr, val) (*(ptr) = (val))
 #endif
 
-// 16-byte load of data this kernel reads once.  FC_NT_LOADS=1 makes it a streaming (nontemporal)
-// load; plain loads are the default: the output kernel gathers 64-byte halves of 128-byte lines
-// whose other halves are gathered by a neighbouring CU of the same XCD, and a plain load keeps
-// the line in that XCD's L2 for it (27.4 vs 28.5 us per map, FETCH_SIZE back to the algorithmic
-// bytes once the gather is issued in two halves).
-#if defined(__HIP_DEVICE_COMPILE__) && FC_NT_LOADS
-#define FC_STREAM_LOAD16(dst, ptr)                                                         \
-    do {                                                                                   \
-        typedef float fc_f4_ __attribute__((ext_vector_type(4)));                          \
-        const fc_f4_ fc_t_ = __builtin_nontemporal_load(reinterpret_cast<const fc_f4_*>(ptr)); \
-        (dst).a.x = fc_t_.x; (dst).a.y = fc_t_.y; (dst).b.x = fc_t_.z; (dst).b.y = fc_t_.w;  \
-    } while (0)
-#else
+// 16-byte load of data this kernel reads once.  A plain load, not a streaming (nontemporal) one:
+// the output kernel gathers 64-byte halves of 128-byte lines whose other halves are gathered by a
+// neighbouring CU of the same XCD, and a plain load keeps the line in that XCD's L2 for it (27.4
+// vs 28.5 us per map with streaming loads, FETCH_SIZE back to the algorithmic bytes once the
+// gather is issued in two halves).
 #define FC_STREAM_LOAD16(dst, ptr) ((dst) = *reinterpret_cast<const ::fc::c32x2*>(ptr))
-#endif
 
 // Scheduling fence (device only): keeps the compiler from interleaving the unrolled rounds of a
 // phase, which multiplies their register footprint.
@@ -134,7 +125,8 @@ FC_HD c32 operator+(c32 a, c32 b) { return mk(a.x + b.x, a.y + b.y); }
 FC_HD c32 operator-(c32 a, c32 b) { return mk(a.x - b.x, a.y - b.y); }
 #endif
 
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(FC_NO_PACKED)
+// device code: packed FP32 complex arithmetic (below); the host side (tests/emu) takes the scalar forms
+#if defined(__HIP_DEVICE_COMPILE__)
 #define FC_PACKED 1
 #else
 #define FC_PACKED 0

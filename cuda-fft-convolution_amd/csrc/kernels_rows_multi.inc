@@ -11,26 +11,6 @@ __global__ void __launch_bounds__(Cfg::NT, 3) k_fast_rows_multi(FastRowsArgs a, 
     const int group = (int)blockIdx.x;
     const int kernel0 = (int)blockIdx.y * per_wg;
     const int nk = kernels - kernel0 < per_wg ? kernels - kernel0 : per_wg;
-#if FC_ROWS_STAGGER_TICKS
-    // experiment (fc_instrument.hpp): de-phase the workgroups that start together on a CU in the launch's first round
-    if (a.timeline && blockIdx.y == 0 && blockIdx.x < 1024) {
-        if (threadIdx.x == 0) {
-            int* ctr = reinterpret_cast<int*>(a.timeline) + 512;      // (the first 2 KB are the timeline's stamps)
-            const unsigned hw = __builtin_amdgcn_s_getreg((15 << 11) | 4);            // HW_ID[15:0]: wave, simd, pipe, cu (11:8), sh (12), se (15:13)
-            const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 7u;      // XCC_ID
-            const unsigned key = (xcc << 8) | ((hw >> 8) & 0xffu);
-            const int k = atomicAdd(ctr + key, 1) & 3;
-            ctr[2048 + 2 * blockIdx.x] = (int)key;
-            ctr[2048 + 2 * blockIdx.x + 1] = k;
-            // FC_ROWS_STAGGER_RAMP = 0: per CU, k x TICKS; 1: a ramp over the whole first round, TICKS from its first to its last workgroup
-            // (the chip-wide bursts of a round that starts together: every workgroup stores its row of map m at the same time)
-            const unsigned long long wait = FC_ROWS_STAGGER_RAMP ? (unsigned long long)blockIdx.x * FC_ROWS_STAGGER_TICKS / 1024 : (unsigned long long)k * FC_ROWS_STAGGER_TICKS;
-            const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-            while (__builtin_amdgcn_s_memrealtime() - t0 < wait) __builtin_amdgcn_s_sleep(8);
-        }
-        __syncthreads();
-    }
-#endif
     DevPhaseCtx<RowMultiState<Cfg>> ctx;
     fast_rows_multi_body<Cfg, NZ2, LINEAR>(ctx, reinterpret_cast<c32*>(fc_smem), a, group, kernel0, nk, rows);
 }

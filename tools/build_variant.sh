@@ -8,13 +8,18 @@ SRC=$ROOT/cuda-fft-convolution_amd/csrc
 OBJ=/tmp/fc_variant_$NAME
 mkdir -p $OBJ $ROOT/cuda-fft-convolution_amd/ab
 FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -fno-slp-vectorize -Wno-unused-function -DFC_INSTRUMENT $*"
+JOBS=${MAX_JOBS:-16}
 pids=""
+compile() {      # one hipcc in the background, at most $JOBS at a time (their exit statuses are collected below)
+  while [ "$(jobs -rp | wc -l)" -ge "$JOBS" ]; do wait -n || true; done
+  /opt/rocm/bin/hipcc $FLAGS "$@" & pids="$pids $!"
+}
 for src in $SRC/kernels*.hip; do      # kernels.hip + one translation unit per kernel family and configuration group
   f=$(basename $src .hip)
-  /opt/rocm/bin/hipcc $FLAGS -I$SRC -c $src -o $OBJ/$f.o & pids="$pids $!"
+  compile -I$SRC -c $src -o $OBJ/$f.o
 done
 for f in fftconv_api plan_cache host_ring blockwise placement fftconv_multi; do      # the host units (csrc/Makefile: HOSTUNITS)
-  /opt/rocm/bin/hipcc $FLAGS -c $SRC/$f.cpp -o $OBJ/$f.o & pids="$pids $!"
+  compile -c $SRC/$f.cpp -o $OBJ/$f.o
 done
 for p in $pids; do wait $p; done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $ROOT/cuda-fft-convolution_amd/ab/$NAME.so $OBJ/*.o -ldl

@@ -4,7 +4,7 @@ per map of the walk: 0 start, 1 after P1, 2 after P2, 3 after P3, 4 after P4, 5 
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "tests")); sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
 import numpy as np, torch
-dbg = torch.zeros(4096, dtype=torch.int64, device="cuda")    # stamps [16][8]; behind them the counters of -DFC_ROWS_STAGGER_TICKS builds
+dbg = torch.zeros(4096, dtype=torch.int64, device="cuda")    # stamps [16][8]
 import util
 fc = util.load_package()
 H = W = 4096; kh = kw = 127; n = 64
