@@ -399,6 +399,33 @@ class Plan:
         _check(self._lib.fftconv_plan_convolve(self._h, n, kptr, kh, kw, HOST, optr, HOST))
         return outs
 
+    def convolve_to_device(self, kernelCell, out_ptrs, kernel_location=HOST):
+        """fftconv_plan_convolve with maps in device memory: asynchronous on the plan's stream.  kernelCell: host arrays
+        (kh x kw x F float32, consumed when the call returns) and / or (device pointer, kh, kw) triples of device-resident
+        kernels ([F][kw][kh] floats, i.e. the same MATLAB array); kernel_location HOST (arrays only), DEVICE (triples only) or
+        AUTO (any mix: the runtime tells them apart).  out_ptrs: one device pointer per kernel, out_h x out_w floats each."""
+        ks, ptrs, khs, kws = [], [], [], []
+        for k in kernelCell:
+            if isinstance(k, tuple):
+                if kernel_location == HOST:
+                    raise FFTConvError(-1, "a device-resident kernel needs kernel_location DEVICE or AUTO")
+                ptrs.append(int(k[0])), khs.append(int(k[1])), kws.append(int(k[2]))
+                continue
+            if kernel_location == DEVICE:
+                raise FFTConvError(-1, "a host kernel needs kernel_location HOST or AUTO")
+            a = _as_matlab_single(k, "kernel")
+            if a.shape[2] != self.info.feature_dim:  # src/cudaConvolutionFFT.cu:242
+                raise FFTConvError(-3, "Kernel and Data must have the same number of features and kernel "
+                                       "size should be smaller than data size")
+            ks.append(a)
+            ptrs.append(a.ctypes.data), khs.append(a.shape[0]), kws.append(a.shape[1])
+        n = len(ptrs)
+        if len(out_ptrs) != n:
+            raise FFTConvError(-1, "out_ptrs must hold one device pointer per kernel")
+        _check(self._lib.fftconv_plan_convolve(self._h, n, (ctypes.c_void_p * n)(*ptrs), (ctypes.c_int * n)(*khs),
+                                               (ctypes.c_int * n)(*kws), int(kernel_location),
+                                               (ctypes.c_void_p * n)(*[int(o) for o in out_ptrs]), DEVICE))
+
     def convolve_packed_device(self, n, kernels_ptr, kh, kw, out_ptr):
         """n equally sized kernels packed in device memory -> n maps packed in device memory;
         asynchronous on the plan's stream."""

@@ -270,7 +270,13 @@ int fftconv_plan_import_spectrum(fftconv_plan *plan, const float *spectrum, int 
 
 /* Per-kernel loop of src/cudaConvolutionFFT.cu:204-291 for arbitrary (possibly different)
  * kernel sizes.  kernels[k]: kh[k] x kw[k] x F, host or device (gpuArray kernels: :224-238);
- * out[k]: FFT_H*FFT_W floats, host or device.  Synchronous for host output. */
+ * out[k]: FFT_H*FFT_W floats, host or device.  Synchronous for host output.
+ * Device output: the maps are queued on the plan's stream and the call may return before they are written.  HOST kernel
+ * arrays (FFTCONV_HOST, and the host members of an FFTCONV_AUTO cell) have been consumed when the call returns, whatever
+ * the output location: a group of at most 512 KiB is gathered by the CPU into the plan's pinned buffer and read from
+ * there (the first such call does not wait for the GPU at all; a later one waits until the work that still reads the
+ * buffer is over), a larger one goes through the runtime's copies from pageable memory, which have read the array when
+ * they return.  Device kernels must stay valid until the stream has passed the call. */
 int fftconv_plan_convolve(fftconv_plan *plan, int n_kernel,
                           const float *const *kernels, const int *kernel_h, const int *kernel_w,
                           int kernel_location,
@@ -300,7 +306,9 @@ int fftconv_plan_prepare_kernels_packed(fftconv_plan *plan, int n_kernel, const 
  * (which sizes the scratch buffers) fftconv_plan_set_image(DEVICE) and
  * fftconv_plan_convolve_packed allocate nothing and never synchronise, so they can be recorded
  * into a HIP graph: bind the plan to the capturing stream, capture, replay the graph
- * (bench.py --graph; the launch-bound small configurations gain most). */
+ * (bench.py --graph; the launch-bound small configurations gain most).  This holds for one-pass plans only: a
+ * block-wise plan (plan option "blockwise" > 0) synchronises its stream between chunks of kernels and cannot be
+ * captured.  fftconv_plan_prepare_kernels_packed may be part of the captured step, deferred or not. */
 int fftconv_plan_set_stream(fftconv_plan *plan, void *hip_stream);
 
 /* Block until everything queued on the plan's stream has finished. */

@@ -208,3 +208,62 @@ def spectrum_bin_error(got, want):
     want = np.asarray(want, dtype=np.complex128)
     e = np.asarray(got, dtype=np.complex128) - want
     return float(np.abs(e).max() / max(float(np.sqrt(np.mean(np.abs(want) ** 2))), 1e-300))
+
+
+# ---- a stream that is behind the host (tests/test_async_gpu.py, tests/test_graph_gpu.py)
+
+_LAG = {}
+
+
+def lag_calibrate(stream):
+    """how lag() spins on this device, measured once with an event pair: ("sleep", cycles of torch.cuda._sleep per millisecond)
+    or, where torch has no _sleep, ("matmul", 2048 x 2048 fp32 products per millisecond)"""
+    import torch
+    if "unit" in _LAG:
+        return _LAG["kind"], _LAG["unit"]
+
+    def timed(work):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        with torch.cuda.stream(stream):
+            e0.record(stream)
+            work()
+            e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    if hasattr(torch.cuda, "_sleep"):
+        n, ms = 250000, 0.0
+        for _ in range(12):                 # grows until one spin takes 5 ms: at most ~40 ms a try, whatever a cycle is
+            ms = timed(lambda: torch.cuda._sleep(n))
+            if ms >= 5.0:
+                break
+            n *= 8
+        ms = min(ms, timed(lambda: torch.cuda._sleep(n)))      # (clocks settled)
+        _LAG["kind"], _LAG["unit"] = "sleep", n / max(ms, 1e-3)
+    else:
+        with torch.cuda.stream(stream):
+            a = torch.ones((2048, 2048), dtype=torch.float32, device=stream.device)
+            _LAG["a"] = a
+            torch.mm(a, a)
+        reps = 64
+        ms = timed(lambda: [torch.mm(a, a) for _ in range(reps)])
+        _LAG["kind"], _LAG["unit"] = "matmul", reps / max(ms, 1e-3)
+    return _LAG["kind"], _LAG["unit"]
+
+
+def lag(stream, ms=50.0):
+    """queues a bounded busy-wait of about `ms` milliseconds on `stream` (a finite spin on the device, never a wait for
+    something the host does later) and returns a torch.cuda.Event recorded right behind it: while ev.query() is False the
+    stream is behind the host, and whatever was queued after lag() has not started"""
+    import torch
+    kind, unit = lag_calibrate(stream)
+    with torch.cuda.stream(stream):
+        if kind == "sleep":
+            torch.cuda._sleep(int(ms * unit))
+        else:
+            a = _LAG["a"]
+            for _ in range(max(1, int(ms * unit))):
+                torch.mm(a, a)
+    ev = torch.cuda.Event()
+    ev.record(stream)
+    return ev
