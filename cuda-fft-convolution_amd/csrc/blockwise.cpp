@@ -83,9 +83,8 @@ bool blocks_preferred(const Geometry& g, const fftconv_plan_options* options) {
     const bool fast = g.fast_rows.ok && g.fast_cols.ok && g.y_tiled();
     if (fast && g.Lh < 5120 && g.Lw < 7040) return false;
     if (!fast && g.Lh <= 8448 && g.Lw <= 8448) return false;      // small or oddly sized: not what blocks are for
-    int limit = 4608;
-    if (options && options->struct_size >= kOptionsMinSize && options->max_transform > 0) limit = std::min(limit, options->max_transform);
-    const SaveTiling t = choose_save_tiling(g.fft_h, g.fft_w, g.max_kh, g.max_kw, limit);
+    const int max_transform = tuning_from(options).max_transform;
+    const SaveTiling t = choose_save_tiling(g.fft_h, g.fft_w, g.max_kh, g.max_kw, max_transform > 0 ? std::min(4608, max_transform) : 4608);
     if (!t.ok || t.h.n * t.w.n < 2) return false;
     DimChoice h1, w1;
     h1.L = g.Lh; h1.n = 1; w1.L = g.Lw; w1.n = 1;
@@ -95,9 +94,8 @@ bool blocks_preferred(const Geometry& g, const fftconv_plan_options* options) {
 
 // creates the block plan of a tiled plan; FFTCONV_ERR_UNSUPPORTED_SIZE if no block shape works
 int tiled_create(fftconv_plan* p, int H, int W, int F, int mkh, int mkw, void* hip_stream, const fftconv_plan_options* options) {
-    int limit = 4224;
-    const bool limited = options && options->struct_size >= kOptionsMinSize && options->max_transform > 0;
-    if (limited) limit = std::min(limit, options->max_transform);
+    const int max_transform = tuning_from(options).max_transform;      // (0: none given)
+    const int limit = max_transform > 0 ? std::min(4224, max_transform) : 4224;
     TiledState* ts = new (std::nothrow) TiledState();
     if (!ts) return api_fail(FFTCONV_ERR_ALLOC, "out of host memory");
     fftconv_plan_options sub_opts = {};
@@ -109,7 +107,7 @@ int tiled_create(fftconv_plan* p, int H, int W, int F, int mkh, int mkw, void* h
     int rc = FFTCONV_ERR_UNSUPPORTED_SIZE;
     // overlap-save first: needs the specialised kernels of the default path for the block transform
     if (tuning_from(options).path_mode == 2) {
-        const SaveTiling t = choose_save_tiling(ts->FH, ts->FW, mkh, mkw, limited ? limit : 4608);
+        const SaveTiling t = choose_save_tiling(ts->FH, ts->FW, mkh, mkw, max_transform > 0 ? limit : 4608);
         if (t.ok) {
             rc = plan_create_internal(&ts->sub, t.h.L, t.w.L, F, mkh, mkw, p->gpu_id, hip_stream, &sub_opts, true);
             if (rc && rc != FFTCONV_ERR_UNSUPPORTED_SIZE) { delete ts; return rc; }
@@ -156,53 +154,29 @@ int tiled_set_image(fftconv_plan* p, const float* data, int location) {
     FC_VERBOSE(p, "Data size: h=%d, w=%d, f=%d", H, W, F);
     FC_VERBOSE(p, "FFT size: h=%d, w=%d (block-wise, %s: %d x %d blocks of %d x %d samples, block transforms %d x %d)", ts->FH, ts->FW,
                ts->save ? "overlap-save" : "overlap-add", ts->nbh, ts->nbw, Bh, Bw, sub->g.Lh, sub->g.Lw);
-    if (ts->save) {
-        // block (by, bx) of the block plan's Lh x Lw samples: image rows [by * Bh - Sh, by * Bh + Bh) (zeros outside the image)
-        const int Lh = ts->Lh, Lw = ts->Lw;
-        if (location == FFTCONV_HOST) ts->hblk.resize((size_t)Lh * Lw * F);
-        else if (int rc = ts->blk.ensure((size_t)Lh * Lw * F)) return rc;
-        for (int b = 0; b < ts->nblk; b++) {
-            const int y0 = (b % ts->nbh) * Bh - ts->Sh, x0 = (b / ts->nbh) * Bw - ts->Sw;       // image coordinates of the block's sample (0, 0)
-            const int ys = std::max(0, y0), ye = std::min(H, y0 + Lh), xs = std::max(0, x0), xe = std::min(W, x0 + Lw);
-            const bool any = ye > ys && xe > xs;
-            if (int rc = fftconv_plan_use_spectrum_buffer(sub, ts->spec_base() + (size_t)b * ts->spec_elems, ts->spec_elems * sizeof(c32))) return rc;
-            if (location == FFTCONV_HOST) {
-                std::fill(ts->hblk.begin(), ts->hblk.end(), 0.f);
-                for (int f = 0; f < F && any; f++)
-                    for (int x = xs; x < xe; x++)
-                        memcpy(&ts->hblk[((size_t)f * Lw + (x - x0)) * Lh + (ys - y0)], &data[((size_t)f * W + x) * H + ys], (size_t)(ye - ys) * sizeof(float));
-                if (int rc = fftconv_plan_set_image(sub, ts->hblk.data(), FFTCONV_HOST)) return rc;   // (hblk is consumed on return: copied or staged)
-            } else {
-                HIP_TRY(hipMemsetAsync(ts->blk.p, 0, (size_t)Lh * Lw * F * sizeof(float), sub->stream));
-                for (int f = 0; f < F && any; f++)
-                    HIP_TRY(hipMemcpy2DAsync(ts->blk.p + ((size_t)f * Lw + (xs - x0)) * Lh + (ys - y0), (size_t)Lh * sizeof(float),
-                                             data + ((size_t)f * W + xs) * H + ys, (size_t)H * sizeof(float), (size_t)(ye - ys) * sizeof(float),
-                                             (size_t)(xe - xs), hipMemcpyDeviceToDevice, sub->stream));
-                if (int rc = fftconv_plan_set_image(sub, ts->blk.p, FFTCONV_DEVICE)) return rc;
-            }
-        }
-        ts->have_image = true;
-        return 0;
-    }
-    if (location == FFTCONV_HOST) ts->hblk.assign((size_t)Bh * Bw * F, 0.f);
-    else if (int rc = ts->blk.ensure((size_t)Bh * Bw * F)) return rc;
+    // Block (by, bx) is bh x bw samples of the image from (y0, x0) on, zeros outside the image.  Overlap-save: the block plan's
+    // Lh x Lw samples, the image rows [by * Bh - Sh, by * Bh + Bh); overlap-add: Bh x Bw samples, the blocks partition the image.
+    const int bh = ts->save ? ts->Lh : Bh, bw = ts->save ? ts->Lw : Bw;
+    if (location == FFTCONV_HOST) ts->hblk.resize((size_t)bh * bw * F);
+    else if (int rc = ts->blk.ensure((size_t)bh * bw * F)) return rc;
     for (int b = 0; b < ts->nblk; b++) {
-        const int y0 = (b % ts->nbh) * Bh, x0 = (b / ts->nbh) * Bw;
-        const int hv = std::min(Bh, H - y0), wv = std::min(Bw, W - x0);
+        const int y0 = (b % ts->nbh) * Bh - ts->Sh, x0 = (b / ts->nbh) * Bw - ts->Sw;       // image coordinates of the block's sample (0, 0)
+        const int ys = std::max(0, y0), ye = std::min(H, y0 + bh), xs = std::max(0, x0), xe = std::min(W, x0 + bw);
+        const bool any = ye > ys && xe > xs;
         if (int rc = fftconv_plan_use_spectrum_buffer(sub, ts->spec_base() + (size_t)b * ts->spec_elems, ts->spec_elems * sizeof(c32))) return rc;
         if (location == FFTCONV_HOST) {
             std::fill(ts->hblk.begin(), ts->hblk.end(), 0.f);
-            for (int f = 0; f < F; f++)
-                for (int x = 0; x < wv; x++)
-                    memcpy(&ts->hblk[((size_t)f * Bw + x) * Bh], &data[((size_t)f * W + (x0 + x)) * H + y0], (size_t)hv * sizeof(float));
+            for (int f = 0; f < F && any; f++)
+                for (int x = xs; x < xe; x++)
+                    memcpy(&ts->hblk[((size_t)f * bw + (x - x0)) * bh + (ys - y0)], &data[((size_t)f * W + x) * H + ys], (size_t)(ye - ys) * sizeof(float));
             if (int rc = fftconv_plan_set_image(sub, ts->hblk.data(), FFTCONV_HOST)) return rc;   // (hblk is consumed on return: copied or staged)
         } else {
             // the block, zero-padded, on the device: one strided copy per feature plane (h is contiguous)
-            if (hv < Bh || wv < Bw) HIP_TRY(hipMemsetAsync(ts->blk.p, 0, (size_t)Bh * Bw * F * sizeof(float), sub->stream));
-            for (int f = 0; f < F; f++)
-                HIP_TRY(hipMemcpy2DAsync(ts->blk.p + (size_t)f * Bw * Bh, (size_t)Bh * sizeof(float),
-                                         data + ((size_t)f * W + x0) * H + y0, (size_t)H * sizeof(float), (size_t)hv * sizeof(float), (size_t)wv,
-                                         hipMemcpyDeviceToDevice, sub->stream));
+            if (ts->save || ye - ys < bh || xe - xs < bw) HIP_TRY(hipMemsetAsync(ts->blk.p, 0, (size_t)bh * bw * F * sizeof(float), sub->stream));
+            for (int f = 0; f < F && any; f++)
+                HIP_TRY(hipMemcpy2DAsync(ts->blk.p + ((size_t)f * bw + (xs - x0)) * bh + (ys - y0), (size_t)bh * sizeof(float),
+                                         data + ((size_t)f * W + xs) * H + ys, (size_t)H * sizeof(float), (size_t)(ye - ys) * sizeof(float),
+                                         (size_t)(xe - xs), hipMemcpyDeviceToDevice, sub->stream));
             if (int rc = fftconv_plan_set_image(sub, ts->blk.p, FFTCONV_DEVICE)) return rc;
         }
     }
@@ -216,20 +190,18 @@ int tiled_set_image(fftconv_plan* p, const float* data, int location) {
 static int tiled_deliver(fftconv_plan* p, float* big, int nk, int k0, bool more, float* const* out, int out_location, float* out_packed) {
     TiledState* ts = p->tiled;
     fftconv_plan* sub = ts->sub;
-    const size_t big_map = ts->big_map(), oe = p->out_elems();
+    const size_t oe = p->out_elems();
     const float* src = big;
     if (p->opt_region != 0) {
         float* dst = out_packed ? out_packed + (size_t)k0 * oe : ts->crop.p;
-        if (p->opt_region == 4) HIP_TRY(launch_pad_maps(big, ts->FH, ts->FW, big_map, dst, p->out_h, p->out_w, oe, nk, sub->stream));
-        else HIP_TRY(launch_crop_maps(big, ts->FH, big_map, dst, p->out_h, p->out_w, oe, p->off_h, p->off_w, nk, sub->stream));
+        if (int rc = launch_region(p, big, dst, nk, sub->stream)) return rc;
         src = dst;
     } else if (out_packed) {
         return 0;
     }
     if (!out_packed)
         for (int j = 0; j < nk; j++)
-            HIP_TRY(hipMemcpyAsync(out[k0 + j], src + (size_t)j * oe, oe * sizeof(float),
-                                   out_location == FFTCONV_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, sub->stream));
+            HIP_TRY(hipMemcpyAsync(out[k0 + j], src + (size_t)j * oe, oe * sizeof(float), copy_kind(out_location, false), sub->stream));
     if ((!out_packed && out_location == FFTCONV_HOST) || more) HIP_TRY(hipStreamSynchronize(sub->stream));   // `big` (and the crop staging) are reused by the next chunk
     return 0;
 }
@@ -261,15 +233,13 @@ int tiled_convolve_save(fftconv_plan* p, int n, const float* const* kernels, con
         // groups of consecutive kernels of equal size, each packed on the device
         std::vector<Group> groups;
         size_t stage_total = 0;
-        for (int j = 0; j < nk;) {
-            int e = j + 1;
-            while (e < nk && kh[k0 + e] == kh[k0 + j] && kw[k0 + e] == kw[k0 + j]) e++;
+        for (int j = 0, e; j < nk; j = e) {
+            e = same_size_run_end(kh + k0, kw + k0, j, nk);
             const size_t per = (size_t)ts->F * kh[k0 + j] * kw[k0 + j];
             bool packed = kernel_location == FFTCONV_DEVICE;
             for (int i = j + 1; i < e && packed; i++) packed = kernels[k0 + i] == kernels[k0 + i - 1] + per;
             groups.push_back(Group{j, e - j, packed ? kernels[k0 + j] : nullptr});
             if (!packed) stage_total += per * (size_t)(e - j);
-            j = e;
         }
         if (stage_total) {
             if (int rc = ts->kstage.ensure(stage_total)) return rc;
@@ -279,9 +249,8 @@ int tiled_convolve_save(fftconv_plan* p, int n, const float* const* kernels, con
                 const size_t per = (size_t)ts->F * kh[k0 + gr.first] * kw[k0 + gr.first];
                 gr.dk = ts->kstage.p + off;
                 for (int i = 0; i < gr.count; i++, off += per)
-                    HIP_TRY(hipMemcpyAsync(ts->kstage.p + off, kernels[k0 + gr.first + i], per * sizeof(float),
-                                           kernel_location == FFTCONV_HOST ? hipMemcpyHostToDevice
-                                           : kernel_location == FFTCONV_AUTO ? hipMemcpyDefault : hipMemcpyDeviceToDevice, sub->stream));
+                    HIP_TRY(hipMemcpyAsync(ts->kstage.p + off, kernels[k0 + gr.first + i], per * sizeof(float), copy_kind(kernel_location, true),
+                                           sub->stream));
             }
         }
         for (int b = 0; b < ts->nblk; b++) {
@@ -292,22 +261,16 @@ int tiled_convolve_save(fftconv_plan* p, int n, const float* const* kernels, con
             win.map_stride = big_map; win.pitch = ts->FH;
             win.h_lo = ts->Sh; win.h_hi = ts->Sh + std::min(ts->Bh, ts->FH - y0);
             win.w_first = ts->Sw; win.ncols = std::min(ts->Bw, ts->FW - x0);
-            int rc = 0;
+            Sink sink;
+            sink.window = &win;
             for (const Group& gr : groups) {
                 // (row h of column w of the block's result belongs at row y0 + h - Sh of column x0 + w - Sw of the map)
                 win.base = big + (size_t)gr.first * big_map + ((ptrdiff_t)(x0 - ts->Sw) * ts->FH + (y0 - ts->Sh));
-                sub->win = &win;
-                Sink sink;
-                sink.packed = win.base;     // unused: the window decides where the maps go
                 // one group that fits one chunk of column spectra: block 0 left the kernels' column spectra in the block plan
                 // (every block runs the same transform), the other blocks reuse them
-                if (b > 0 && groups.size() == 1 && gr.count <= batch_sizes(sub, gr.count, kw[k0 + gr.first]).nbA && !sub->deferred.on) {
-                    sub->prepared.dk = gr.dk; sub->prepared.n = gr.count; sub->prepared.kh = kh[k0 + gr.first]; sub->prepared.kw = kw[k0 + gr.first];
-                    sub->prepared.stream = sub->stream;
-                }
-                rc = run_group(sub, gr.count, gr.dk, kh[k0 + gr.first], kw[k0 + gr.first], sink);
-                sub->win = nullptr;
-                if (rc) return rc;
+                if (b > 0 && groups.size() == 1 && gr.count <= batch_sizes(sub, gr.count, kw[k0 + gr.first]).nbA && !sub->deferred.on)
+                    sub->prepared = KernelSet{gr.dk, gr.count, kh[k0 + gr.first], kw[k0 + gr.first], sub->stream};
+                if (int rc = run_group(sub, gr.count, gr.dk, kh[k0 + gr.first], kw[k0 + gr.first], sink)) return rc;
             }
         }
         if (int rc = tiled_deliver(p, big, nk, k0, k0 + nc < n, out, out_location, out_packed)) return rc;
@@ -362,8 +325,7 @@ int tiled_convolve(fftconv_plan* p, int n, const float* const* kernels, const in
             size_t off = 0;
             for (int j = 0; j < nk; j++) {
                 const size_t per = (size_t)ts->F * kh[k0 + j] * kw[k0 + j];
-                HIP_TRY(hipMemcpyAsync(ts->kstage.p + off, kernels[k0 + j], per * sizeof(float),
-                                       kernel_location == FFTCONV_HOST ? hipMemcpyHostToDevice : hipMemcpyDefault, sub->stream));
+                HIP_TRY(hipMemcpyAsync(ts->kstage.p + off, kernels[k0 + j], per * sizeof(float), copy_kind(kernel_location, true), sub->stream));
                 staged[j] = ts->kstage.p + off;
                 off += per;
             }

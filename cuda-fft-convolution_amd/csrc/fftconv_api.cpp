@@ -1,6 +1,7 @@
 // fftconv_api.cpp -- host side of libfftconv.so: the C ABI of include/fftconv.h on top of the
 // HIP kernels.  C++ host code in the role of the reference's MEX gateways
 // (src/cudaConvolutionFFT.cu, src/cudaFFTData.cu, src/cudaConvFFTData.cu); no CPU compute path.
+#include <climits>
 #include <cstdarg>
 #include <cstdlib>
 #include <mutex>
@@ -133,182 +134,233 @@ int flush_pending_prepare(fftconv_plan* p) {
     p->stream = pd.stream;                      // where the caller ordered the kernels' readiness
     const int rc = launch_kernel_cols(p, pd.dk, 0, pd.na, pd.kh, pd.kw);
     p->stream = cur;
-    if (rc) return rc;
-    p->prepared.dk = pd.dk; p->prepared.n = pd.n; p->prepared.kh = pd.kh; p->prepared.kw = pd.kw; p->prepared.stream = pd.stream;
+    if (!rc) p->prepared = pd;
+    return rc;
+}
+
+// How the maps of a group leave the device: decided once per group (plan_delivery), read by every step of the loop.
+enum class Route {
+    Packed,   // the caller's packed device buffer: the output kernel (or the crop kernel) writes there
+    Window,   // block plan of an overlap-save plan: the output kernel stores its window of the full maps (OutWindow)
+    Copies,   // staged on the device, then one copy per map on the plan's stream (device pointers; host maps no other route takes)
+    Pinned,   // small host maps: staged, a launch's maps come back in ONE copy into the plan's pinned buffer (deliver_pinned)
+    Ring,     // host maps of at least host_min_kb: two staging buffers, the copy-out of batch b overlaps the compute of batch b + 1
+};
+struct Delivery {
+    Route route = Route::Packed;
+    // a region other than the whole window: the output kernel writes the window into O, a crop
+    // kernel compacts the region into the destination (the caller's packed buffer or the staging OC)
+    bool cropped = false;
+    DevBuf<float>* stage = nullptr;    // staged routes: where the maps wait for their copy (OC when cropped, else O)
+    size_t oe = 0;                     // floats per delivered map
+    bool staged() const { return route == Route::Copies || route == Route::Pinned || route == Route::Ring; }
+};
+
+int plan_delivery(fftconv_plan* p, const Sink& sink, int nbY, Delivery& d) {
+    const Geometry& g = p->g;
+    if (sink.window && !g.fast_cols.ok) return api_fail(FFTCONV_ERR_INVALID_ARG, "an output window needs the specialised output kernel");
+    d.cropped = p->opt_region != 0;
+    d.stage = d.cropped ? &p->OC : &p->O;
+    d.oe = p->out_elems();
+    const size_t map_bytes = d.oe * sizeof(float);
+    // host output: the ring for maps of at least host_min_kb (1 MiB).  Smaller ones leave by blocking copies on the plan's stream:
+    // the copy threads buy them nothing (a one-shot call would start and join them for a few hundred KB), and
+    // small destination buffers are heap neighbours that share pages, which the runtime pins in place from
+    // several threads at once.  A one-shot call on 92-KB maps died (SIGABRT / SIGSEGV, no message) about once
+    // in 50-100 runs of tests/test_gpu_parity.py::test_blockwise_one_shot_matches_oracle on some boxes of the
+    // pool and never on others; the cause was not isolated, these threads are what that call had to itself.
+    if (sink.window) d.route = Route::Window;
+    else if (sink.packed) d.route = Route::Packed;
+    else if (sink.location != FFTCONV_HOST) d.route = Route::Copies;
+    else if (p->opt_host_stream != 0 && map_bytes >= ((size_t)p->opt_host_min_kb << 10)) d.route = Route::Ring;
+    else if (p->opt_host_pinned && map_bytes <= FC_PIN_OUT_BYTES / 2) d.route = Route::Pinned;
+    else d.route = Route::Copies;
+    if (d.cropped)
+        if (int rc = p->O.ensure(g.map_elems() * nbY)) return rc;
+    if (d.staged())
+        if (int rc = d.stage->ensure(d.oe * nbY * (d.route == Route::Ring ? 2 : 1))) return rc;
+    if (d.route == Route::Ring) return ring_begin(p);
+    return 0;
+}
+
+// spectral rows of ny maps: the column spectra at `a` times the image spectrum, transformed along w into Y
+int launch_spectral_rows_batch(fftconv_plan* p, const c32* a, int kw, int ny) {
+    const Geometry& g = p->g;
+    if (int rc = p->prof_begin(PK_SPECTRAL, ny)) return rc;
+    if (g.fast_rows.ok) {   // (a walk of one map per workgroup where the multi-map walk is off: rows_group_for)
+        FastRowsArgs fa = fast_rows_args(g, p->d, a, kw, p->spec(), p->Y.p);
+        HIP_TRY(launch_fast_rows_multi(g.Lw, fast_rows_nz2(g, kw), fa, g.rows, ny, g.rows_group_for(ny, p->num_cus), p->stream));
+    } else {
+        SpectralRowsArgs sa = spectral_rows_args(g, p->t, p->d, a, kw, p->spec(), p->Y.p);
+        HIP_TRY(launch_spectral_rows(sa, g.rows, ny, rows_threads(g), p->rows_lds(), p->stream));
+    }
+    return p->prof_end();
+}
+
+// output columns of ny maps: Y transformed along h into the maps at obase (or into the window of an overlap-save block)
+int launch_output_cols(fftconv_plan* p, const OutWindow* win, float* obase, int ny) {
+    const Geometry& g = p->g;
+    if (int rc = p->prof_begin(PK_OUT_COLS, ny)) return rc;
+    if (g.fast_cols.ok) {
+        FastColsArgs fa = fast_cols_args(g, p->d, p->Y.p, obase, win ? win->map_stride : g.map_elems(), ny);
+        if (win) {
+            fa.h_lo = win->h_lo; fa.fft_h = win->h_hi; fa.w_first = win->w_first; fa.out_pitch = win->pitch;
+            fa.tiles_per_kernel = win->ncols / g.fast_cols.T; fa.ntiles = fa.tiles_per_kernel * ny;
+        }
+        HIP_TRY(launch_fast_cols(g.M, g.fast_cols.T, fa, p->num_cus, p->stream));
+    } else {
+        ColsC2RArgs ca = cols_c2r_args(g, p->t, p->d, p->Y.p, obase, g.map_elems());
+        HIP_TRY(launch_cols_c2r(ca, tiles_for(g.fft_w, g.T_cols), ny, cols_threads(g), p->cols_lds(), p->stream));
+    }
+    return p->prof_end();
+}
+
+// Route::Pinned -- small maps to host arrays: as many as fit the plan's pinned buffer come back in ONE copy and are handed
+// out by the CPU (a copy into pageable memory is a blocking runtime call per map)
+// (two halves: the copy of the next chunk runs while the CPU hands out the current one; a single map above
+//  FC_PIN_ONE_MAP_BYTES takes the plain copy of deliver_batch: the CPU's pass over it costs more than the runtime's pinning --
+//  one 324-KiB map: 77 against 60 us per convolve, four of them: 131 against 166, profiles/r04s_small_call_latency.txt)
+int deliver_pinned(fftconv_plan* p, const Delivery& d, float* const* out, int ny) {
+    const size_t mb = d.oe * sizeof(float);
+    const int per_copy = (int)std::min<size_t>((size_t)ny, (FC_PIN_OUT_BYTES / 2) / mb);
+    const int nchunks = (ny + per_copy - 1) / per_copy;
+    if (int rc = p->pin_out.ensure((size_t)per_copy * mb * (nchunks > 1 ? 2 : 1))) return rc;
+    for (int h = 0; h < 2; h++)
+        if (!p->pin_out_done[h]) HIP_TRY(hipEventCreateWithFlags(&p->pin_out_done[h], hipEventDisableTiming));
+    auto copy_chunk = [&](int c) -> hipError_t {
+        const int j0 = c * per_copy, nj = std::min(per_copy, ny - j0);
+        hipError_t e = hipMemcpyAsync(p->pin_out.p + (size_t)(c & 1) * per_copy * mb, d.stage->p + (size_t)j0 * d.oe, (size_t)nj * mb,
+                                      hipMemcpyDeviceToHost, p->stream);
+        if (e == hipSuccess) e = hipEventRecord(p->pin_out_done[c & 1], p->stream);
+        return e;
+    };
+    HIP_TRY(copy_chunk(0));
+    for (int c = 0; c < nchunks; c++) {
+        if (c + 1 < nchunks) HIP_TRY(copy_chunk(c + 1));
+        HIP_TRY(hipEventSynchronize(p->pin_out_done[c & 1]));
+        const int j0 = c * per_copy, nj = std::min(per_copy, ny - j0);
+        for (int j = 0; j < nj; j++)
+            memcpy(out[j0 + j], p->pin_out.p + ((size_t)(c & 1) * per_copy + j) * mb, mb);
+    }
+    return 0;   // (the staging buffer is free again: its last copy has been waited for)
+}
+
+// the maps [first, first + ny) are queued into `dest` (staging buffer buf of a streamed group): their way to the caller
+int deliver_batch(fftconv_plan* p, const Delivery& d, const Sink& sink, int first, int ny, int buf, const float* dest) {
+    if (d.route == Route::Ring) return ring_batch_launched(p, sink, first, ny, buf, dest);
+    if (d.route == Route::Pinned && (ny > 1 || d.oe * sizeof(float) <= FC_PIN_ONE_MAP_BYTES)) return deliver_pinned(p, d, sink.ptrs + first, ny);
+    if (!d.staged()) return 0;         // the kernels wrote where the caller reads
+    for (int j = 0; j < ny; j++)
+        HIP_TRY(hipMemcpyAsync(sink.ptrs[first + j], dest + (size_t)j * d.oe, d.oe * sizeof(float), copy_kind(sink.location, false), p->stream));
+    if (sink.location == FFTCONV_HOST) HIP_TRY(hipStreamSynchronize(p->stream));
     return 0;
 }
 
 // Core of the per-kernel loop (src/cudaConvolutionFFT.cu:204-291) for n kernels of one size,
-// packed on the device at dk ([n][F][kw][kh]).
+// packed on the device at dk ([n][F][kw][kh]).  Per batch of maps: kernel columns (once per chunk), spectral rows, the wait
+// for the staging buffer, output columns, crop or pad, then the batch's delivery.
 int run_group_impl(fftconv_plan* p, int n, const float* dk, int kh, int kw, const Sink& sink) {
     const Geometry& g = p->g;
     if (!p->have_image) return api_fail(FFTCONV_ERR_NO_IMAGE, "no image spectrum: call fftconv_plan_set_image first");
     if (int rc = check_kernel_size(p, kh, kw)) return rc;
     if (int rc = flush_pending_prepare(p)) return rc;
     const BatchSizes bs = batch_sizes(p, n, kw);
-    const size_t per_a = bs.per_a;
     const int nbY = bs.nbY, nbA = bs.nbA;
     FC_VERBOSE(p, "Kernel size: h=%d, w=%d", kh, kw);                 // src/cudaConvolutionFFT.cu:240
     FC_VERBOSE(p, "N Kernel: %d (maps per launch %d, kernels per column-spectrum chunk %d, %s)", n, nbY, nbA,
-               sink.packed ? "packed device output" : sink.location == FFTCONV_HOST ? "host output" : "device output");   // :68
-    if (int rc = p->A.ensure(per_a * nbA)) return rc;
+               (sink.packed || sink.window) ? "packed device output" : sink.location == FFTCONV_HOST ? "host output" : "device output");   // :68
+    if (int rc = p->A.ensure(bs.per_a * nbA)) return rc;
     if (int rc = p->Y.ensure(g.y_elems_per_kernel() * nbY)) return rc;
-    const OutWindow* win = p->win;
-    if (win && !g.fast_cols.ok) return api_fail(FFTCONV_ERR_INVALID_ARG, "an output window needs the specialised output kernel");
-    const bool staged = (sink.packed == nullptr) && !win;
-    // host output: two staging buffers, the copy-out of batch b overlaps the compute of batch b + 1
-    // ... for maps of at least host_min_kb (1 MiB).  Smaller ones leave by blocking copies on the plan's stream:
-    // the copy threads buy them nothing (a one-shot call would start and join them for a few hundred KB), and
-    // small destination buffers are heap neighbours that share pages, which the runtime pins in place from
-    // several threads at once.  A one-shot call on 92-KB maps died (SIGABRT / SIGSEGV, no message) about once
-    // in 50-100 runs of tests/test_gpu_parity.py::test_blockwise_one_shot_matches_oracle on some boxes of the
-    // pool and never on others; the cause was not isolated, these threads are what that call had to itself.
-    const bool streamed = staged && sink.location == FFTCONV_HOST && p->opt_host_stream != 0 &&
-                          p->out_elems() * sizeof(float) >= ((size_t)p->opt_host_min_kb << 10);
-    // a region other than the whole window: the output kernel writes the window into O, a crop
-    // kernel compacts the region into the destination (the caller's packed buffer or the staging OC)
-    const bool cropped = p->opt_region != 0;
-    const size_t oe = p->out_elems();
-    DevBuf<float>& stage = cropped ? p->OC : p->O;
-    if (cropped)
-        if (int rc = p->O.ensure(g.map_elems() * nbY)) return rc;
-    if (staged)
-        if (int rc = stage.ensure(oe * nbY * (streamed ? 2 : 1))) return rc;
-    if (streamed)
-        if (int rc = ring_ensure(p)) return rc;
-    if (p->Y.fresh) {   // before anything is written into it: the tuner may keep another allocation
-        int tune_k = (int)p->opt_tune_placement;
-        if (tune_k < 0) tune_k = win ? 0 : placement_auto_candidates(p, (size_t)std::min(nbY, n) * g.map_elems() * sizeof(float));
-        if (tune_k > 1 && !win) {
-            const bool direct = !cropped && !staged;   // the output kernel writes straight into the caller's packed buffer
-            float* first_obase = cropped ? p->O.p : (staged ? stage.p : sink.packed);
-            if (int rc = tune_intermediate_placement(p, tune_k, direct ? n : std::min(nbY, n), nbY, first_obase, direct ? oe : 0)) return rc;
-        }
-        p->Y.fresh = false;
-    }
-    int batch = 0;
-    struct { bool valid = false; int first = 0, count = 0, buf = 0; } prev;
-
-    const int T = g.T_cols;
-    const int cthreads = cols_threads(g), rthreads = rows_threads(g);
+    Delivery d;
+    if (int rc = plan_delivery(p, sink, nbY, d)) return rc;
+    if (p->Y.fresh)     // before anything is written into it: the tuner may keep another allocation
+        if (int rc = tune_intermediate_placement(p, sink, n, nbY, d.cropped ? p->O.p : d.staged() ? d.stage->p : sink.packed, !d.cropped && !d.staged()))
+            return rc;
     for (int a0 = 0; a0 < n; a0 += nbA) {
         const int na = std::min(nbA, n - a0);
-        const bool have_cols = (a0 == 0 && p->prepared.dk == dk && p->prepared.n == n && p->prepared.kh == kh && p->prepared.kw == kw &&
-                                p->prepared.stream == p->stream);
+        const bool have_cols = a0 == 0 && p->prepared == KernelSet{dk, n, kh, kw, p->stream};
         p->prepared.dk = nullptr;   // A is about to be consumed / overwritten
         if (!have_cols)
             if (int rc = launch_kernel_cols(p, dk, a0, na, kh, kw)) return rc;
         for (int y0 = 0; y0 < na; y0 += nbY) {
-            const int ny = std::min(nbY, na - y0);
+            const int ny = std::min(nbY, na - y0), first = a0 + y0;
             FC_VERBOSE(p, "maps %d..%d: spectral rows (%s, %d rows x %d points, %d maps per workgroup), output columns (%s, %d-point, %d columns per tile)",
-                       a0 + y0, a0 + y0 + ny - 1, g.fast_rows.ok ? "specialised" : "generic", g.rows, g.Lw, g.rows_group_for(ny, p->num_cus),
+                       first, first + ny - 1, g.fast_rows.ok ? "specialised" : "generic", g.rows, g.Lw, g.rows_group_for(ny, p->num_cus),
                        g.fast_cols.ok ? "specialised" : "generic", g.M, g.fast_cols.ok ? g.fast_cols.T : g.T_cols);
-            if (int rc = p->prof_begin(PK_SPECTRAL, ny)) return rc;
-            if (g.rows_group_for(ny, p->num_cus) > 1) {
-                FastRowsArgs fa = fast_rows_args(g, p->d, p->A.p + (size_t)y0 * per_a, kw, p->spec(), p->Y.p);
-                HIP_TRY(launch_fast_rows_multi(g.Lw, fast_rows_nz2(g, kw), fa, g.rows, ny, g.rows_group_for(ny, p->num_cus), p->stream));
-            } else if (g.fast_rows.ok) {
-                FastRowsArgs fa = fast_rows_args(g, p->d, p->A.p + (size_t)y0 * per_a, kw, p->spec(), p->Y.p);
-                HIP_TRY(launch_fast_rows(g.Lw, fast_rows_nz2(g, kw), fa, g.rows, ny, p->stream));
-            } else {
-                SpectralRowsArgs sa = spectral_rows_args(g, p->t, p->d, p->A.p + (size_t)y0 * per_a, kw, p->spec(), p->Y.p);
-                HIP_TRY(launch_spectral_rows(sa, g.rows, ny, rthreads, p->rows_lds(), p->stream));
-            }
-            if (int rc = p->prof_end()) return rc;
-            const int buf = streamed ? (batch & 1) : 0;
-            float* dest = win ? win->base + (size_t)(a0 + y0) * win->map_stride                               // where the maps of this batch go
-                          : staged ? stage.p + (size_t)buf * nbY * oe : sink.packed + (size_t)(a0 + y0) * oe;
-            float* obase = cropped ? p->O.p : dest;                                                            // where the output kernel writes
-            if (streamed && batch >= 2) {   // staging buffer `buf` still holds batch - 2 until its copy-out is over
-                if (p->ring->nslots == 0) p->ring->wait_staging_free(buf);
-                else HIP_TRY(hipStreamWaitEvent(p->stream, p->ring->copy_done[buf], 0));
-            }
-            if (int rc = p->prof_begin(PK_OUT_COLS, ny)) return rc;
-            if (g.fast_cols.ok) {
-                FastColsArgs fa = fast_cols_args(g, p->d, p->Y.p, obase, win ? win->map_stride : g.map_elems(), ny);
-                if (win) {
-                    fa.h_lo = win->h_lo; fa.fft_h = win->h_hi; fa.w_first = win->w_first; fa.out_pitch = win->pitch;
-                    fa.tiles_per_kernel = win->ncols / g.fast_cols.T; fa.ntiles = fa.tiles_per_kernel * ny;
-                }
-                HIP_TRY(launch_fast_cols(g.M, g.fast_cols.T, fa, p->num_cus, p->stream));
-            } else {
-                ColsC2RArgs ca = cols_c2r_args(g, p->t, p->d, p->Y.p, obase, g.map_elems());
-                HIP_TRY(launch_cols_c2r(ca, tiles_for(g.fft_w, T), ny, cthreads, p->cols_lds(), p->stream));
-            }
-            if (int rc = p->prof_end()) return rc;
-            if (cropped && p->opt_region == 4)
-                HIP_TRY(launch_pad_maps(p->O.p, g.fft_h, g.fft_w, g.map_elems(), dest, p->out_h, p->out_w, oe, ny, p->stream));
-            else if (cropped)
-                HIP_TRY(launch_crop_maps(p->O.p, g.fft_h, g.map_elems(), dest, p->out_h, p->out_w, oe, p->off_h, p->off_w, ny, p->stream));
-            if (streamed) {
-                HIP_TRY(hipEventRecord(p->ring->compute_done[buf], p->stream));
-                if (prev.valid)
-                    if (int rc = ring_drain(p, sink, prev.first, prev.count, prev.buf, stage.p + (size_t)prev.buf * nbY * oe)) return rc;
-                prev.valid = true; prev.first = a0 + y0; prev.count = ny; prev.buf = buf;
-                batch++;
-            } else if (staged && sink.location == FFTCONV_HOST && p->opt_host_pinned && oe * sizeof(float) <= FC_PIN_OUT_BYTES / 2 &&
-                       (ny > 1 || oe * sizeof(float) <= FC_PIN_ONE_MAP_BYTES)) {
-                // small maps to host arrays: as many as fit the plan's pinned buffer come back in ONE copy and are handed
-                // out by the CPU (a copy into pageable memory is a blocking runtime call per map)
-                // (two halves: the copy of the next chunk runs while the CPU hands out the current one; a single map above
-                //  FC_PIN_ONE_MAP_BYTES takes the plain copy below: the CPU's pass over it costs more than the runtime's pinning --
-                //  one 324-KiB map: 77 against 60 us per convolve, four of them: 131 against 166, profiles/r04s_small_call_latency.txt)
-                const size_t mb = oe * sizeof(float);
-                const int per_copy = (int)std::min<size_t>((size_t)ny, (FC_PIN_OUT_BYTES / 2) / mb);
-                const int nchunks = (ny + per_copy - 1) / per_copy;
-                if (int rc = p->pin_out.ensure((size_t)per_copy * mb * (nchunks > 1 ? 2 : 1))) return rc;
-                for (int h = 0; h < 2; h++)
-                    if (!p->pin_out_done[h]) HIP_TRY(hipEventCreateWithFlags(&p->pin_out_done[h], hipEventDisableTiming));
-                auto copy_chunk = [&](int c) -> hipError_t {
-                    const int j0 = c * per_copy, nj = std::min(per_copy, ny - j0);
-                    hipError_t e = hipMemcpyAsync(p->pin_out.p + (size_t)(c & 1) * per_copy * mb, stage.p + (size_t)j0 * oe, (size_t)nj * mb,
-                                                  hipMemcpyDeviceToHost, p->stream);
-                    if (e == hipSuccess) e = hipEventRecord(p->pin_out_done[c & 1], p->stream);
-                    return e;
-                };
-                HIP_TRY(copy_chunk(0));
-                for (int c = 0; c < nchunks; c++) {
-                    if (c + 1 < nchunks) HIP_TRY(copy_chunk(c + 1));
-                    HIP_TRY(hipEventSynchronize(p->pin_out_done[c & 1]));
-                    const int j0 = c * per_copy, nj = std::min(per_copy, ny - j0);
-                    for (int j = 0; j < nj; j++)
-                        memcpy(sink.ptrs[a0 + y0 + j0 + j], p->pin_out.p + ((size_t)(c & 1) * per_copy + j) * mb, mb);
-                }
-                // (the staging buffer is free again: its last copy has been waited for)
-            } else if (staged) {
-                for (int j = 0; j < ny; j++) {
-                    float* dst = sink.ptrs[a0 + y0 + j];
-                    HIP_TRY(hipMemcpyAsync(dst, stage.p + (size_t)j * oe, oe * sizeof(float),
-                                           sink.location == FFTCONV_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
-                                           p->stream));
-                }
-                if (sink.location == FFTCONV_HOST) HIP_TRY(hipStreamSynchronize(p->stream));
-            }
+            if (int rc = launch_spectral_rows_batch(p, p->A.p + (size_t)y0 * bs.per_a, kw, ny)) return rc;
+            int buf = 0;
+            if (d.route == Route::Ring)
+                if (int rc = ring_claim_staging(p, &buf)) return rc;
+            float* dest = sink.window ? sink.window->base + (size_t)first * sink.window->map_stride            // where the maps of this batch go
+                          : d.staged() ? d.stage->p + (size_t)buf * nbY * d.oe : sink.packed + (size_t)first * d.oe;
+            if (int rc = launch_output_cols(p, sink.window, d.cropped ? p->O.p : dest, ny)) return rc;
+            if (d.cropped)
+                if (int rc = launch_region(p, p->O.p, dest, ny, p->stream)) return rc;
+            if (int rc = deliver_batch(p, d, sink, first, ny, buf, dest)) return rc;
         }
     }
-    if (streamed) {
-        if (prev.valid)
-            if (int rc = ring_drain(p, sink, prev.first, prev.count, prev.buf, stage.p + (size_t)prev.buf * nbY * oe)) return rc;
-        hipError_t e = p->ring->wait_idle();
-        if (e != hipSuccess) return api_fail(FFTCONV_ERR_HIP, "host-output copy failed: %s", hipGetErrorString(e));
-    }
+    if (d.route == Route::Ring)
+        if (int rc = ring_finish(p, sink)) return rc;
     FC_VERBOSE(p, "FFT done");                                        // src/cudaConvolutionFFT.cu:258
     return 0;
+}
+
+// Options that are a `long` member of the plan and nothing else: fftconv_plan_set_option and fftconv_plan_get_option are both
+// served from this table.  Options with logic of their own are code in those two functions.
+enum : unsigned {
+    OPT_BOOL = 1,       // stored as value != 0
+    OPT_REJECT = 2,     // a value outside [lo, hi] is an error (otherwise it is clamped)
+    OPT_FORGETS = 4,    // the kernel column spectra in A depend on it: forget_prepared
+    OPT_RING = 8,       // the host-output ring is sized by it: torn down, rebuilt by the next host-output call
+    OPT_GET_ONLY = 16,  // get_option only: read-only, or set_option handles the name in code
+    OPT_SET_ONLY = 32,
+};
+struct LongOption {
+    const char* name;
+    long fftconv_plan::*member;
+    long lo, hi;
+    unsigned flags;
+};
+const LongOption kLongOptions[] = {
+    {"tune_placement", &fftconv_plan::opt_tune_placement, -1, 8, 0},
+    {"kernel_chunk_mb", &fftconv_plan::opt_kernel_chunk_mb, 0, LONG_MAX, OPT_FORGETS},
+    {"batch_maps", &fftconv_plan::opt_batch_maps, 0, LONG_MAX, OPT_FORGETS},
+    {"verbose", &fftconv_plan::opt_verbose, 0, 1, OPT_BOOL},
+    {"flip_kernels", &fftconv_plan::opt_flip_kernels, 0, 1, OPT_BOOL | OPT_FORGETS},
+    {"host_pinned", &fftconv_plan::opt_host_pinned, 0, 1, OPT_BOOL},
+    {"host_min_kb", &fftconv_plan::opt_host_min_kb, 0, 1 << 30, OPT_REJECT},
+    {"host_stream", &fftconv_plan::opt_host_stream, 0, 1 << 20, OPT_REJECT | OPT_RING},   // (0, 1 or 2: checked once the ring is down)
+    {"host_threads", &fftconv_plan::opt_host_threads, 0, 1 << 20, OPT_REJECT | OPT_RING | OPT_SET_ONLY},
+    {"host_chunk_kb", &fftconv_plan::opt_host_chunk_kb, 0, 1 << 20, OPT_REJECT | OPT_RING | OPT_SET_ONLY},
+    {"host_slots", &fftconv_plan::opt_host_slots, 0, 1 << 20, OPT_REJECT | OPT_RING | OPT_SET_ONLY},
+    {"tuned_candidates", &fftconv_plan::tuned_candidates, 0, 0, OPT_GET_ONLY},
+    {"tuned_best", &fftconv_plan::tuned_best, 0, 0, OPT_GET_ONLY},
+    {"output_region", &fftconv_plan::opt_region, 0, 0, OPT_GET_ONLY},
+    {"dynamic_tiles", &fftconv_plan::opt_dynamic_tiles, 0, 0, OPT_GET_ONLY},
+    {"defer_prepare", &fftconv_plan::opt_defer_prepare, 0, 0, OPT_GET_ONLY},
+};
+const LongOption* find_option(const char* name, unsigned not_flag) {
+    for (const LongOption& o : kLongOptions)
+        if (!strcmp(name, o.name)) return (o.flags & not_flag) ? nullptr : &o;
+    return nullptr;
 }
 
 }  // namespace
 
 namespace fc {
 
+int launch_region(const fftconv_plan* p, const float* src, float* dst, int nmaps, hipStream_t s) {
+    const Geometry& g = p->g;      // (block-wise plans: g holds the whole window)
+    if (p->opt_region == 4) HIP_TRY(launch_pad_maps(src, g.fft_h, g.fft_w, g.map_elems(), dst, p->out_h, p->out_w, p->out_elems(), nmaps, s));
+    else HIP_TRY(launch_crop_maps(src, g.fft_h, g.map_elems(), dst, p->out_h, p->out_w, p->out_elems(), p->off_h, p->off_w, nmaps, s));
+    return 0;
+}
+
 // run_group_impl + on failure: nothing of the host-output ring may still be writing into the
 // caller's buffers when the error is returned
 int run_group(fftconv_plan* p, int n, const float* dk, int kh, int kw, const Sink& sink) {
     const int rc = run_group_impl(p, n, dk, kh, kw, sink);
-    if (rc && p->ring) {
-        const std::string keep = g_last_error;
-        (void)p->ring->wait_idle();
-        g_last_error = keep;
-    }
+    if (rc && p->ring) (void)keep_error([&] { return p->ring->wait_idle(); });
     return rc;
 }
 
@@ -358,6 +410,52 @@ int fftconv_plan_create_ex(fftconv_plan** plan, int data_h, int data_w, int feat
 
 }  // extern "C"
 
+// What a fresh single-pass plan needs on its device: the kernels' attributes, its tables (Tables -> DeviceTables), the tile queue.
+static int plan_device_setup(fftconv_plan* p) {
+    const Tables& t = p->t;
+    DeviceTables& d = p->d;
+    if (int rc = use_device(p)) return rc;
+    hipError_t e = kernels_init();
+    if (e != hipSuccess) return api_fail(FFTCONV_ERR_HIP, "kernel setup failed: %s", hipGetErrorString(e));
+    if (int rc = upload(p->tw_m, t.pm.tw, &d.tw_m)) return rc;
+    if (int rc = upload(p->tw_w, t.pw.tw, &d.tw_w)) return rc;
+    if (int rc = upload(p->pairs, t.pairs, &d.pairs)) return rc;
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, p->gpu_id) == hipSuccess && prop.multiProcessorCount > 0) p->num_cus = prop.multiProcessorCount;
+    if (p->g.fast_cols.ok) {
+        const FastColsTables& ft = t.fcl;
+        if (int rc = upload(p->fc_tw1, ft.tw1, &d.fc_tw1)) return rc;
+        if (int rc = upload(p->fc_tw2, ft.tw2, &d.fc_tw2)) return rc;
+        if (int rc = upload(p->fc_pairs, ft.pairs, &d.fc_pairs)) return rc;
+        if (int rc = upload(p->fc_rowoff, ft.rowoff, &d.fc_rowoff)) return rc;
+        if (int rc = upload(p->fc_pair_row_of, ft.pair_row_of, &d.fc_pair_row_of)) return rc;
+        // Dynamic tile queue of the persistent OUTPUT kernel (option "dynamic_tiles"): on by default where a tile is long enough
+        // for its one-ahead ticket to arrive in time -- M >= 432.  Alone on the GPU it then measures equal or up to 3 % faster
+        // than the static deal, beside another kernel it loses half as much (profiles/r05a_contention_ab.txt); on the short
+        // tiles of small transforms (M = 336: +18 %, cfg1's M = 144: +4 us a launch) it does not pay
+        // (profiles/r05k_dynamic_tiles_by_size.txt).  Zeroed once; every launch leaves the counters at zero.
+        if (int rc = p->queue.ensure(FC_QUEUE_WORDS)) return rc;
+        if (hipMemset(p->queue.p, 0, FC_QUEUE_WORDS * sizeof(int)) != hipSuccess) return api_fail(FFTCONV_ERR_HIP, "hipMemset of the tile queue failed");
+        p->opt_dynamic_tiles = p->g.M >= 432 ? 1 : 0;
+        d.queue = p->opt_dynamic_tiles ? p->queue.p : nullptr;
+    }
+    if (p->g.fast_rows.ok && p->g.F == 1) {   // resident workgroups per CU of the multi-map row kernel: what rows_group_auto deals over
+        FastRowsArgs qa = fast_rows_args(p->g, d, nullptr, p->g.max_kw, nullptr, nullptr);
+        int per_cu = 0;
+        if (fast_rows_multi_wgs_per_cu(p->g.Lw, fast_rows_nz2(p->g, std::min(p->g.max_kw, p->g.fast_rows.max_kw)), qa, &per_cu) == hipSuccess && per_cu > 0)
+            p->g.rows_slots_per_cu = per_cu;
+        else
+            (void)hipGetLastError();
+    }
+    if (p->g.fast_rows.ok) {
+        const FastRowsTables& fr = t.fr;
+        if (int rc = upload(p->fr_tw1, fr.tw1, &d.fr_tw1)) return rc;
+        if (int rc = upload(p->fr_tw2, fr.tw2, &d.fr_tw2)) return rc;
+        if (int rc = upload(p->fr_map, fr.relayout, &d.fr_relayout)) return rc;
+    }
+    return 0;
+}
+
 // cyclic: the block plan of an overlap-save block-wise plan (PlanTuning::cyclic) -- never block-wise itself
 int fc::plan_create_internal(fftconv_plan** plan, int data_h, int data_w, int feature_dim, int max_kernel_h, int max_kernel_w, int gpu_id,
                          void* hip_stream, const fftconv_plan_options* options, bool cyclic) {
@@ -369,12 +467,9 @@ int fc::plan_create_internal(fftconv_plan** plan, int data_h, int data_w, int fe
     if (int rc = fftconv_device_count(&ndev)) return rc;
     if (gpu_id < 0) HIP_TRY(hipGetDevice(&gpu_id));
     if (gpu_id >= ndev) return api_fail(FFTCONV_ERR_NO_DEVICE, "gpu_id %d out of range (%d devices)", gpu_id, ndev);
+    if (options && options->struct_size < kOptionsMinSize) return api_fail(FFTCONV_ERR_INVALID_ARG, "fftconv_plan_options.struct_size is not set");
     fftconv_plan* p = new (std::nothrow) fftconv_plan();
     if (!p) return api_fail(FFTCONV_ERR_ALLOC, "out of host memory");
-    if (options && options->struct_size < kOptionsMinSize) {
-        delete p;
-        return api_fail(FFTCONV_ERR_INVALID_ARG, "fftconv_plan_options.struct_size is not set");
-    }
     PlanTuning tune = tuning_from(options);
     tune.cyclic = cyclic;
     if (cyclic) { tune.exact_window = false; tune.max_transform = 0; }
@@ -386,101 +481,26 @@ int fc::plan_create_internal(fftconv_plan** plan, int data_h, int data_w, int fe
     // large single-pass sizes run on the slower long-transform kernels: blocks of a mid-sized transform (overlap-save, the
     // output kernel storing each block's rectangle of the maps directly) are faster where the cost model says so
     if (single_pass && may_block && blocks_preferred(p->g, options)) single_pass = false;
-    if (!single_pass) {
-        // too large for one LDS-resident pass (or beyond max_transform), or faster in blocks: a block-wise plan, unless the caller opted out
-        int rc = FFTCONV_ERR_UNSUPPORTED_SIZE;
-        if (cyclic)
-            (void)api_fail(FFTCONV_ERR_UNSUPPORTED_SIZE, "no specialised kernels for a %dx%d block transform with kernels up to %dx%d", data_h, data_w,
-                       max_kernel_h, max_kernel_w);
-        else if (tune.exact_window)
-            (void)api_fail(FFTCONV_ERR_UNSUPPORTED_SIZE,
-                       "sizes %dx%dx%d with kernels up to %dx%d: exact_window needs transforms of the %dx%d window itself (complex lengths %d and %d, "
-                       "direct or by Bluestein), and their work lengths do not fit the single-pass LDS transform%s", data_h, data_w, feature_dim,
-                       max_kernel_h, max_kernel_w, fft_size16(data_h + max_kernel_h - 1), fft_size16(data_w + max_kernel_w - 1),
-                       fft_size16(data_h + max_kernel_h - 1) / 2, fft_size16(data_w + max_kernel_w - 1), tune.max_transform > 0 ? " within max_transform" : "");
-        else if (options_no_blockwise(options))
-            (void)api_fail(FFTCONV_ERR_UNSUPPORTED_SIZE, "sizes %dx%dx%d with kernels up to %dx%d do not fit the single-pass LDS transform%s", data_h,
-                       data_w, feature_dim, max_kernel_h, max_kernel_w, tune.max_transform > 0 ? " within max_transform" : "");
-        else
-            rc = tiled_create(p, data_h, data_w, feature_dim, max_kernel_h, max_kernel_w, hip_stream, options);
-        if (rc) { delete p; return rc; }
-        { std::lock_guard<std::mutex> lk(g_live_mutex); g_live_plans.insert(p); }
-        *plan = p;
-        return 0;
-    }
     int rc = 0;
-    do {
-        if ((rc = use_device(p))) break;
-        hipError_t e = kernels_init();
-        if (e != hipSuccess) { rc = api_fail(FFTCONV_ERR_HIP, "kernel setup failed: %s", hipGetErrorString(e)); break; }
-        if ((rc = p->tw_m.ensure(p->t.pm.tw.size()))) break;
-        if ((rc = p->tw_w.ensure(p->t.pw.tw.size()))) break;
-        if ((rc = p->pairs.ensure(p->t.pairs.size()))) break;
-        auto cp = [&](void* dst, const void* src, size_t bytes) -> int {
-            HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
-            return 0;
-        };
-        if ((rc = cp(p->tw_m.p, p->t.pm.tw.data(), p->t.pm.tw.size() * sizeof(c32)))) break;
-        if ((rc = cp(p->tw_w.p, p->t.pw.tw.data(), p->t.pw.tw.size() * sizeof(c32)))) break;
-        if ((rc = cp(p->pairs.p, p->t.pairs.data(), p->t.pairs.size() * sizeof(PairEntry)))) break;
-        p->d.tw_m = p->tw_m.p;
-        p->d.tw_w = p->tw_w.p;
-        p->d.pairs = p->pairs.p;
-        {
-            hipDeviceProp_t prop;
-            if (hipGetDeviceProperties(&prop, gpu_id) == hipSuccess && prop.multiProcessorCount > 0)
-                p->num_cus = prop.multiProcessorCount;
-        }
-        if (p->g.fast_cols.ok) {
-            const FastColsTables& ft = p->t.fcl;
-            if ((rc = p->fc_tw1.ensure(ft.tw1.size()))) break;
-            if ((rc = p->fc_tw2.ensure(ft.tw2.size()))) break;
-            if ((rc = p->fc_pairs.ensure(ft.pairs.size()))) break;
-            if ((rc = p->fc_rowoff.ensure(ft.rowoff.size()))) break;
-            if ((rc = cp(p->fc_tw1.p, ft.tw1.data(), ft.tw1.size() * sizeof(c32)))) break;
-            if ((rc = cp(p->fc_tw2.p, ft.tw2.data(), ft.tw2.size() * sizeof(c32)))) break;
-            if ((rc = cp(p->fc_pairs.p, ft.pairs.data(), ft.pairs.size() * sizeof(PairEntry)))) break;
-            if ((rc = cp(p->fc_rowoff.p, ft.rowoff.data(), ft.rowoff.size() * sizeof(int)))) break;
-            p->d.fc_tw1 = p->fc_tw1.p;
-            p->d.fc_tw2 = p->fc_tw2.p;
-            p->d.fc_pairs = p->fc_pairs.p;
-            p->d.fc_rowoff = p->fc_rowoff.p;
-            if ((rc = p->fc_pair_row_of.ensure(ft.pair_row_of.size()))) break;
-            if ((rc = cp(p->fc_pair_row_of.p, ft.pair_row_of.data(), ft.pair_row_of.size() * sizeof(int)))) break;
-            p->d.fc_pair_row_of = p->fc_pair_row_of.p;
-            // Dynamic tile queue of the persistent OUTPUT kernel (option "dynamic_tiles"): on by default where a tile is long enough
-            // for its one-ahead ticket to arrive in time -- M >= 432.  Alone on the GPU it then measures equal or up to 3 % faster
-            // than the static deal, beside another kernel it loses half as much (profiles/r05a_contention_ab.txt); on the short
-            // tiles of small transforms (M = 336: +18 %, cfg1's M = 144: +4 us a launch) it does not pay
-            // (profiles/r05k_dynamic_tiles_by_size.txt).  Zeroed once; every launch leaves the counters at zero.
-            if ((rc = p->queue.ensure(FC_QUEUE_WORDS))) break;
-            if (hipMemset(p->queue.p, 0, FC_QUEUE_WORDS * sizeof(int)) != hipSuccess) { rc = api_fail(FFTCONV_ERR_HIP, "hipMemset of the tile queue failed"); break; }
-            p->opt_dynamic_tiles = p->g.M >= 432 ? 1 : 0;
-            p->d.queue = p->opt_dynamic_tiles ? p->queue.p : nullptr;
-        }
-        if (p->g.fast_rows.ok && p->g.F == 1) {   // resident workgroups per CU of the multi-map row kernel: what rows_group_auto deals over
-            FastRowsArgs qa = fast_rows_args(p->g, p->d, nullptr, p->g.max_kw, nullptr, nullptr);
-            int per_cu = 0;
-            if (fast_rows_multi_wgs_per_cu(p->g.Lw, fast_rows_nz2(p->g, std::min(p->g.max_kw, p->g.fast_rows.max_kw)), qa, &per_cu) == hipSuccess && per_cu > 0)
-                p->g.rows_slots_per_cu = per_cu;
-            else
-                (void)hipGetLastError();
-        }
-        if (p->g.fast_rows.ok) {
-            const FastRowsTables& fr = p->t.fr;
-            if ((rc = p->fr_tw1.ensure(fr.tw1.size()))) break;
-            if ((rc = p->fr_tw2.ensure(fr.tw2.size()))) break;
-            if ((rc = p->fr_map.ensure(fr.relayout.size()))) break;
-            if ((rc = cp(p->fr_tw1.p, fr.tw1.data(), fr.tw1.size() * sizeof(c32)))) break;
-            if ((rc = cp(p->fr_tw2.p, fr.tw2.data(), fr.tw2.size() * sizeof(c32)))) break;
-            if ((rc = cp(p->fr_map.p, fr.relayout.data(), fr.relayout.size() * sizeof(int)))) break;
-            p->d.fr_tw1 = p->fr_tw1.p;
-            p->d.fr_tw2 = p->fr_tw2.p;
-            p->d.fr_relayout = p->fr_map.p;
-        }
-    } while (0);
+    if (single_pass)
+        rc = plan_device_setup(p);
+    // too large for one LDS-resident pass (or beyond max_transform), or faster in blocks: a block-wise plan, unless the caller opted out
+    else if (cyclic)
+        rc = api_fail(FFTCONV_ERR_UNSUPPORTED_SIZE, "no specialised kernels for a %dx%d block transform with kernels up to %dx%d", data_h, data_w,
+                      max_kernel_h, max_kernel_w);
+    else if (tune.exact_window)
+        rc = api_fail(FFTCONV_ERR_UNSUPPORTED_SIZE,
+                      "sizes %dx%dx%d with kernels up to %dx%d: exact_window needs transforms of the %dx%d window itself (complex lengths %d and %d, "
+                      "direct or by Bluestein), and their work lengths do not fit the single-pass LDS transform%s", data_h, data_w, feature_dim,
+                      max_kernel_h, max_kernel_w, fft_size16(data_h + max_kernel_h - 1), fft_size16(data_w + max_kernel_w - 1),
+                      fft_size16(data_h + max_kernel_h - 1) / 2, fft_size16(data_w + max_kernel_w - 1), tune.max_transform > 0 ? " within max_transform" : "");
+    else if (options_no_blockwise(options))
+        rc = api_fail(FFTCONV_ERR_UNSUPPORTED_SIZE, "sizes %dx%dx%d with kernels up to %dx%d do not fit the single-pass LDS transform%s", data_h,
+                      data_w, feature_dim, max_kernel_h, max_kernel_w, tune.max_transform > 0 ? " within max_transform" : "");
+    else
+        rc = tiled_create(p, data_h, data_w, feature_dim, max_kernel_h, max_kernel_w, hip_stream, options);
     if (rc) {
-        p->release_all();
+        p->release_all();      // (what plan_device_setup had uploaded; nothing in the other cases)
         delete p;
         return rc;
     }
@@ -581,21 +601,20 @@ int fftconv_plan_set_image(fftconv_plan* plan, const float* data, int location) 
     if (p->deferred.on && p->deferred.stream != p->stream)
         if (int rc = flush_pending_prepare(p)) return rc;
     if (int rc = p->prof_begin(PK_IMAGE_COLS, g.F)) return rc;
-    if (g.fast_fwd && p->deferred.on) {
-        // the deferred kernel-column pass of fftconv_plan_prepare_kernels_packed and the image's column pass: ONE launch
-        const auto pd = p->deferred;
-        p->deferred.on = false;
+    if (g.fast_fwd) {
         FastColsFwdArgs fa = fast_cols_fwd_args(g, p->d, dimg, (size_t)g.H * g.W, g.H, g.H, g.W, g.F, sgen,
                                                 (size_t)g.rows * g.s_pitch, g.s_pitch, false);
-        FastColsFwdArgs fk = fast_cols_fwd_args(g, p->d, pd.dk, (size_t)pd.kh * pd.kw, pd.kh, pd.kh, pd.kw, pd.na * g.F, p->A.p,
-                                                (size_t)g.rows * a_pitch_for(pd.kw), a_pitch_for(pd.kw), true);
-        FC_VERBOSE(p, "image columns (%d tiles) and the columns of %d kernels (%d tiles) in one launch", fa.ntiles, pd.na, fk.ntiles);
-        HIP_TRY(launch_fast_cols_fwd_pair(g.M, g.fast_cols.T, fa, fk, fast_cols_fwd_pruned_ok(g.fast_cols, pd.kh), p->num_cus, p->stream));
-        p->prepared.dk = pd.dk; p->prepared.n = pd.n; p->prepared.kh = pd.kh; p->prepared.kw = pd.kw; p->prepared.stream = p->stream;
-    } else if (g.fast_fwd) {
-        FastColsFwdArgs fa = fast_cols_fwd_args(g, p->d, dimg, (size_t)g.H * g.W, g.H, g.H, g.W, g.F, sgen,
-                                                (size_t)g.rows * g.s_pitch, g.s_pitch, false);
-        HIP_TRY(launch_fast_cols_fwd(g.M, g.fast_cols.T, false, fa, p->num_cus, p->stream));
+        if (p->deferred.on) {
+            // the deferred kernel-column pass of fftconv_plan_prepare_kernels_packed and the image's column pass: ONE launch
+            const auto pd = p->deferred;
+            p->deferred.on = false;
+            FastColsFwdArgs fk = fast_cols_fwd_args(g, p->d, pd.dk, (size_t)pd.kh * pd.kw, pd.kh, pd.kh, pd.kw, pd.na * g.F, p->A.p,
+                                                    (size_t)g.rows * a_pitch_for(pd.kw), a_pitch_for(pd.kw), true);
+            FC_VERBOSE(p, "image columns (%d tiles) and the columns of %d kernels (%d tiles) in one launch", fa.ntiles, pd.na, fk.ntiles);
+            HIP_TRY(launch_fast_cols_fwd_pair(g.M, g.fast_cols.T, fa, fk, fast_cols_fwd_pruned_ok(g.fast_cols, pd.kh), p->num_cus, p->stream));
+            p->prepared = pd;      // (pd.stream is p->stream: a request on another stream was flushed above)
+        } else
+            HIP_TRY(launch_fast_cols_fwd(g.M, g.fast_cols.T, false, fa, p->num_cus, p->stream));
     } else {
         ColsR2CArgs ia = image_cols_args(g, p->t, p->d, dimg, sgen);
         HIP_TRY(launch_cols_r2c(ia, tiles_for(g.W, g.T_cols), g.F, cols_threads(g), p->cols_lds(), p->stream));
@@ -644,11 +663,9 @@ static int spectrum_exchange(fftconv_plan* p, float* spectrum, int location, boo
     if (to_natural && !p->have_image) return api_fail(FFTCONV_ERR_NO_IMAGE, "no image spectrum: call fftconv_plan_set_image first");
     if (int rc = use_device(p)) return rc;
     if (int rc = p->ensure_spectrum()) return rc;
-    if (!p->nat_row_of.p) {
-        if (int rc = p->nat_row_of.ensure(p->t.nat_row_of.size())) return rc;
-        if (int rc = p->nat_col_of.ensure(p->t.nat_col_of.size())) return rc;
-        HIP_TRY(hipMemcpy(p->nat_row_of.p, p->t.nat_row_of.data(), p->t.nat_row_of.size() * sizeof(int), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(p->nat_col_of.p, p->t.nat_col_of.data(), p->t.nat_col_of.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (!p->nat_col_of.p) {     // (the second of the two: both are there, or both are uploaded again)
+        if (int rc = upload(p->nat_row_of, p->t.nat_row_of)) return rc;
+        if (int rc = upload(p->nat_col_of, p->t.nat_col_of)) return rc;
     }
     const size_t n = (size_t)g.F * g.fft_w * g.rows;
     c32* nat = reinterpret_cast<c32*>(spectrum);
@@ -715,11 +732,8 @@ int fftconv_plan_convolve_packed(fftconv_plan* plan, int n_kernel, const float* 
         std::vector<int> khs(n_kernel, kernel_h), kws(n_kernel, kernel_w);
         for (int j = 0; j < n_kernel; j++) kp[j] = kernels_device + per * j;
         const int rc = tiled_convolve(plan, n_kernel, kp.data(), khs.data(), kws.data(), FFTCONV_DEVICE, nullptr, FFTCONV_DEVICE, out_device);
-        if (rc) {     // as fftconv_plan_convolve: nothing of a failed call may still be running when the error is returned
-            const std::string keep = g_last_error;
-            (void)hipStreamSynchronize(plan->tiled->sub->stream);
-            g_last_error = keep;
-        }
+        // as fftconv_plan_convolve: nothing of a failed call may still be running when the error is returned
+        if (rc) (void)keep_error([&] { return hipStreamSynchronize(plan->tiled->sub->stream); });
         return rc;
     }
     Sink sink;
@@ -740,15 +754,16 @@ int fftconv_plan_prepare_kernels_packed(fftconv_plan* plan, int n_kernel, const 
     if (int rc = flush_pending_prepare(p)) return rc;      // an earlier request nobody consumed
     if (int rc = p->A.ensure(bs.per_a * bs.nbA)) return rc;
     p->prepared.dk = nullptr;
+    const KernelSet ks{kernels_device, n_kernel, kernel_h, kernel_w, p->stream};
     const bool timed_apart = p->profile && (p->profile_mask & ((1u << PK_KERNEL_COLS) | (1u << PK_IMAGE_COLS)));   // per-kind figures wanted
     if (p->opt_defer_prepare && p->g.fast_fwd && !p->opt_flip_kernels && !timed_apart) {   // deferred: rides in the launch of the next image's column pass
-        p->deferred.on = true; p->deferred.dk = kernels_device; p->deferred.n = n_kernel; p->deferred.na = std::min(bs.nbA, n_kernel);
-        p->deferred.kh = kernel_h; p->deferred.kw = kernel_w; p->deferred.stream = p->stream;
+        static_cast<KernelSet&>(p->deferred) = ks;
+        p->deferred.on = true;
+        p->deferred.na = std::min(bs.nbA, n_kernel);
         return 0;
     }
     if (int rc = launch_kernel_cols(p, kernels_device, 0, std::min(bs.nbA, n_kernel), kernel_h, kernel_w)) return rc;
-    p->prepared.dk = kernels_device; p->prepared.n = n_kernel; p->prepared.kh = kernel_h; p->prepared.kw = kernel_w;
-    p->prepared.stream = p->stream;
+    p->prepared = ks;
     return 0;
 }
 
@@ -761,13 +776,9 @@ int fftconv_plan_convolve(fftconv_plan* plan, int n_kernel, const float* const* 
     const Geometry& g = p->g;
     if (int rc = use_device(p)) return rc;
     if (p->tiled) {
-        if (int rc = tiled_convolve(p, n_kernel, kernels, kernel_h, kernel_w, kernel_location, out, out_location, nullptr)) {
-            const std::string keep = g_last_error;
-            (void)hipStreamSynchronize(p->tiled->sub->stream);   // nothing may still be writing into the caller's buffers
-            g_last_error = keep;
-            return rc;
-        }
-        return 0;
+        const int rc = tiled_convolve(p, n_kernel, kernels, kernel_h, kernel_w, kernel_location, out, out_location, nullptr);
+        if (rc) (void)keep_error([&] { return hipStreamSynchronize(p->tiled->sub->stream); });   // nothing may still be writing into the caller's buffers
+        return rc;
     }
     if (!p->have_image) return api_fail(FFTCONV_ERR_NO_IMAGE, "no image spectrum: call fftconv_plan_set_image first");
     // validate everything up front so nothing is launched on a bad cell (the reference fails
@@ -777,10 +788,8 @@ int fftconv_plan_convolve(fftconv_plan* plan, int n_kernel, const float* const* 
         if (int rc = check_kernel_size(p, kernel_h[k], kernel_w[k])) return rc;
     }
     // groups of consecutive kernels of equal size
-    int k0 = 0;
-    while (k0 < n_kernel) {
-        int k1 = k0 + 1;
-        while (k1 < n_kernel && kernel_h[k1] == kernel_h[k0] && kernel_w[k1] == kernel_w[k0]) k1++;
+    for (int k0 = 0, k1; k0 < n_kernel; k0 = k1) {
+        k1 = same_size_run_end(kernel_h, kernel_w, k0, n_kernel);
         const int n = k1 - k0, kh = kernel_h[k0], kw = kernel_w[k0];
         const size_t per = (size_t)g.F * kh * kw;
         const float* dk = nullptr;
@@ -797,24 +806,18 @@ int fftconv_plan_convolve(fftconv_plan* plan, int n_kernel, const float* const* 
         } else {
             if (int rc = p->K.ensure(per * n)) return rc;
             for (int j = 0; j < n; j++)
-                HIP_TRY(hipMemcpyAsync(p->K.p + per * j, kernels[k0 + j], per * sizeof(float),
-                                       kernel_location == FFTCONV_HOST ? hipMemcpyHostToDevice
-                                       : kernel_location == FFTCONV_AUTO ? hipMemcpyDefault : hipMemcpyDeviceToDevice,
-                                       p->stream));
+                HIP_TRY(hipMemcpyAsync(p->K.p + per * j, kernels[k0 + j], per * sizeof(float), copy_kind(kernel_location, true), p->stream));
             dk = p->K.p;
         }
         Sink sink;
         sink.ptrs = out + k0;
         sink.location = out_location;
         const int rcg = run_group(p, n, dk, kh, kw, sink);
-        if (kernels_pinned) {
-            const std::string keep = g_last_error;
-            const int rcm = p->pin_k.mark(p->stream);
-            if (rcg) g_last_error = keep;
-            else if (rcm) return rcm;
+        if (kernels_pinned) {      // (whatever the group's outcome: the launches that read the buffer are in the stream)
+            if (rcg) (void)keep_error([&] { return p->pin_k.mark(p->stream); });
+            else if (int rcm = p->pin_k.mark(p->stream)) return rcm;
         }
         if (rcg) return rcg;
-        k0 = k1;
     }
     if (out_location == FFTCONV_HOST) HIP_TRY(hipStreamSynchronize(p->stream));
     return 0;
@@ -851,9 +854,18 @@ int fftconv_plan_set_option(fftconv_plan* plan, const char* name, long value) {
         if (!strcmp(name, "verbose")) plan->opt_verbose = value != 0;
         return fftconv_plan_set_option(plan->tiled->sub, name, value);
     }
-    if (!strcmp(name, "tune_placement")) { plan->opt_tune_placement = value < 0 ? -1 : (value > 8 ? 8 : value); return 0; }
-    if (!strcmp(name, "kernel_chunk_mb")) { plan->opt_kernel_chunk_mb = value < 0 ? 0 : value; plan->prepared.dk = nullptr; plan->deferred.on = false; return 0; }
-    if (!strcmp(name, "batch_maps")) { plan->opt_batch_maps = value < 0 ? 0 : value; plan->prepared.dk = nullptr; plan->deferred.on = false; return 0; }
+    if (const LongOption* o = find_option(name, OPT_GET_ONLY)) {
+        if ((o->flags & OPT_REJECT) && (value < o->lo || value > o->hi)) return api_fail(FFTCONV_ERR_INVALID_ARG, "option '%s' out of range", name);
+        if (o->flags & OPT_RING) {
+            if (int rc = use_device(plan)) return rc;
+            HIP_TRY(hipStreamSynchronize(plan->stream));
+            plan->release_ring();
+            if (o->member == &fftconv_plan::opt_host_stream && value > 2) return api_fail(FFTCONV_ERR_INVALID_ARG, "host_stream is 0, 1 or 2");
+        }
+        plan->*(o->member) = (o->flags & OPT_BOOL) ? (value != 0) : std::min(std::max(value, o->lo), o->hi);
+        if (o->flags & OPT_FORGETS) plan->forget_prepared();
+        return 0;
+    }
     if (!strcmp(name, "profile")) {
         if (value != 0 && plan->deferred.on && (plan->profile_mask & ((1u << PK_KERNEL_COLS) | (1u << PK_IMAGE_COLS)))) {   // per-kind figures: the kernels' column pass is timed as a launch of its own
             if (int rc = use_device(plan)) return rc;
@@ -862,7 +874,6 @@ int fftconv_plan_set_option(fftconv_plan* plan, const char* name, long value) {
         plan->profile = value != 0;
         return 0;
     }
-    if (!strcmp(name, "verbose")) { plan->opt_verbose = value != 0; return 0; }
     if (!strcmp(name, "dynamic_tiles")) {
         // 1: the persistent output kernel takes its tiles from a queue in device memory (fast_cols.hpp: TileQueue; the default
         // from M = 432 on) instead of a fixed share per workgroup (0); 2: the forward column kernels (image, kernels) too.  A step
@@ -911,23 +922,6 @@ int fftconv_plan_set_option(fftconv_plan* plan, const char* name, long value) {
         plan->opt_region = value; plan->out_h = oh; plan->out_w = ow; plan->off_h = fh; plan->off_w = fw;
         return 0;
     }
-    if (!strcmp(name, "flip_kernels")) { plan->opt_flip_kernels = value != 0; plan->prepared.dk = nullptr; plan->deferred.on = false; return 0; }
-    if (!strcmp(name, "host_pinned")) { plan->opt_host_pinned = value != 0; return 0; }
-    if (!strcmp(name, "host_min_kb")) {
-        if (value < 0 || value > (1 << 30)) return api_fail(FFTCONV_ERR_INVALID_ARG, "option '%s' out of range", name);
-        plan->opt_host_min_kb = value;
-        return 0;
-    }
-    if (!strcmp(name, "host_stream") || !strcmp(name, "host_threads") || !strcmp(name, "host_chunk_kb") || !strcmp(name, "host_slots")) {
-        if (value < 0 || value > (1 << 20)) return api_fail(FFTCONV_ERR_INVALID_ARG, "option '%s' out of range", name);
-        if (int rc = use_device(plan)) return rc;
-        HIP_TRY(hipStreamSynchronize(plan->stream));
-        plan->release_ring();      // rebuilt with the new shape by the next host-output call
-        if (!strcmp(name, "host_stream") && value > 2) return api_fail(FFTCONV_ERR_INVALID_ARG, "host_stream is 0, 1 or 2");
-        (!strcmp(name, "host_stream") ? plan->opt_host_stream : name[5] == 't' ? plan->opt_host_threads
-         : name[5] == 'c' ? plan->opt_host_chunk_kb : plan->opt_host_slots) = value;
-        return 0;
-    }
     return api_fail(FFTCONV_ERR_INVALID_ARG, "unknown option '%s'", name);
 }
 
@@ -936,25 +930,13 @@ int fftconv_plan_get_option(fftconv_plan* plan, const char* name, long* value) {
     if (!strcmp(name, "blockwise")) { *value = plan->tiled ? plan->tiled->nblk : 0; return 0; }   // read-only: number of blocks (0 = one pass)
     if (!strcmp(name, "overlap_save")) { *value = plan->tiled && plan->tiled->save ? 1 : 0; return 0; }   // read-only: blocks stored by the output kernel (1) or summed (0)
     if (plan->tiled && strcmp(name, "output_region")) return fftconv_plan_get_option(plan->tiled->sub, name, value);
-    if (!strcmp(name, "batch_maps")) { *value = plan->opt_batch_maps; return 0; }
-    if (!strcmp(name, "kernel_chunk_mb")) { *value = plan->opt_kernel_chunk_mb; return 0; }
-    if (!strcmp(name, "tune_placement")) { *value = plan->opt_tune_placement; return 0; }
-    if (!strcmp(name, "tuned_candidates")) { *value = plan->tuned_candidates; return 0; }
-    if (!strcmp(name, "tuned_best")) { *value = plan->tuned_best; return 0; }
+    if (const LongOption* o = find_option(name, OPT_SET_ONLY)) { *value = plan->*(o->member); return 0; }
     if (!strcmp(name, "rows_group")) { *value = plan->g.rows_group; return 0; }
     // read-only: which passes of this plan run on specialised (compile-time) kernels: bit 0 the spectral rows (w), bit 1 the
     // column passes (h: image / kernel columns forwards, output columns); 3 = no generic kernel runs
     if (!strcmp(name, "specialised_kernels")) { *value = (plan->g.fast_rows.ok ? 1 : 0) | (plan->g.fast_cols.ok ? 2 : 0); return 0; }
     if (!strcmp(name, "rows_slots_per_cu")) { *value = plan->g.rows_slots_per_cu; return 0; }   // read-only: resident row workgroups per CU
-    if (!strcmp(name, "host_stream")) { *value = plan->opt_host_stream; return 0; }
-    if (!strcmp(name, "host_min_kb")) { *value = plan->opt_host_min_kb; return 0; }
-    if (!strcmp(name, "host_pinned")) { *value = plan->opt_host_pinned; return 0; }
-    if (!strcmp(name, "output_region")) { *value = plan->opt_region; return 0; }
-    if (!strcmp(name, "flip_kernels")) { *value = plan->opt_flip_kernels; return 0; }
     if (!strcmp(name, "profile")) { *value = plan->profile ? 1 : 0; return 0; }
-    if (!strcmp(name, "verbose")) { *value = plan->opt_verbose; return 0; }
-    if (!strcmp(name, "dynamic_tiles")) { *value = plan->opt_dynamic_tiles; return 0; }
-    if (!strcmp(name, "defer_prepare")) { *value = plan->opt_defer_prepare; return 0; }
     if (!strcmp(name, "prepare_pending")) { *value = plan->deferred.on ? 1 : 0; return 0; }   // read-only: a recorded, not yet launched preparation
     return api_fail(FFTCONV_ERR_INVALID_ARG, "unknown option '%s'", name);
 }
@@ -981,9 +963,7 @@ int fftconv_fft_data(const float* data, int data_h, int data_w, int feature_dim,
     fftconv_plan* p = nullptr;
     if (int rc = fftconv_plan_create(&p, data_h, data_w, feature_dim, kernel_h, kernel_w, gpu_id, nullptr)) return rc;
     if (int rc = fftconv_plan_set_image(p, data, FFTCONV_HOST)) {
-        std::string keep = g_last_error;
-        fftconv_plan_destroy(p);
-        g_last_error = keep;
+        (void)keep_error([&] { return fftconv_plan_destroy(p); });
         return rc;
     }
     *fft_data = p;

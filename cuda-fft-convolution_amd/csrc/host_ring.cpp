@@ -7,8 +7,12 @@
 namespace fc {
 
 // pinned ring + copy stream + host copy threads of the host-output path, sized for this plan's maps
-int ring_ensure(fftconv_plan* p) {
-    if (p->ring) return 0;
+int ring_begin(fftconv_plan* p) {
+    if (p->ring) {
+        p->ring->batch = 0;
+        p->ring->prev.valid = false;
+        return 0;
+    }
     const size_t map_bytes = p->out_elems() * sizeof(float);
     size_t chunk = p->opt_host_chunk_kb > 0 ? (size_t)p->opt_host_chunk_kb << 10 : (size_t)8 << 20;
     chunk = std::min(chunk, (map_bytes + 4095) / 4096 * 4096);
@@ -65,9 +69,13 @@ static bool caller_pinned(const void* ptr) {
     return at.type == hipMemoryTypeHost;
 }
 
-// queue the copy-out of the maps [first, first + count) that sit in staging buffer `buf`
-int ring_drain(fftconv_plan* p, const Sink& sink, int first, int count, int buf, const float* staging) {
+// queue the copy-out of the last launched batch, if it is still waiting for that: the maps [first, first + count) in staging buffer `buf`
+static int ring_drain(fftconv_plan* p, const Sink& sink) {
     HostRing* r = p->ring;
+    if (!r->prev.valid) return 0;
+    r->prev.valid = false;
+    const int first = r->prev.first, count = r->prev.count, buf = r->prev.buf;
+    const float* staging = r->prev.staging;
     const size_t map_bytes = p->out_elems() * sizeof(float);
     if (r->nslots == 0) {   // direct: whole maps, one per host thread at a time
         for (int j = 0; j < count; j++)
@@ -96,6 +104,32 @@ int ring_drain(fftconv_plan* p, const Sink& sink, int first, int count, int buf,
         }
     }
     HIP_TRY(hipEventRecord(r->copy_done[buf], r->copy_stream));
+    return 0;
+}
+
+int ring_claim_staging(fftconv_plan* p, int* buf) {
+    HostRing* r = p->ring;
+    *buf = r->batch & 1;
+    if (r->batch >= 2) {   // the buffer still holds batch - 2 until its copy-out is over
+        if (r->nslots == 0) r->wait_staging_free(*buf);
+        else HIP_TRY(hipStreamWaitEvent(p->stream, r->copy_done[*buf], 0));
+    }
+    return 0;
+}
+
+int ring_batch_launched(fftconv_plan* p, const Sink& sink, int first, int count, int buf, const float* staging) {
+    HostRing* r = p->ring;
+    HIP_TRY(hipEventRecord(r->compute_done[buf], p->stream));
+    if (int rc = ring_drain(p, sink)) return rc;
+    r->prev.valid = true; r->prev.first = first; r->prev.count = count; r->prev.buf = buf; r->prev.staging = staging;
+    r->batch++;
+    return 0;
+}
+
+int ring_finish(fftconv_plan* p, const Sink& sink) {
+    if (int rc = ring_drain(p, sink)) return rc;
+    hipError_t e = p->ring->wait_idle();
+    if (e != hipSuccess) return api_fail(FFTCONV_ERR_HIP, "host-output copy failed: %s", hipGetErrorString(e));
     return 0;
 }
 

@@ -43,6 +43,11 @@ struct HostRing {
     bool stop = false;
     hipError_t worker_error = hipSuccess;
     std::vector<std::thread> workers;
+    // the two device staging buffers of a streamed group (host_ring.cpp: ring_claim_staging, ring_batch_launched): batches launched so
+    // far, and the last one, whose copy-out is queued once the next batch has been launched.  Meaningful between ring_begin, which
+    // resets both, and ring_finish only: a group that failed leaves them as they were
+    int batch = 0;
+    struct { bool valid = false; int first = 0, count = 0, buf = 0; const float* staging = nullptr; } prev;
 
     // Fresh caller buffers (malloc'ed, never touched) would be faulted in page by page inside the
     // runtime's pinning of the destination; populating them here, in the copy threads and ahead

@@ -170,13 +170,6 @@ hipError_t launch_fast_rows_fwd(int L, const FastRowsFwdArgs& a, int rows, hipSt
     return e;
 }
 
-hipError_t launch_fast_rows_multi(int L, int nz2, const FastRowsArgs& a, int rows, int kernels, int kernels_per_wg, hipStream_t s);
-
-// one map per workgroup: the multi-map walk with a walk length of 1 (round 4: the separate one-map kernel is gone)
-hipError_t launch_fast_rows(int L, int nz2, const FastRowsArgs& a, int rows, int kernels, hipStream_t s) {
-    return launch_fast_rows_multi(L, nz2, a, rows, kernels, 1, s);
-}
-
 hipError_t launch_fast_rows_multi(int L, int nz2, const FastRowsArgs& a, int rows, int kernels, int kernels_per_wg, hipStream_t s) {
     if (rows <= 0 || kernels <= 0) return hipSuccess;
     if (a.F < 1 || kernels_per_wg < 1) return hipErrorInvalidValue;

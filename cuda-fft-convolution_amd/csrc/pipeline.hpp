@@ -20,7 +20,7 @@ struct PlanTuning {
     // specialised kernels with the tiled, pair-adjacent intermediate
     int path_mode = 2;
     // maps per workgroup of the multi-map row kernel (fast_rows_multi.hpp): -1 = chosen per
-    // launch (rows_group_for), 0 / 1 = plain one-map kernel, > 1 = fixed
+    // launch (rows_group_for), 0 / 1 = one map per workgroup (the same kernel, a walk of one), > 1 = fixed
     int rows_group = -1;
     // largest transform length a plan may use (0 = whatever fits the LDS); larger problems are left
     // to the block-wise path of the one-shot entry

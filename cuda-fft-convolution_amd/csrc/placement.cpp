@@ -9,7 +9,7 @@ namespace fc {
 // processes sharing one device -- the rehearsals of the N > 1 tests -- stop tuning as soon as the others' buffers are there), five candidates.  Why a
 // default: which state an untuned plan gets is a property of the box -- six of six fresh processes slow on one (369 against 373.5 Gpixel-filters/s at
 // cfg3), five of six fast on another (profiles/r05q_default_vs_tuned_final_library*.txt).
-int placement_auto_candidates(const fftconv_plan* p, size_t launch_map_bytes) {
+static int placement_auto_candidates(const fftconv_plan* p, size_t launch_map_bytes) {
     if (!p->g.fast_cols.ok || launch_map_bytes < ((size_t)2 << 30)) return 0;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return 0; }
@@ -26,11 +26,16 @@ int placement_auto_candidates(const fftconv_plan* p, size_t launch_map_bytes) {
 // freed.  The probes write into `out`, which the convolve that follows overwrites; they read the candidates as
 // allocated (the driver hands out zeroed memory).  Blocking (~70 ms), once per allocation: what FFTW calls
 // measuring at plan time.
-int tune_intermediate_placement(fftconv_plan* p, int k, int n, int nbY, float* out, size_t out_stride_per_map) {
-    // (out_stride_per_map > 0: the call's batches write to out + first_map * stride, and every batch's
-    // destination is probed -- an 18-GB map buffer spans several placement regions; 0: one staging buffer)
+int tune_intermediate_placement(fftconv_plan* p, const Sink& sink, int n, int nbY, float* out, bool direct) {
     const Geometry& g = p->g;
     p->Y.fresh = false;
+    // (an overlap-save block's window is a rectangle inside the maps, not what the probes would write: never tuned)
+    int k = sink.window ? 0 : (int)p->opt_tune_placement;
+    if (k < 0) k = placement_auto_candidates(p, (size_t)std::min(nbY, n) * g.map_elems() * sizeof(float));
+    // (direct: the call's batches write to out + first_map * stride, and every batch's destination is probed -- an 18-GB map
+    // buffer spans several placement regions; otherwise one launch into the one staging buffer)
+    const size_t out_stride_per_map = direct ? p->out_elems() : 0;
+    if (!direct) n = std::min(nbY, n);
     if (k < 2 || !g.fast_cols.ok || n < 1) return 0;
     {   // the tuner synchronises and frees: not inside a stream capture (the first convolve of a graph keeps its allocation)
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;

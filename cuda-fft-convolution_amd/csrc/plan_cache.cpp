@@ -78,6 +78,15 @@ fftconv_plan* cache_take(const CacheKey& key) {
     return nullptr;
 }
 
+// takes the least recently used idle plan out of the cache (lock held) and onto `drop`
+void evict_lru(PlanCache& c, std::vector<fftconv_plan*>& drop) {
+    size_t lru = 0;
+    for (size_t i = 1; i < c.idle.size(); i++)
+        if (c.idle[i].stamp < c.idle[lru].stamp) lru = i;
+    drop.push_back(c.idle[lru].plan);
+    c.idle.erase(c.idle.begin() + (long)lru);
+}
+
 // hand a plan (back) to the cache; plans pushed out by the limits are destroyed (outside the lock)
 void cache_put(const CacheKey& key, fftconv_plan* p) {
     PlanCache& c = plan_cache();
@@ -93,13 +102,7 @@ void cache_put(const CacheKey& key, fftconv_plan* p) {
             }
             c.idle.push_back(CacheEntry{key, p, ++c.clock, plan_device_bytes(p)});
             auto total = [&] { size_t t = 0; for (const CacheEntry& e : c.idle) t += e.bytes; return t; };
-            while (!c.idle.empty() && ((int)c.idle.size() > c.max_plans || (c.idle.size() > 1 && total() > c.max_bytes))) {
-                size_t lru = 0;
-                for (size_t i = 1; i < c.idle.size(); i++)
-                    if (c.idle[i].stamp < c.idle[lru].stamp) lru = i;
-                drop.push_back(c.idle[lru].plan);
-                c.idle.erase(c.idle.begin() + (long)lru);
-            }
+            while (!c.idle.empty() && ((int)c.idle.size() > c.max_plans || (c.idle.size() > 1 && total() > c.max_bytes))) evict_lru(c, drop);
         }
     }
     for (fftconv_plan* d : drop) fftconv_plan_destroy(d);
@@ -115,13 +118,13 @@ bool fc::cache_release_idle() {
         drop.swap(c.idle);
     }
     if (drop.empty()) return false;
-    const std::string keep = api_last_error();
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = -1; }
-    for (CacheEntry& e : drop) (void)fftconv_plan_destroy(e.plan);     // (makes the plan's device current)
-    if (dev >= 0) (void)hipSetDevice(dev);
-    api_set_last_error(keep);
-    return true;
+    return keep_error([&] {
+        int dev = -1;
+        if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = -1; }
+        for (CacheEntry& e : drop) (void)fftconv_plan_destroy(e.plan);     // (makes the plan's device current)
+        if (dev >= 0) (void)hipSetDevice(dev);
+        return true;
+    });
 }
 
 namespace {
@@ -143,13 +146,7 @@ int fftconv_cache_configure(int max_plans, size_t max_bytes) {
         std::lock_guard<std::mutex> lk(c.m);
         c.max_plans = max_plans;
         if (max_bytes) c.max_bytes = max_bytes;
-        while ((int)c.idle.size() > c.max_plans) {
-            size_t lru = 0;
-            for (size_t i = 1; i < c.idle.size(); i++)
-                if (c.idle[i].stamp < c.idle[lru].stamp) lru = i;
-            drop.push_back(c.idle[lru].plan);
-            c.idle.erase(c.idle.begin() + (long)lru);
-        }
+        while ((int)c.idle.size() > c.max_plans) evict_lru(c, drop);
     }
     for (fftconv_plan* d : drop) fftconv_plan_destroy(d);
     return 0;
@@ -270,9 +267,8 @@ int fftconv_convolution_fft_ex(const float* data, int data_h, int data_w, int fe
         sink.ptrs = out;
         sink.location = FFTCONV_HOST;
         rc = run_group(p, n_kernel, staged_dk, kernel_h[0], kernel_w[0], sink);
-        const std::string keep_err = api_last_error();
-        const int rcm = p->pin_k.mark(p->stream);
-        if (!rc) rc = rcm; else api_set_last_error(keep_err);
+        if (rc) (void)keep_error([&] { return p->pin_k.mark(p->stream); });
+        else rc = p->pin_k.mark(p->stream);
         if (!rc) {
             hipError_t e = hipStreamSynchronize(p->stream);
             if (e != hipSuccess) rc = api_fail(FFTCONV_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
@@ -283,15 +279,13 @@ int fftconv_convolution_fft_ex(const float* data, int data_h, int data_w, int fe
     if (rc) p->deferred.on = false;       // (a failed image leaves no request behind in a plan that goes back into the cache)
     tm.convolve_ms = ms_since(t2);
     const auto t3 = std::chrono::steady_clock::now();
-    std::string keep = api_last_error();
     // argument-class failures were found before anything was queued and leave the plan as it was; after a HIP or
     // allocation failure the plan is not trusted again
     const bool reusable = rc == 0 || rc == FFTCONV_ERR_INVALID_ARG || rc == FFTCONV_ERR_KERNEL_SHAPE || rc == FFTCONV_ERR_KERNEL_EXCEEDS_MAX ||
                           rc == FFTCONV_ERR_THREAD_SIZE;
-    if (!p->tiled) { p->prepared.dk = nullptr; p->deferred.on = false; }   // (both may name pin_k, whose contents the next call replaces)
-    if (reusable) cache_put(key, p);
-    else fftconv_plan_destroy(p);
-    if (rc) api_set_last_error(keep);
+    if (!p->tiled) p->forget_prepared();   // (both records may name pin_k, whose contents the next call replaces)
+    auto release = [&] { if (reusable) cache_put(key, p); else (void)fftconv_plan_destroy(p); return 0; };
+    (void)(rc ? keep_error(release) : release());
     tm.release_ms = ms_since(t3);
     tm.total_ms = ms_since(t0);
     g_call_timing = tm;

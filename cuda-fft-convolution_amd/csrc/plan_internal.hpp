@@ -1,8 +1,9 @@
 // plan_internal.hpp -- what the host translation units of libfftconv.so share (not installed): the plan object behind
 // include/fftconv.h, its device / pinned buffers, and the internal entry points each unit offers the others.
-//   fftconv_api.cpp    plan core: creation, image transform, the per-kernel loop (run_group), options, two-step pair
+//   fftconv_api.cpp    plan core: creation (plan_device_setup), image transform, the per-kernel loop (run_group: plan_delivery,
+//                      launch_spectral_rows_batch, launch_output_cols, deliver_batch), options (kLongOptions), two-step pair
 //   plan_cache.cpp     plan cache of the one-shot entries + fftconv_convolution_fft[_ex] (the MEX body)
-//   host_ring.cpp      host-output streaming (copy threads, pinned ring)
+//   host_ring.cpp      host-output streaming (copy threads, pinned ring, the two staging buffers of a streamed group)
 //   blockwise.cpp      block-wise plans (overlap-save / overlap-add) and their planner
 //   placement.cpp      opt-in placement tuning of the intermediate
 //   fftconv_multi.cpp  several GPUs from one process (public API + api_internal.hpp only)
@@ -52,6 +53,28 @@ inline PlanTuning tuning_from(const fftconv_plan_options* o) {
     return t;
 }
 
+// fn() is a cleanup on a failing path (a wait, a destroy): the thread's last-error text -- the failure's -- survives it
+template <class Fn>
+auto keep_error(Fn&& fn) {
+    const std::string keep = api_last_error();
+    auto r = fn();
+    api_set_last_error(keep);
+    return r;
+}
+
+// copy between the plan's device buffers and memory at `location` (FFTCONV_AUTO names kernels only: towards the device)
+inline hipMemcpyKind copy_kind(int location, bool to_device) {
+    if (location == FFTCONV_HOST) return to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+    return to_device && location == FFTCONV_AUTO ? hipMemcpyDefault : hipMemcpyDeviceToDevice;
+}
+
+// end of the run of consecutive kernels that have the size of kernel k0
+inline int same_size_run_end(const int* kh, const int* kw, int k0, int n) {
+    int k1 = k0 + 1;
+    while (k1 < n && kh[k1] == kh[k0] && kw[k1] == kw[k0]) k1++;
+    return k1;
+}
+
 // plan_cache.cpp: destroys every idle plan of the one-shot entries' cache (device scratch, pinned staging, copy threads);
 // true if there was one.  Called by DevBuf::ensure when the device is out of memory.
 bool cache_release_idle();
@@ -97,6 +120,15 @@ struct DevBuf {
     }
     size_t bytes() const { return cap * sizeof(T); }
 };
+
+// sizes buf for a host table, copies the table and stores the device pointer where the kernels' arguments read it
+template <class T>
+int upload(DevBuf<T>& buf, const std::vector<T>& v, const T** slot = nullptr) {
+    if (int rc = buf.ensure(v.size())) return rc;
+    HIP_TRY(hipMemcpy(buf.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    if (slot) *slot = buf.p;
+    return 0;
+}
 
 // Pinned host staging of the small-call path (host arrays in / out of a few hundred KB: the sizes the reference's demo
 // calls with).  A copy between pageable memory and the device is a blocking runtime call of 10-25 us whatever its size,
@@ -158,7 +190,7 @@ struct PinBuf {
 
 struct TiledState;
 
-// Where the block plan of an overlap-save block-wise plan stores its maps (set around each run by tiled_convolve): rows
+// Where the block plan of an overlap-save block-wise plan stores its maps (Sink::window, built per block by tiled_convolve_save): rows
 // [h_lo, h_hi) of columns [w_first, w_first + ncols) of the block's circular result, row h of column w of map j at
 // base + j * map_stride + w * pitch + h -- the block's rectangle of the full maps (base is offset accordingly).
 struct OutWindow {
@@ -167,19 +199,28 @@ struct OutWindow {
     int pitch, h_lo, h_hi, w_first, ncols;
 };
 
+// n packed kernels of one size at dk whose column spectra are (or are to be) in A, and the stream that orders A's contents
+struct KernelSet {
+    const float* dk = nullptr;
+    int n = 0, kh = 0, kw = 0;
+    hipStream_t stream = nullptr;
+    bool operator==(const KernelSet& o) const { return dk == o.dk && n == o.n && kh == o.kh && kw == o.kw && stream == o.stream; }
+};
+
 using namespace fc;   // (host units only: this header is not installed)
 
 struct fftconv_plan {
     TiledState* tiled = nullptr;   // block-wise plan: sizes beyond one LDS-resident pass, or large sizes that run faster in blocks (see TiledState)
-    const OutWindow* win = nullptr;   // block plan of an overlap-save plan: the output kernel writes this window, whatever the sink says
     Geometry g;
     Tables t;
     DeviceTables d;
     int gpu_id = 0;
     hipStream_t stream = nullptr;
     bool have_image = false;
-    DevBuf<c32> tw_m, tw_w;
-    DevBuf<PairEntry> pairs;
+    // device copies of the Tables (fftconv_api.cpp: plan_device_setup; the natural-order pair: on first use)
+    DevBuf<c32> tw_m, tw_w, fr_tw1, fr_tw2, fc_tw1, fc_tw2;
+    DevBuf<PairEntry> pairs, fc_pairs;
+    DevBuf<int> fr_map, fc_rowoff, fc_pair_row_of, nat_row_of, nat_col_of;
     DevBuf<c32> S;     // image spectrum (own buffer)
     c32* Sx = nullptr; // caller-owned spectrum buffer, if any
     c32* spec() const { return Sx ? Sx : S.p; }   // S is allocated by the first use that needs it (ensure_spectrum)
@@ -200,20 +241,14 @@ struct fftconv_plan {
     PinBuf pin_img, pin_k, pin_out;   // pinned host staging of small host arrays (PinBuf above)
     hipEvent_t pin_out_done[2] = {nullptr, nullptr};   // copy into each half of pin_out complete
     long opt_host_pinned = 1;         // 0: small host arrays take the plain copies (A/B, tests)
-    DevBuf<c32> fr_tw1, fr_tw2;
-    DevBuf<int> fr_map;
-    DevBuf<c32> fc_tw1, fc_tw2;
-    DevBuf<PairEntry> fc_pairs;
-    DevBuf<int> fc_rowoff, fc_pair_row_of;
     DevBuf<int> queue;                    // counters of the dynamic tile queue (option "dynamic_tiles"; allocated when it is first set)
     long opt_dynamic_tiles = 0;           // 1: the persistent output kernel takes its tiles from a queue (fast_cols.hpp: TileQueue); 2: the forward column kernels too
-    DevBuf<int> nat_row_of, nat_col_of;   // natural-order spectrum exchange (uploaded on first use)
-    DevBuf<c32> NS;                       // its device staging for host callers
+    DevBuf<c32> NS;                       // device staging of the natural-order spectrum exchange for host callers
     int num_cus = 256;
     long opt_batch_maps = 0;
     long opt_kernel_chunk_mb = 0;
-    int tuned_candidates = 0, tuned_best = 0;   // of the last placement tuning (fftconv_plan_get_option)
-    long opt_tune_placement = -1;  // > 1: that many candidate allocations of the intermediate are tried (tune_intermediate_placement); 0 / 1: never;
+    long tuned_candidates = 0, tuned_best = 0;   // of the last placement tuning (fftconv_plan_get_option)
+    long opt_tune_placement = -1;  // > 1: that many candidate allocations of the intermediate are tried (placement.cpp); 0 / 1: never;
                                    // -1 (default): automatic -- placement_auto_candidates (placement.cpp)
     long opt_host_stream = 1;      // copy-out of host maps: 0 blocking, 1 direct by host threads, 2 pinned ring
     long opt_host_min_kb = FC_HOST_MIN_KB;   // maps smaller than this leave by blocking copies whatever host_stream says
@@ -226,12 +261,13 @@ struct fftconv_plan {
     bool profile = false;
     unsigned profile_mask = ~0u;   // which kinds (bit = PK_* index) are timed while `profile` is on
     bool prof_open = false;        // the last prof_begin recorded a start event
-    // kernel column spectra of the first chunk already in A (fftconv_plan_prepare_kernels_packed)
-    struct { const float* dk = nullptr; int n = 0, kh = 0, kw = 0; hipStream_t stream = nullptr; } prepared;   // (stream: the one A was produced on)
+    // kernel column spectra of the first chunk already in A (fftconv_plan_prepare_kernels_packed); dk == nullptr: none
+    KernelSet prepared;
     // fftconv_plan_prepare_kernels_packed DEFERRED: the kernels' column pass is launched by whichever comes first, the
     // next set_image on the same stream (then in ONE launch with the image's column pass: launch_fast_cols_fwd_pair) or
     // the next convolve / any call that must see it done (flush_pending_prepare)
-    struct { bool on = false; const float* dk = nullptr; int n = 0, na = 0, kh = 0, kw = 0; hipStream_t stream = nullptr; } deferred;
+    struct Deferred : KernelSet { bool on = false; int na = 0; } deferred;   // (na: kernels of the first chunk)
+    void forget_prepared() { prepared.dk = nullptr; deferred.on = false; }    // A's contents, or what they depend on, are about to change
     std::vector<EventPair> pending;
     std::vector<EventPair> pool;
     double prof_ms[PK_COUNT] = {0, 0, 0, 0, 0};
@@ -310,6 +346,7 @@ struct Sink {
     float* packed = nullptr;        // device base, maps consecutive
     float* const* ptrs = nullptr;   // or one pointer per map
     int location = FFTCONV_DEVICE;  // of ptrs
+    const OutWindow* window = nullptr;   // or (block plan of an overlap-save plan) the output kernel stores this window of the full maps
 };
 
 struct BatchSizes {
@@ -323,6 +360,8 @@ int use_device(const fftconv_plan* p);
 BatchSizes batch_sizes(const fftconv_plan* p, int n, int kw);
 int check_kernel_size(const fftconv_plan* p, int kh, int kw);
 int check_thread_size(const double* thread_size, int n_thread_size);
+// the plan's "output_region" of nmaps full-window maps at src, compacted into dst: 4 pads to the pow2 window, the others crop
+int launch_region(const fftconv_plan* p, const float* src, float* dst, int nmaps, hipStream_t s);
 // Core of the per-kernel loop for n kernels of one size, packed on the device at dk ([n][F][kw][kh]); on failure nothing of the
 // host-output ring is still writing into the caller's buffers when the error is returned
 int run_group(fftconv_plan* p, int n, const float* dk, int kh, int kw, const Sink& sink);
@@ -331,14 +370,21 @@ int plan_create_internal(fftconv_plan** plan, int data_h, int data_w, int featur
                          void* hip_stream, const fftconv_plan_options* options, bool cyclic);
 
 // ---- host-output streaming (host_ring.cpp) ----
-// pinned ring + copy stream + host copy threads of the host-output path, sized for this plan's maps
-int ring_ensure(fftconv_plan* p);
-// queue the copy-out of the maps [first, first + count) that sit in staging buffer `buf`
-int ring_drain(fftconv_plan* p, const Sink& sink, int first, int count, int buf, const float* staging);
+// A streamed group (run_group, host maps of at least host_min_kb) has two staging buffers on the device: batch b is computed into
+// buffer b & 1 while the copy-out of batch b - 1 runs.
+// start of a group: the plan's ring (pinned ring + copy stream + host copy threads, sized for its maps), created on first use
+int ring_begin(fftconv_plan* p);
+// which staging buffer the next batch is computed into; the plan's stream (or the host) waits until its previous contents have left
+int ring_claim_staging(fftconv_plan* p, int* buf);
+// the maps [first, first + count) have been launched into `staging` (buffer buf): queues the copy-out of the batch before it
+int ring_batch_launched(fftconv_plan* p, const Sink& sink, int first, int count, int buf, const float* staging);
+// end of a group: the last batch's copy-out, and every map in the caller's memory
+int ring_finish(fftconv_plan* p, const Sink& sink);
 
 // ---- placement tuning (placement.cpp) ----
-int tune_intermediate_placement(fftconv_plan* p, int k, int n, int nbY, float* out, size_t out_stride_per_map);
-int placement_auto_candidates(const fftconv_plan* p, size_t launch_map_bytes);
+// before the first launch of a group of n maps into a (re)allocated intermediate: times candidate allocations of it where the plan's
+// tune_placement option (or its automatic default) says so.  direct: the output kernel writes the caller's packed maps, from `out` on
+int tune_intermediate_placement(fftconv_plan* p, const Sink& sink, int n, int nbY, float* out, bool direct);
 
 // ---- block-wise plans (blockwise.cpp) ----
 bool blocks_preferred(const Geometry& g, const fftconv_plan_options* options);

@@ -281,7 +281,7 @@ def auto_walk(F, num_cus=256, slots_per_cu=4):
 
 def _logged(fn):
     """(fn(), what it wrote to the process's stderr): the plan's "verbose" lines, one per launch with its maps per launch,
-    kernels per column-spectrum chunk and maps per workgroup of the row kernel (fftconv_api.cpp: run_group_impl)"""
+    kernels per column-spectrum chunk and maps per workgroup of the row kernel (fftconv_api.cpp: run_group)"""
     import tempfile
     with tempfile.TemporaryFile() as tmp:
         saved = os.dup(2)
