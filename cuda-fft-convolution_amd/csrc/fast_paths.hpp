@@ -5,6 +5,7 @@
 // configs), chosen so that every stage keeps most lanes busy and the LDS budget allows
 // 3 waves per SIMD.  The planner prefers these lengths (planner.hpp: choose_length).
 #pragma once
+#include <type_traits>
 #include <vector>
 
 #include "fast_cols.hpp"
@@ -45,7 +46,9 @@ constexpr double FC_FACTOR_1088 = 0.60, FC_FACTOR_4160 = 0.60;
 //     of 16 points against 24 / 32.  No rule came out of it -- 5120 as 16.16.20 is 6 % SLOWER than 8.32.20, 4608 as 16.16.18 14 % slower
 //     than 12.16.24 -- and everything else it tried was within noise (+-3 %) or slower (up to +90 %); the list is what survived.
 //   * Radix orders at 4224 (round 2): 8.24.22 25.0 us per map, 12.16.22 25.6, 11.16.24 27.3, 16.12.22 28.0: small R1, fat stage 3.
-// Three groups, one translation unit each per kernel family (kernels_rows*_g?.hip): build time only.
+// Three groups, one translation unit each per kernel family (kernels_rows*_g?.hip, tests/emu/emu_rows_g?.cpp).  A fourth group
+// takes three edits: its table macro (and its branch in FC_ROW_CONFIGS_OF_GROUP), FC_ROW_GROUPS, and a _g3 file per family with
+// its Makefile entry -- the fan-out over the groups (first_group below) follows FC_ROW_GROUPS.  The columns likewise.
 #define FC_FAST_ROW_CONFIGS_G0(X)   \
     X(8448, 16, 24, 22, 768, 2, 3)  \
     X(8448, 16, 24, 22, 768, 2, 6)  \
@@ -174,6 +177,18 @@ inline double fast_rows_factor(int L, int max_kw) {
     return 0.45;
 }
 
+// Tries f(std::integral_constant<int, G>{}) for the groups G = 0 .. N-1 in order and stops at the first result that tests true
+// (a match: true, or an engaged optional); no match: the last group's (false / empty) result.
+template <int N, int G = 0, class F>
+inline auto first_group(F&& f) {
+    if constexpr (G + 1 < N) {
+        if (auto r = f(std::integral_constant<int, G>{})) return r;
+        return first_group<N, G + 1>(f);
+    } else {
+        return f(std::integral_constant<int, G>{});
+    }
+}
+
 // Calls run.template go<Cfg, NZ2>() for the first listed configuration of length L (in group G: the translation units
 // of a kernel family instantiate one group each) whose NZ2 covers `nz2_needed` (configurations are listed with
 // ascending NZ2).  false if there is none.
@@ -188,29 +203,17 @@ inline bool fast_rows_dispatch_group(int L, int nz2_needed, Runner&& run) {
 #undef FC_X
     return false;
 }
+// Forward image-row kernel (fast_rows_fwd.hpp): one instantiation per length -- the first listed configuration of that
+// length (nz2_needed = 0), the NZ2 dropped: run.template go<Cfg>().
 template <class Runner>
-inline bool fast_rows_dispatch(int L, int nz2_needed, Runner&& run) {
-    return fast_rows_dispatch_group<0>(L, nz2_needed, run) || fast_rows_dispatch_group<1>(L, nz2_needed, run) ||
-           fast_rows_dispatch_group<2>(L, nz2_needed, run);
-}
-
-// Forward image-row kernel (fast_rows_fwd.hpp): one instantiation per length (the first listed
-// configuration of that length; NZ2 does not matter).  run.template go<Cfg>().
+struct DropNZ2 {
+    Runner& run;
+    template <class Cfg, int>
+    void go() { run.template go<Cfg>(); }
+};
 template <int G, class Runner>
 inline bool fast_rows_fwd_dispatch_group(int L, Runner&& run) {
-    bool done = false;
-#define FC_X(LL, A, B, C, NTT, RP, NZ)                          \
-    if (!done && L == LL) {                                     \
-        run.template go<RowCfg<LL, A, B, C, NTT, RP>>();        \
-        done = true;                                            \
-    }
-    FC_ROW_CONFIGS_OF_GROUP(G, FC_X);
-#undef FC_X
-    return done;
-}
-template <class Runner>
-inline bool fast_rows_fwd_dispatch(int L, Runner&& run) {
-    return fast_rows_fwd_dispatch_group<0>(L, run) || fast_rows_fwd_dispatch_group<1>(L, run) || fast_rows_fwd_dispatch_group<2>(L, run);
+    return fast_rows_dispatch_group<G>(L, 0, DropNZ2<std::remove_reference_t<Runner>>{run});
 }
 
 // Host tables of a fast row configuration.
@@ -354,34 +357,7 @@ inline double fast_cols_ps(int M) {
     }
 }
 
-// Forward column kernel (fast_cols_fwd.hpp): same configurations; NZ2 = 3 (pruned, short kernels)
-// or R2 (any input length).  run.template go<Cfg, NZ2>().
-template <int G, class Runner>
-inline bool fast_cols_fwd_dispatch_group(int M, int T, bool pruned, Runner&& run) {
-#define FC_X(MM, A, B, C, TT, NTT)                                       \
-    if (M == MM && T == TT) {                                            \
-        if constexpr (B > 3) {                                           \
-            if (pruned) { run.template go<ColCfg<MM, A, B, C, TT, NTT>, 3>(); return true; }  \
-        }                                                                \
-        run.template go<ColCfg<MM, A, B, C, TT, NTT>, B>();              \
-        return true;                                                     \
-    }
-    FC_COL_CONFIGS_OF_GROUP(G, FC_X);
-#undef FC_X
-    return false;
-}
-template <class Runner>
-inline bool fast_cols_fwd_dispatch(int M, int T, bool pruned, Runner&& run) {
-    return fast_cols_fwd_dispatch_group<0>(M, T, pruned, run) || fast_cols_fwd_dispatch_group<1>(M, T, pruned, run);
-}
-
-// may the pruned variant take columns of h_in samples?  (one non-zero input per stage-1 butterfly,
-// at most 3 non-zero inputs per stage-2 butterfly)
-inline bool fast_cols_fwd_pruned_ok(const FastColsInfo& fi, int h_in) {
-    const int nz = (h_in + 1) / 2, m1 = fi.M / fi.R1;
-    return fi.R2 > 3 && nz <= m1 && nz <= 3 * fi.R3;
-}
-
+// Calls run.template go<Cfg>() for the configuration (M, T) if group G lists it; false if it does not.
 template <int G, class Runner>
 inline bool fast_cols_dispatch_group(int M, int T, Runner&& run) {
 #define FC_X(MM, A, B, C, TT, NTT)                          \
@@ -393,9 +369,30 @@ inline bool fast_cols_dispatch_group(int M, int T, Runner&& run) {
 #undef FC_X
     return false;
 }
+// Forward column kernel (fast_cols_fwd.hpp): same configurations, with the pruned choice added: run.template go<Cfg, NZ2>()
+// with NZ2 = 3 (pruned, short kernels; where R2 > 3) or R2 (any input length).
 template <class Runner>
-inline bool fast_cols_dispatch(int M, int T, Runner&& run) {
-    return fast_cols_dispatch_group<0>(M, T, run) || fast_cols_dispatch_group<1>(M, T, run);
+struct WithPrunedChoice {
+    Runner& run;
+    bool pruned;
+    template <class Cfg>
+    void go() {
+        if constexpr (Cfg::R2 > 3) {
+            if (pruned) { run.template go<Cfg, 3>(); return; }
+        }
+        run.template go<Cfg, Cfg::R2>();
+    }
+};
+template <int G, class Runner>
+inline bool fast_cols_fwd_dispatch_group(int M, int T, bool pruned, Runner&& run) {
+    return fast_cols_dispatch_group<G>(M, T, WithPrunedChoice<std::remove_reference_t<Runner>>{run, pruned});
+}
+
+// may the pruned variant take columns of h_in samples?  (one non-zero input per stage-1 butterfly,
+// at most 3 non-zero inputs per stage-2 butterfly)
+inline bool fast_cols_fwd_pruned_ok(const FastColsInfo& fi, int h_in) {
+    const int nz = (h_in + 1) / 2, m1 = fi.M / fi.R1;
+    return fi.R2 > 3 && nz <= m1 && nz <= 3 * fi.R3;
 }
 
 // Sliced tail round of the output kernel (fast_cols.hpp, SLICED): for the small transforms (M <= 1056: the launches of
@@ -421,6 +418,75 @@ inline bool fast_cols_slice_plan(int M, int T, int want, FastColsArgs& a, int& g
     a.ntiles = full_rounds * want;
     grid = want;
     return true;
+}
+
+// ---- Launch decisions: which instantiation a launch runs, with which arguments, on what grid.  Plain host code: the launchers
+// ---- (kernels_*.inc) and the CPU tier's runners (tests/emu/emu_runners.hpp) both call these, so neither can drift from the other.
+
+// Row kernel: f(std::bool_constant<LINEAR>{}), LINEAR as fast_rows_multi_linear says.  (m1 a whole number of HALF layout tiles:
+// LINEAR whatever the intermediate's layout -- the other variant is not built, so f is not instantiated for it)
+template <class Cfg, class F>
+inline void fast_rows_visit_linear(const FastRowsArgs& a, F&& f) {
+    if constexpr ((2 * Cfg::m1) % FC_Y_TILE_W == 0) f(std::true_type{});
+    else if (fast_rows_multi_linear(a, Cfg::L, Cfg::m1)) f(std::true_type{});
+    else f(std::false_type{});
+}
+// Row kernels: `groups` workgroups of RPW rows by `walks` of per_wg kernels (the F = 1 grid; the forward rows use the groups alone);
+// `flat`: the 1-D grid of the F > 1 walk, groups rounded up to whole rounds of the 8 XCDs
+struct FastRowsGrid { int groups, walks, flat; };
+inline FastRowsGrid fast_rows_grid(int rows, int rpw, int kernels, int per_wg) {
+    const int groups = (rows + rpw - 1) / rpw, walks = (kernels + per_wg - 1) / per_wg;
+    return {groups, walks, 8 * ((groups + 7) / 8) * walks};
+}
+
+// Persistent column kernels: as many workgroups as fit at once (LDS-limited), one or two per CU ...
+inline int persistent_want(size_t lds_bytes, int nt, int num_cus) {
+    const int by_lds = (int)(FC_LDS_BUDGET / lds_bytes), by_threads = 768 / nt;
+    const int per_cu = by_lds < by_threads ? by_lds : by_threads;
+    return num_cus * (per_cu < 1 ? 1 : per_cu);
+}
+// ... and no more than there are tiles
+inline int persistent_grid(size_t lds_bytes, int nt, int num_cus, int ntiles) {
+    const int want = persistent_want(lds_bytes, nt, num_cus);
+    return ntiles < want ? ntiles : want;
+}
+// image-and-kernels pair launch with the dynamic tile queue: a counter each, or none
+inline bool fast_cols_fwd_pair_queues_ok(const FastColsFwdArgs& a, const FastColsFwdArgs& b) {
+    return (!a.queue && !b.queue) || (a.queue && b.queue && a.queue != b.queue);
+}
+
+// Output kernel: the instantiation fast_cols_body<Cfg, TILED, SLICED, DYN> of a launch, its arguments and its grid on `want`
+// persistent workgroups.  Small transforms on the tiled intermediate deal a partial last round of tiles in column slices
+// (fast_cols_slice_plan), statically: that wins over the dynamic tile queue (fast_cols.hpp; chunks of one tile per workgroup
+// of an XCD), which the row-major intermediate ignores.
+enum class FastColsVariant { ROW_MAJOR, TILED, TILED_SLICED, TILED_DYN };
+struct FastColsShape {
+    FastColsVariant variant;
+    FastColsArgs a;
+    int grid;
+};
+inline FastColsShape fast_cols_launch_shape(int M, int T, const FastColsArgs& a, int want) {
+    FastColsShape r{FastColsVariant::TILED_SLICED, a, 0};
+    r.a.queue = nullptr;
+    if (fast_cols_slice_plan(M, T, want, r.a, r.grid)) return r;
+    r.a = a;
+    r.grid = a.ntiles < want ? a.ntiles : want;
+    r.variant = !a.y_tiled ? FastColsVariant::ROW_MAJOR : a.queue ? FastColsVariant::TILED_DYN : FastColsVariant::TILED;
+    if (r.variant == FastColsVariant::TILED_DYN) {
+        r.a.queue_shift = 0;
+        while ((16 << r.a.queue_shift) <= r.grid) r.a.queue_shift++;
+    }
+    return r;
+}
+// f(bool_constant<TILED>, bool_constant<SLICED>, bool_constant<DYN>) of a variant (SLICED exists for the small transforms only)
+template <class Cfg, class F>
+inline void fast_cols_visit_variant(FastColsVariant v, F&& f) {
+    using yes = std::true_type;
+    using no = std::false_type;
+    if (v == FastColsVariant::TILED) f(yes{}, no{}, no{});
+    else if (v == FastColsVariant::TILED_SLICED) { if constexpr (Cfg::M <= FC_SLICE_MAX_M) f(yes{}, yes{}, no{}); }
+    else if (v == FastColsVariant::TILED_DYN) f(yes{}, no{}, yes{});
+    else f(no{}, no{}, no{});
 }
 
 struct FastColsTables {

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <optional>
+
 #include "fast_paths.hpp"
 #include "kernels_body.hpp"
 
@@ -40,5 +42,17 @@ hipError_t launch_fast_cols_fwd(int M, int T, bool pruned, const FastColsFwdArgs
 hipError_t launch_fast_cols_fwd_pair(int M, int T, const FastColsFwdArgs& image, const FastColsFwdArgs& kernels, bool kernels_pruned,
                                      int num_cus, hipStream_t s);
 hipError_t launch_cols_c2r(const ColsC2RArgs& a, int tiles, int kernels, int threads, size_t lds_bytes, hipStream_t s);
+
+
+// The specialised launchers' per-group entry points: the translation unit kernels_*_g<G>.hip defines the specialisation for its
+// group G of configurations (fast_paths.hpp); empty: no configuration of that group matches.  kernels.hip tries the groups in order.
+using GroupResult = std::optional<hipError_t>;
+template <int G> GroupResult launch_fast_rows_fwd_group(int L, const FastRowsFwdArgs& a, int rows, hipStream_t s);
+template <int G> GroupResult launch_fast_rows_multi_group(int L, int nz2, const FastRowsArgs& a, int rows, int kernels, int kernels_per_wg, hipStream_t s);
+template <int G> GroupResult fast_rows_multi_wgs_per_cu_group(int L, int nz2, const FastRowsArgs& a, int* wgs_per_cu);
+template <int G> GroupResult launch_fast_cols_group(int M, int T, const FastColsArgs& a, int num_cus, hipStream_t s);
+template <int G> GroupResult launch_fast_cols_fwd_group(int M, int T, bool pruned, const FastColsFwdArgs& a, int num_cus, hipStream_t s);
+template <int G> GroupResult launch_fast_cols_fwd_pair_group(int M, int T, const FastColsFwdArgs& image, const FastColsFwdArgs& kernels,
+                                                             bool kernels_pruned, int num_cus, hipStream_t s);
 
 }  // namespace fc

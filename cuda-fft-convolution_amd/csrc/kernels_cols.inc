@@ -1,5 +1,6 @@
 // kernels_cols.inc -- the output-column kernel (fast_cols.hpp).
-// Included by kernels_cols_g<G>.hip with FC_TU_GROUP = G (one group of column configurations per translation unit).
+// Included by kernels_cols_g<G>.hip with FC_TU_GROUP = G: defines group G's entry point (kernels.hpp) over that group of column
+// configurations.
 #include "kernels_common.hpp"
 
 namespace fc {
@@ -18,59 +19,21 @@ struct FastColsLauncher {
     hipError_t err = hipSuccess;
     template <class Cfg>
     void go() {
-        if (a.y_tiled) launch<Cfg, true>();
-        else launch<Cfg, false>();
-    }
-    template <class Cfg, bool TILED>
-    void launch() {
-        static LdsAttrMask attr_mask{0};
         const size_t lds = (size_t)Cfg::LDS_ELEMS * sizeof(c32);
-        err = ensure_lds_attr(k_fast_cols<Cfg, TILED>, attr_mask);
-        if (err != hipSuccess) return;
-        // persistent: as many workgroups as fit at once (LDS-limited), one or two per CU
-        const int per_cu = (int)((size_t)(160 * 1024) / lds) < 768 / Cfg::NT ? (int)((size_t)(160 * 1024) / lds) : 768 / Cfg::NT;
-        const int want = max_wg * (per_cu < 1 ? 1 : per_cu);
-        if constexpr (TILED && Cfg::M <= FC_SLICE_MAX_M) {    // small transforms: a partial last round of tiles is dealt in column slices
-            FastColsArgs b = a;
-            b.queue = nullptr;                 // (the sliced tail round is dealt statically)
-            int sgrid = 0;
-            if (fast_cols_slice_plan(Cfg::M, Cfg::T, want, b, sgrid)) {
-                static LdsAttrMask attr_mask_s{0};
-                err = ensure_lds_attr(k_fast_cols<Cfg, TILED, true>, attr_mask_s);
-                if (err != hipSuccess) return;
-                hipLaunchKernelGGL((k_fast_cols<Cfg, TILED, true>), dim3(sgrid), dim3(Cfg::NT), lds, s, b);
-                err = hipGetLastError();
-                return;
-            }
-        }
-        const int grid = a.ntiles < want ? a.ntiles : want;
-        if constexpr (TILED) {
-            if (a.queue) {   // dynamic tile queue (fast_cols.hpp; the counters are zero between launches): chunks of one tile per workgroup of an XCD
-                static LdsAttrMask attr_mask_d{0};
-                err = ensure_lds_attr(k_fast_cols<Cfg, TILED, false, true>, attr_mask_d);
-                if (err != hipSuccess) return;
-                FastColsArgs b = a;
-                b.queue_shift = 0;
-                while ((16 << b.queue_shift) <= grid) b.queue_shift++;
-                hipLaunchKernelGGL((k_fast_cols<Cfg, TILED, false, true>), dim3(grid), dim3(Cfg::NT), lds, s, b);
-                err = hipGetLastError();
-                return;
-            }
-        }
-        hipLaunchKernelGGL((k_fast_cols<Cfg, TILED>), dim3(grid), dim3(Cfg::NT), lds, s, a);
-        err = hipGetLastError();
+        const FastColsShape sh = fast_cols_launch_shape(Cfg::M, Cfg::T, a, persistent_want(lds, Cfg::NT, max_wg));
+        fast_cols_visit_variant<Cfg>(sh.variant, [&](auto tiled, auto sliced, auto dyn) {
+            err = launch_lds<k_fast_cols<Cfg, tiled.value, sliced.value, dyn.value>>(dim3(sh.grid), Cfg::NT, lds, s, sh.a);
+        });
     }
 };
 
 }  // namespace
 
-#define FC_CAT2(a, b) a##b
-#define FC_CAT(a, b) FC_CAT2(a, b)
-
-hipError_t FC_CAT(launch_fast_cols_g, FC_TU_GROUP)(int M, int T, const FastColsArgs& a, int num_cus, hipStream_t s, bool* matched) {
+template <>
+GroupResult launch_fast_cols_group<FC_TU_GROUP>(int M, int T, const FastColsArgs& a, int num_cus, hipStream_t s) {
     FastColsLauncher l{a, num_cus, s};
-    *matched = fast_cols_dispatch_group<FC_TU_GROUP>(M, T, l);
-    return *matched ? l.err : hipErrorInvalidValue;
+    if (!fast_cols_dispatch_group<FC_TU_GROUP>(M, T, l)) return {};
+    return l.err;
 }
 
 }  // namespace fc

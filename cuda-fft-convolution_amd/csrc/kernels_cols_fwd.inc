@@ -1,5 +1,6 @@
 // kernels_cols_fwd.inc -- the forward-column kernel (fast_cols_fwd.hpp).
-// Included by kernels_cols_fwd_g<G>.hip with FC_TU_GROUP = G (one group of column configurations per translation unit).
+// Included by kernels_cols_fwd_g<G>.hip with FC_TU_GROUP = G: defines group G's entry points (kernels.hpp) over that group of column
+// configurations.
 #include "kernels_common.hpp"
 
 namespace fc {
@@ -33,17 +34,9 @@ struct FastColsFwdPairLauncher {
     hipError_t err = hipSuccess;
     template <class Cfg, int NZ2B>
     void go() {
-        static LdsAttrMask attr_mask{0};
         const size_t lds = (size_t)Cfg::LDS_ELEMS * sizeof(c32);
-        err = ensure_lds_attr(k_fast_cols_fwd_pair<Cfg, NZ2B>, attr_mask);
-        if (err != hipSuccess) return;
-        const int per_cu = (int)((size_t)(160 * 1024) / lds) < 768 / Cfg::NT ? (int)((size_t)(160 * 1024) / lds) : 768 / Cfg::NT;
-        const int want = num_cus * (per_cu < 1 ? 1 : per_cu);
-        const int total = a.ntiles + b.ntiles;
-        const int grid = total < want ? total : want;
-        if ((a.queue || b.queue) && (!a.queue || !b.queue || a.queue == b.queue)) { err = hipErrorInvalidValue; return; }   // dynamic tile queue: a counter each
-        hipLaunchKernelGGL((k_fast_cols_fwd_pair<Cfg, NZ2B>), dim3(grid), dim3(Cfg::NT), lds, s, a, b);
-        err = hipGetLastError();
+        if (!fast_cols_fwd_pair_queues_ok(a, b)) { err = hipErrorInvalidValue; return; }
+        err = launch_lds<k_fast_cols_fwd_pair<Cfg, NZ2B>>(dim3(persistent_grid(lds, Cfg::NT, num_cus, a.ntiles + b.ntiles)), Cfg::NT, lds, s, a, b);
     }
 };
 
@@ -54,34 +47,26 @@ struct FastColsFwdLauncher {
     hipError_t err = hipSuccess;
     template <class Cfg, int NZ2>
     void go() {
-        static LdsAttrMask attr_mask{0};
         const size_t lds = (size_t)Cfg::LDS_ELEMS * sizeof(c32);
-        err = ensure_lds_attr(k_fast_cols_fwd<Cfg, NZ2>, attr_mask);
-        if (err != hipSuccess) return;
-        const int per_cu = (int)((size_t)(160 * 1024) / lds) < 768 / Cfg::NT ? (int)((size_t)(160 * 1024) / lds) : 768 / Cfg::NT;
-        const int want = num_cus * (per_cu < 1 ? 1 : per_cu);
-        const int grid = a.ntiles < want ? a.ntiles : want;
-        hipLaunchKernelGGL((k_fast_cols_fwd<Cfg, NZ2>), dim3(grid), dim3(Cfg::NT), lds, s, a);
-        err = hipGetLastError();
+        err = launch_lds<k_fast_cols_fwd<Cfg, NZ2>>(dim3(persistent_grid(lds, Cfg::NT, num_cus, a.ntiles)), Cfg::NT, lds, s, a);
     }
 };
 
 }  // namespace
 
-#define FC_CAT2(a, b) a##b
-#define FC_CAT(a, b) FC_CAT2(a, b)
-
-hipError_t FC_CAT(launch_fast_cols_fwd_g, FC_TU_GROUP)(int M, int T, bool pruned, const FastColsFwdArgs& a, int num_cus, hipStream_t s, bool* matched) {
+template <>
+GroupResult launch_fast_cols_fwd_group<FC_TU_GROUP>(int M, int T, bool pruned, const FastColsFwdArgs& a, int num_cus, hipStream_t s) {
     FastColsFwdLauncher l{a, num_cus, s};
-    *matched = fast_cols_fwd_dispatch_group<FC_TU_GROUP>(M, T, pruned, l);
-    return *matched ? l.err : hipErrorInvalidValue;
+    if (!fast_cols_fwd_dispatch_group<FC_TU_GROUP>(M, T, pruned, l)) return {};
+    return l.err;
 }
 
-hipError_t FC_CAT(launch_fast_cols_fwd_pair_g, FC_TU_GROUP)(int M, int T, const FastColsFwdArgs& image, const FastColsFwdArgs& kernels, bool kernels_pruned,
-                                                           int num_cus, hipStream_t s, bool* matched) {
+template <>
+GroupResult launch_fast_cols_fwd_pair_group<FC_TU_GROUP>(int M, int T, const FastColsFwdArgs& image, const FastColsFwdArgs& kernels,
+                                                        bool kernels_pruned, int num_cus, hipStream_t s) {
     FastColsFwdPairLauncher l{image, kernels, num_cus, s};
-    *matched = fast_cols_fwd_dispatch_group<FC_TU_GROUP>(M, T, kernels_pruned, l);
-    return *matched ? l.err : hipErrorInvalidValue;
+    if (!fast_cols_fwd_dispatch_group<FC_TU_GROUP>(M, T, kernels_pruned, l)) return {};
+    return l.err;
 }
 
 }  // namespace fc

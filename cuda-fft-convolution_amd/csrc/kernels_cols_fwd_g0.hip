@@ -1,4 +1,4 @@
 // kernels_cols_fwd_g0.hip -- forward-column kernels, configurations of group 0 of fast_paths.hpp
-// (the kernel families are spread over translation units only to compile in parallel: make -j).
+// (one translation unit per kernel family and group: they compile in parallel, and each defines its group's entry points).
 #define FC_TU_GROUP 0
 #include "kernels_cols_fwd.inc"

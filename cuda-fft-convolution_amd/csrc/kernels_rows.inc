@@ -1,7 +1,8 @@
 // kernels_rows.inc -- the forward image-row kernel (fast_rows_fwd.hpp).  (Until round 4 also the one-map spectral-row kernel
 // of fast_rows.hpp: single-map launches now take the multi-map walk with one map per workgroup -- the one-map form kept part
 // of its per-thread state in scratch behind a vmcnt(0), and was one more kernel per configuration to build.)
-// Included by kernels_rows_g<G>.hip with FC_TU_GROUP = G (one group of row configurations per translation unit).
+// Included by kernels_rows_g<G>.hip with FC_TU_GROUP = G: defines group G's entry point (kernels.hpp) over that group of row
+// configurations.
 #include "kernels_common.hpp"
 
 namespace fc {
@@ -20,25 +21,17 @@ struct FastRowsFwdLauncher {
     hipError_t err = hipSuccess;
     template <class Cfg>
     void go() {
-        static LdsAttrMask attr_mask{0};
-        const size_t lds = (size_t)Cfg::LDS_ELEMS * sizeof(c32);
-        err = ensure_lds_attr(k_fast_rows_fwd<Cfg>, attr_mask);
-        if (err != hipSuccess) return;
-        const int groups = (rows + Cfg::RPW - 1) / Cfg::RPW;
-        hipLaunchKernelGGL((k_fast_rows_fwd<Cfg>), dim3(groups), dim3(Cfg::NT), lds, s, a, rows);
-        err = hipGetLastError();
+        err = launch_lds<k_fast_rows_fwd<Cfg>>(dim3(fast_rows_grid(rows, Cfg::RPW, 1, 1).groups), Cfg::NT, (size_t)Cfg::LDS_ELEMS * sizeof(c32), s, a, rows);
     }
 };
 
 }  // namespace
 
-#define FC_CAT2(a, b) a##b
-#define FC_CAT(a, b) FC_CAT2(a, b)
-
-hipError_t FC_CAT(launch_fast_rows_fwd_g, FC_TU_GROUP)(int L, const FastRowsFwdArgs& a, int rows, hipStream_t s, bool* matched) {
+template <>
+GroupResult launch_fast_rows_fwd_group<FC_TU_GROUP>(int L, const FastRowsFwdArgs& a, int rows, hipStream_t s) {
     FastRowsFwdLauncher l{a, rows, s};
-    *matched = fast_rows_fwd_dispatch_group<FC_TU_GROUP>(L, l);
-    return *matched ? l.err : hipErrorInvalidValue;
+    if (!fast_rows_fwd_dispatch_group<FC_TU_GROUP>(L, l)) return {};
+    return l.err;
 }
 
 }  // namespace fc

@@ -1,6 +1,6 @@
 // kernels_rows_multi.inc -- the multi-map spectral-row kernel (fast_rows_multi.hpp), the default.
 // Included by kernels_rows_multi_g<G>.hip with FC_TU_GROUP = G: each translation unit instantiates the row
-// configurations of one group of fast_paths.hpp (build time only; see kernels_common.hpp).
+// configurations of one group of fast_paths.hpp and defines that group's entry points (kernels.hpp).
 #include "kernels_common.hpp"
 
 namespace fc {
@@ -43,18 +43,12 @@ struct FastRowsMultiOccupancy {
     hipError_t err = hipSuccess;
     template <class Cfg, int NZ2>
     void go() {
-        // (m1 a whole number of HALF layout tiles: LINEAR whatever the intermediate's layout -- the other variant is not built)
-        if constexpr ((2 * Cfg::m1) % FC_Y_TILE_W == 0) query<Cfg, NZ2, true>();
-        else if (fast_rows_multi_linear(a, Cfg::L, Cfg::m1)) query<Cfg, NZ2, true>();
-        else query<Cfg, NZ2, false>();
-    }
-    template <class Cfg, int NZ2, bool LINEAR>
-    void query() {
-        static LdsAttrMask attr_mask{0};
-        err = ensure_lds_attr(k_fast_rows_multi<Cfg, NZ2, LINEAR>, attr_mask);
-        if (err != hipSuccess) return;
-        err = hipOccupancyMaxActiveBlocksPerMultiprocessor(&result, reinterpret_cast<const void*>(k_fast_rows_multi<Cfg, NZ2, LINEAR>), Cfg::NT,
-                                                           (size_t)Cfg::LDS_ELEMS * sizeof(c32));
+        fast_rows_visit_linear<Cfg>(a, [&](auto linear) {
+            constexpr auto kernel = k_fast_rows_multi<Cfg, NZ2, linear.value>;
+            err = ensure_lds_attr<kernel>();
+            if (err != hipSuccess) return;
+            err = hipOccupancyMaxActiveBlocksPerMultiprocessor(&result, reinterpret_cast<const void*>(kernel), Cfg::NT, (size_t)Cfg::LDS_ELEMS * sizeof(c32));
+        });
     }
 };
 
@@ -65,51 +59,30 @@ struct FastRowsMultiLauncher {
     hipError_t err = hipSuccess;
     template <class Cfg, int NZ2>
     void go() {
-        if constexpr ((2 * Cfg::m1) % FC_Y_TILE_W == 0) launch<Cfg, NZ2, true>();
-        else if (fast_rows_multi_linear(a, Cfg::L, Cfg::m1)) launch<Cfg, NZ2, true>();
-        else launch<Cfg, NZ2, false>();
-    }
-    template <class Cfg, int NZ2, bool LINEAR>
-    void launch() {
         const size_t lds = (size_t)Cfg::LDS_ELEMS * sizeof(c32);
-        const int groups = (rows + Cfg::RPW - 1) / Cfg::RPW;
-        const int walks = (kernels + per_wg - 1) / per_wg;
-        if (a.F > 1) {
-            static LdsAttrMask attr_mask_f{0};
-            err = ensure_lds_attr(k_fast_rows_multi_f<Cfg, NZ2, LINEAR>, attr_mask_f);
-            if (err != hipSuccess) return;
-            const dim3 grid(8 * ((groups + 7) / 8) * walks);
-            hipLaunchKernelGGL((k_fast_rows_multi_f<Cfg, NZ2, LINEAR>), grid, dim3(Cfg::NT), lds, s, a, rows, kernels, per_wg, groups, walks);
-        } else {
-            static LdsAttrMask attr_mask{0};
-            err = ensure_lds_attr(k_fast_rows_multi<Cfg, NZ2, LINEAR>, attr_mask);
-            if (err != hipSuccess) return;
-            const dim3 grid(groups, walks);
-            hipLaunchKernelGGL((k_fast_rows_multi<Cfg, NZ2, LINEAR>), grid, dim3(Cfg::NT), lds, s, a, rows, kernels, per_wg);
-        }
-        err = hipGetLastError();
+        const FastRowsGrid g = fast_rows_grid(rows, Cfg::RPW, kernels, per_wg);
+        fast_rows_visit_linear<Cfg>(a, [&](auto linear) {
+            if (a.F > 1) err = launch_lds<k_fast_rows_multi_f<Cfg, NZ2, linear.value>>(dim3(g.flat), Cfg::NT, lds, s, a, rows, kernels, per_wg, g.groups, g.walks);
+            else err = launch_lds<k_fast_rows_multi<Cfg, NZ2, linear.value>>(dim3(g.groups, g.walks), Cfg::NT, lds, s, a, rows, kernels, per_wg);
+        });
     }
 };
 
 }  // namespace
 
-#define FC_CAT2(a, b) a##b
-#define FC_CAT(a, b) FC_CAT2(a, b)
-
-// (*matched false: no configuration of this group has the length -- the caller tries the next group)
-hipError_t FC_CAT(fast_rows_multi_wgs_per_cu_g, FC_TU_GROUP)(int L, int nz2, const FastRowsArgs& a, int* wgs_per_cu, bool* matched) {
+template <>
+GroupResult fast_rows_multi_wgs_per_cu_group<FC_TU_GROUP>(int L, int nz2, const FastRowsArgs& a, int* wgs_per_cu) {
     FastRowsMultiOccupancy q{a};
-    *matched = fast_rows_dispatch_group<FC_TU_GROUP>(L, nz2, q);
-    if (!*matched) return hipErrorInvalidValue;
+    if (!fast_rows_dispatch_group<FC_TU_GROUP>(L, nz2, q)) return {};
     if (q.err == hipSuccess && wgs_per_cu) *wgs_per_cu = q.result;
     return q.err;
 }
 
-hipError_t FC_CAT(launch_fast_rows_multi_g, FC_TU_GROUP)(int L, int nz2, const FastRowsArgs& a, int rows, int kernels, int kernels_per_wg, hipStream_t s,
-                                                        bool* matched) {
+template <>
+GroupResult launch_fast_rows_multi_group<FC_TU_GROUP>(int L, int nz2, const FastRowsArgs& a, int rows, int kernels, int kernels_per_wg, hipStream_t s) {
     FastRowsMultiLauncher l{a, rows, kernels, kernels_per_wg, s};
-    *matched = fast_rows_dispatch_group<FC_TU_GROUP>(L, nz2, l);
-    return *matched ? l.err : hipErrorInvalidValue;
+    if (!fast_rows_dispatch_group<FC_TU_GROUP>(L, nz2, l)) return {};
+    return l.err;
 }
 
 }  // namespace fc

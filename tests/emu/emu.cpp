@@ -17,6 +17,14 @@ using namespace fc;
 using namespace emu;
 
 namespace {
+// the first group of configurations that has the length takes the run (as kernels.hip for the product's launchers)
+bool run_fast_rows(int L, int nz2, EmuFastRows& run) { return first_group<FC_ROW_GROUPS>([&](auto g) { return fast_rows_group<g.value>(L, nz2, run); }); }
+bool run_fast_rows_fwd(int L, EmuFastRowsFwd& run) { return first_group<FC_ROW_GROUPS>([&](auto g) { return fast_rows_fwd_group<g.value>(L, run); }); }
+bool run_fast_cols(int M, int T, EmuFastCols& run) { return first_group<FC_COL_GROUPS>([&](auto g) { return fast_cols_group<g.value>(M, T, run); }); }
+bool run_fast_cols_fwd(int M, int T, bool pruned, EmuFastColsFwd& run) {
+    return first_group<FC_COL_GROUPS>([&](auto g) { return fast_cols_fwd_group<g.value>(M, T, pruned, run); });
+}
+
 PlanTuning g_tune;   // path mode / rows group of the emulated plans (pipeline.hpp PlanTuning)
 // the output window of a block of an overlap-save block-wise plan (fftconv_api.cpp: OutWindow), applied to the output kernel
 struct { bool on = false; int h_lo = 0, h_hi = 0, w_first = 0, ncols = 0, pitch = 0; } g_win;
@@ -253,6 +261,19 @@ int emu_row_configs(int* L, int* nz2, int max) {
     FC_FAST_ROW_CONFIGS(FC_X)
 #undef FC_X
     return n;
+}
+
+// the output kernel's launch shape (fast_paths.hpp: fast_cols_launch_shape) for `ntiles` tiles of a tiled / row-major
+// intermediate on `want` persistent workgroups, with or without a tile queue: out[7] = variant (0 row-major, 1 tiled,
+// 2 tiled SLICED, 3 tiled DYN), grid, ntiles, tail_first, tail_tiles, slice_shift, queue_shift
+void emu_fast_cols_launch_shape(int M, int T, int tiled, int ntiles, int want, int with_queue, int* out) {
+    FastColsArgs a{};
+    a.y_tiled = tiled != 0;
+    a.ntiles = ntiles;
+    a.queue = with_queue ? g_queue : nullptr;
+    const FastColsShape sh = fast_cols_launch_shape(M, T, a, want);
+    const int r[7] = {(int)sh.variant, sh.grid, sh.a.ntiles, sh.a.tail_first, sh.a.tail_tiles, sh.a.slice_shift, sh.a.queue_shift};
+    std::copy(r, r + 7, out);
 }
 
 // the planner alone (no preference for lengths with specialised kernels)

@@ -163,6 +163,32 @@ def test_emulated_oversize_kernel_policy(emu):
     assert L[1] != 16 and rc == -3
 
 
+# (M, T, tiled, ntiles, want, with_queue) -> (variant, grid, ntiles, tail_first, tail_tiles, slice_shift, queue_shift); variant:
+# 0 row-major, 1 tiled, 2 tiled SLICED, 3 tiled DYN.  Recorded from fast_cols_slice_plan plus the launcher's own rules as they
+# stood before the launch shape became a function of its own.
+FAST_COLS_LAUNCH_SHAPES = [
+    ((144, 16, 0, 18, 8, 1), (0, 8, 18, 0, 0, 0, 0)),             # row-major intermediate: the queue is ignored
+    ((144, 16, 1, 18, 256, 0), (1, 18, 18, 0, 0, 0, 0)),          # fewer tiles than one round: whole tiles
+    ((144, 16, 1, 16, 8, 0), (1, 8, 16, 0, 0, 0, 0)),             # whole rounds only: nothing to slice
+    ((2112, 8, 1, 4224, 256, 1), (3, 256, 4224, 0, 0, 0, 5)),     # tile queue: chunks of 2^5 tiles on 256 workgroups ...
+    ((1152, 8, 1, 40, 256, 1), (3, 40, 40, 0, 0, 0, 2)),          # ... of 2^2 on 40
+    # by hand: 18 tiles on 8 workgroups = 2 full rounds (16 tiles) + 2 tiles, 8 / 2 = 4 slices of 4 columns each
+    ((144, 16, 1, 18, 8, 0), (2, 8, 16, 16, 2, 2, 0)),
+    ((576, 16, 1, 288, 256, 1), (2, 256, 256, 256, 32, 3, 0)),    # the sliced tail wins over the queue (dealt statically)
+    ((1152, 8, 1, 300, 256, 0), (1, 256, 300, 0, 0, 0, 0)),       # M > FC_SLICE_MAX_M: a partial last round stays whole
+    ((1056, 16, 1, 300, 256, 0), (2, 256, 256, 256, 44, 2, 0)),   # M = FC_SLICE_MAX_M: 44 tiles in 4 slices each
+]
+
+
+def test_output_kernel_launch_shape(emu):
+    """the decision both the launcher and the emulator's runner take from (fast_paths.hpp: fast_cols_launch_shape): which
+    instantiation of the output kernel runs, on what grid, with which tail / queue fields"""
+    for args, want in FAST_COLS_LAUNCH_SHAPES:
+        out = (ctypes.c_int * 7)()
+        emu.emu_fast_cols_launch_shape(*args, out)
+        assert tuple(out) == want, (args, tuple(out), want)
+
+
 # ---------------------------------------------------------------- the C-ABI library itself
 
 def declared_symbols():
