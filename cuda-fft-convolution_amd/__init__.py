@@ -57,11 +57,28 @@ class PlanOptions(ctypes.Structure):
     """fftconv_plan_options (include/fftconv.h): choices fixed at plan creation."""
     _fields_ = [("struct_size", ctypes.c_size_t), ("kernel_path", ctypes.c_int), ("rows_group", ctypes.c_int),
                 ("max_transform", ctypes.c_int), ("exact_window", ctypes.c_int), ("blockwise", ctypes.c_int),
-                ("verbose", ctypes.c_int)]
+                ("verbose", ctypes.c_int), ("map_format", ctypes.c_int)]
 
-    def __init__(self, kernel_path=0, rows_group=0, max_transform=0, exact_window=0, blockwise=0, verbose=0):
+    def __init__(self, kernel_path=0, rows_group=0, max_transform=0, exact_window=0, blockwise=0, verbose=0, map_format=0):
         super().__init__(ctypes.sizeof(PlanOptions), int(kernel_path), int(rows_group), int(max_transform), int(exact_window), int(blockwise),
-                         int(verbose))
+                         int(verbose), int(map_format))
+
+
+# Element format of the result maps (plan option / PlanOptions field "map_format") and the NumPy dtype a host map comes back in.
+# NumPy has no bfloat16: those maps are uint16 arrays of bfloat16 BIT PATTERNS (a float32 view: ``a.astype(np.uint32) << 16``
+# viewed as float32; torch: ``torch.from_numpy(a).view(torch.bfloat16)``).
+MAP_F32, MAP_F16, MAP_BF16 = 0, 1, 2
+MAP_DTYPES = {MAP_F32: np.dtype(np.float32), MAP_F16: np.dtype(np.float16), MAP_BF16: np.dtype(np.uint16)}
+
+
+def _options_map_dtype(options):
+    """dtype of the maps a one-shot call with these options returns"""
+    if options is None:
+        return MAP_DTYPES[MAP_F32]
+    fmt = options.get("map_format", 0) if isinstance(options, dict) else options.map_format
+    if int(fmt) not in MAP_DTYPES:
+        raise FFTConvError(-1, "map_format is 0 (fp32), 1 (fp16) or 2 (bfloat16)")
+    return MAP_DTYPES[int(fmt)]
 
 
 class CallTiming(ctypes.Structure):
@@ -274,7 +291,9 @@ def cudaConvolutionFFT(data, maxKernelH, maxKernelW, kernelCell, threadSize=None
     """One-shot convolution, host arrays in / host arrays out (list of FFT_H x FFT_W float32,
     Fortran order).  Mirrors the MEX entry of src/cudaConvolutionFFT.cu.  ``options``: a
     PlanOptions (or a dict of its fields) for fftconv_convolution_fft_ex; ``out``: optional list of
-    caller buffers (FFT_H x FFT_W float32, Fortran order) to fill instead of fresh arrays."""
+    caller buffers (FFT_H x FFT_W float32, Fortran order) to fill instead of fresh arrays.
+    With ``map_format`` 1 in the options the maps (and ``out``) are np.float16, with 2 np.uint16 arrays of
+    bfloat16 bit patterns (MAP_DTYPES)."""
     lib = load_library()
     if not isinstance(kernelCell, (list, tuple)):
         raise FFTConvError(-1, "Kernel must be a cell array")  # src/cudaConvolutionFFT.cu:64-65
@@ -283,12 +302,13 @@ def cudaConvolutionFFT(data, maxKernelH, maxKernelW, kernelCell, threadSize=None
     ks, kptr, kh, kw, kf = _kernel_tables(kernelCell)
     n = len(ks)
     fh, fw = fft_size16(H + int(maxKernelH) - 1), fft_size16(W + int(maxKernelW) - 1)
+    dt = _options_map_dtype(options)
     if out is None:
-        outs = [np.empty((fh, fw), dtype=np.float32, order="F") for _ in range(n)]
+        outs = [np.empty((fh, fw), dtype=dt, order="F") for _ in range(n)]
     else:
         outs = list(out)
-        if len(outs) != n or any(o.dtype != np.float32 or o.shape != (fh, fw) or not o.flags.f_contiguous for o in outs):
-            raise FFTConvError(-1, "out must hold one FFT_H x FFT_W float32 Fortran-order buffer per kernel")
+        if len(outs) != n or any(o.dtype != dt or o.shape != (fh, fw) or not o.flags.f_contiguous for o in outs):
+            raise FFTConvError(-1, "out must hold one FFT_H x FFT_W %s Fortran-order buffer per kernel" % dt.name)
     optr = (ctypes.c_void_p * n)(*[o.ctypes.data for o in outs])
     tptr, tn, _keep = _thread_size(threadSize)
     ofh, ofw = ctypes.c_int(0), ctypes.c_int(0)
@@ -376,7 +396,8 @@ class Plan:
     def convolve(self, kernelCell, out=None):
         """host kernels (list of kh x kw x F float32) -> list of host maps.  ``out``: optional list
         of caller buffers to fill (FFT_H x FFT_W float32, Fortran order; pageable, or pinned for a
-        direct DMA copy-out) instead of fresh arrays."""
+        direct DMA copy-out) instead of fresh arrays.  Plan option "map_format" 1: the maps (and ``out``)
+        are np.float16; 2: np.uint16 arrays of bfloat16 bit patterns (MAP_DTYPES)."""
         ks, kptr, kh, kw, kf = _kernel_tables(kernelCell)
         for k in ks:
             if k.shape[2] != self.info.feature_dim:  # src/cudaConvolutionFFT.cu:242
@@ -385,16 +406,17 @@ class Plan:
         n = len(ks)
         _check(self._lib.fftconv_plan_get_info(self._h, ctypes.byref(self.info)))   # out_h / out_w follow "output_region"
         oh, ow = self.info.out_h, self.info.out_w
+        dt = MAP_DTYPES[self.get_option("map_format")]
         if out is None:
-            outs = [np.empty((oh, ow), dtype=np.float32, order="F") for _ in range(n)]
+            outs = [np.empty((oh, ow), dtype=dt, order="F") for _ in range(n)]
         else:
             outs = list(out)
             if len(outs) != n:
                 raise FFTConvError(-1, "out must hold one buffer per kernel")
             for o in outs:
-                if (o.dtype != np.float32 or o.shape != (oh, ow)
+                if (o.dtype != dt or o.shape != (oh, ow)
                         or not o.flags.f_contiguous or not o.flags.writeable):
-                    raise FFTConvError(-1, "out buffers must be writable out_h x out_w float32 in Fortran order")
+                    raise FFTConvError(-1, "out buffers must be writable out_h x out_w %s in Fortran order" % dt.name)
         optr = (ctypes.c_void_p * n)(*[o.ctypes.data for o in outs])
         _check(self._lib.fftconv_plan_convolve(self._h, n, kptr, kh, kw, HOST, optr, HOST))
         return outs
@@ -403,7 +425,8 @@ class Plan:
         """fftconv_plan_convolve with maps in device memory: asynchronous on the plan's stream.  kernelCell: host arrays
         (kh x kw x F float32, consumed when the call returns) and / or (device pointer, kh, kw) triples of device-resident
         kernels ([F][kw][kh] floats, i.e. the same MATLAB array); kernel_location HOST (arrays only), DEVICE (triples only) or
-        AUTO (any mix: the runtime tells them apart).  out_ptrs: one device pointer per kernel, out_h x out_w floats each."""
+        AUTO (any mix: the runtime tells them apart).  out_ptrs: one device pointer per kernel, out_h x out_w elements of the
+        plan's "map_format" each (info.out_map_bytes: the caller sizes the buffers)."""
         ks, ptrs, khs, kws = [], [], [], []
         for k in kernelCell:
             if isinstance(k, tuple):
@@ -427,8 +450,8 @@ class Plan:
                                                (ctypes.c_void_p * n)(*[int(o) for o in out_ptrs]), DEVICE))
 
     def convolve_packed_device(self, n, kernels_ptr, kh, kw, out_ptr):
-        """n equally sized kernels packed in device memory -> n maps packed in device memory;
-        asynchronous on the plan's stream."""
+        """n equally sized kernels packed in device memory -> n maps packed in device memory (info.out_map_bytes each:
+        the caller sizes the buffer for the plan's "map_format"); asynchronous on the plan's stream."""
         _check(self._lib.fftconv_plan_convolve_packed(self._h, int(n), ctypes.c_void_p(int(kernels_ptr)),
                                                       int(kh), int(kw), ctypes.c_void_p(int(out_ptr))))
 
@@ -502,6 +525,9 @@ class MultiPlan:
         _check(self._lib.fftconv_multi_plan(self._h, 0, ctypes.byref(p), ctypes.byref(dev)))
         self.info = PlanInfo()
         _check(self._lib.fftconv_plan_get_info(p, ctypes.byref(self.info)))
+        fmt = ctypes.c_long(0)
+        _check(self._lib.fftconv_plan_get_option(p, b"map_format", ctypes.byref(fmt)))
+        self.map_dtype = MAP_DTYPES[int(fmt.value)]      # every plan of the handle was created with the same options
 
     def __len__(self):
         return self._lib.fftconv_multi_size(self._h)
@@ -537,7 +563,7 @@ class MultiPlan:
                 raise FFTConvError(-3, "Kernel and Data must have the same number of features and kernel "
                                        "size should be smaller than data size")
         n = len(ks)
-        outs = [np.empty((self.info.fft_h, self.info.fft_w), dtype=np.float32, order="F") for _ in range(n)]
+        outs = [np.empty((self.info.fft_h, self.info.fft_w), dtype=self.map_dtype, order="F") for _ in range(n)]
         optr = (ctypes.c_void_p * n)(*[o.ctypes.data for o in outs])
         _check(self._lib.fftconv_multi_convolve(self._h, n, kptr, kh, kw, HOST, optr, HOST))
         return outs

@@ -102,6 +102,7 @@ int tiled_create(fftconv_plan* p, int H, int W, int F, int mkh, int mkw, void* h
     if (options && options->struct_size >= kOptionsMinSize) memcpy(&sub_opts, options, std::min(sizeof(sub_opts), options->struct_size));
     sub_opts.struct_size = sizeof(sub_opts);
     sub_opts.blockwise = 1;          // the block plan itself is a single pass
+    sub_opts.map_format = 0;         // ... and stores fp32 (block-wise plans have no 16-bit maps: pipeline.hpp, map_format_error)
     ts->H = H; ts->W = W; ts->F = F; ts->mkh = mkh; ts->mkw = mkw;
     ts->FH = fft_size16(H + mkh - 1); ts->FW = fft_size16(W + mkw - 1);
     int rc = FFTCONV_ERR_UNSUPPORTED_SIZE;

@@ -150,7 +150,8 @@ struct FastColsArgs {
     const c32* Y;            // [n][i][y_pitch]
     size_t y_kernel_stride;
     int y_pitch;
-    float* out;              // kernel n at out + n*out_kernel_stride; (h, w) at w*fft_h + h
+    float* out;              // kernel n at out + n*out_kernel_stride; (h, w) at w*fft_h + h (strides and pitches count map
+                             // ELEMENTS: with a 16-bit out_format the pointer is opaque and the elements are 2 bytes)
     size_t out_kernel_stride;
     int fft_h, fft_w;        // output window: fft_h <= 2M (rows beyond it are cropped), fft_w % T == 0,
                              // every column < fft_w exists in Y
@@ -178,6 +179,9 @@ struct FastColsArgs {
     // Unsliced launches only.
     int* queue;
     int queue_shift;
+    // element format of the maps (fc_common.hpp: FC_MAP_*).  Read by the 16-bit instantiations only (OUT16 below), where it
+    // tells fp16 from bf16; the fp32 instantiations never look at it.
+    int out_format;
 };
 
 template <class C>
@@ -251,7 +255,10 @@ FC_HD int pair_of_unit(int u) {
 // tiles on 256 workgroups are 4 full rounds + 64 tiles; as 256 quarter tiles the fifth round moves a quarter of the bytes).
 // DYN: tiles from the dynamic queue (g.queue; see TileQueue above) instead of the static deal -- a template parameter so that
 // the static kernel carries none of the queue's scalar state (as a run-time switch it cost 6 SGPRs and 44 SGPR spills).
-template <class C, bool TILED, bool SLICED = false, bool DYN = false, class Ctx>
+// OUT16: the maps hold 16-bit elements (g.out_format: fp16 or bf16, uniform over the launch).  Only the store of C4 differs: a
+// thread's complex value is rows 2n, 2n + 1 of a column, converted and stored as ONE 32-bit word (out_pitch and h_lo are even:
+// the word is aligned).  A template parameter for the same reason as DYN: the fp32 kernel keeps its code and its registers.
+template <class C, bool TILED, bool SLICED = false, bool DYN = false, bool OUT16 = false, class Ctx>
 FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int nwg) {
     static_assert(!SLICED || TILED, "column slices exist for the tiled intermediate only");
     static_assert(!(SLICED && DYN), "the sliced tail round is dealt statically");
@@ -542,7 +549,9 @@ FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int
 
         FC_COLS_STAMP(3);
         // C4: inverse stage 1 straight to the map: out[w][2n], out[w][2n+1] = re, im of z[n]
-        float* out = g.out + (size_t)kernel * g.out_kernel_stride;
+        [[maybe_unused]] float* out = g.out + (size_t)kernel * g.out_kernel_stride;
+        [[maybe_unused]] uint16_t* out16 = reinterpret_cast<uint16_t*>(g.out) + (size_t)kernel * g.out_kernel_stride;
+        [[maybe_unused]] const bool out_bf16 = g.out_format == FC_MAP_BF16;
         const int pair_lo = g.h_lo >> 1;                                 // complex pairs [pair_lo, pair_lo + nout) of a column are stored
         const unsigned nout = (unsigned)((g.fft_h - g.h_lo) >> 1);
         ctx.phase([&](int t, [[maybe_unused]] State& st) {
@@ -578,12 +587,20 @@ FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int
                         v[c] = cmulc(p[c * C::S1], pw[c]);
                     });
                     Dft<R1, +1>::run(v);
+                    if constexpr (OUT16) {
+                        uint32_t* o = reinterpret_cast<uint32_t*>(out16 + (size_t)(w0 + col) * g.out_pitch);
+                        static_for<0, R1>([&](auto a_) {
+                            constexpr int a = decltype(a_)::value;
+                            if ((unsigned)(j + a * m1 - pair_lo) < nout) FC_STREAM_STORE4(&o[j + a * m1], fc_pack_map16(v[a].x, v[a].y, out_bf16));
+                        });
+                    } else {
                     c32* o = reinterpret_cast<c32*>(out + (size_t)(w0 + col) * g.out_pitch);
                     static_for<0, R1>([&](auto a_) {
                         constexpr int a = decltype(a_)::value;
                         if constexpr (FC_COLS_DBG & 8) { if (v[a].x == 1.2345e-30f) o[j + a * m1] = v[a]; }
                         else if ((unsigned)(j + a * m1 - pair_lo) < nout) FC_STREAM_STORE(&o[j + a * m1], v[a]);
                     });
+                    }
                 }
             }
         });

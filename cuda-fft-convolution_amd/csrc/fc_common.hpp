@@ -6,6 +6,7 @@
 //     workgroup bodies sequentially so the algorithm can be checked without a GPU).
 // The host build is test infrastructure; the product library contains no CPU compute path.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 
 #include "fc_instrument.hpp"
@@ -47,6 +48,13 @@
     } while (0)
 #else
 #define FC_STREAM_STORE(ptr, val) (*(ptr) = (val))
+#endif
+
+// The same for one 32-bit word: two 16-bit map elements (rows 2n, 2n + 1 of a column), 4 bytes per lane.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define FC_STREAM_STORE4(ptr, val) __builtin_nontemporal_store((uint32_t)(val), reinterpret_cast<uint32_t*>(ptr))
+#else
+#define FC_STREAM_STORE4(ptr, val) (*reinterpret_cast<uint32_t*>(ptr) = (uint32_t)(val))
 #endif
 
 // 16-byte load of data this kernel reads once.  A plain load, not a streaming (nontemporal) one:
@@ -207,6 +215,66 @@ FC_HD c32 fma_js(float s, c32 a, c32 t) {
     return r;
 #else
     return mk(t.x - s * a.y, t.y + s * a.x);
+#endif
+}
+
+// Element format of the result maps (plan option "map_format"): the arithmetic is fp32 up to the store, which converts each
+// value once -- round to nearest even, subnormal results kept, fp16 overflow to +-inf.
+enum { FC_MAP_F32 = 0, FC_MAP_F16 = 1, FC_MAP_BF16 = 2 };
+FC_HD constexpr size_t fc_map_elem_bytes(int format) { return format == FC_MAP_F32 ? 4 : 2; }
+
+FC_HD uint32_t fc_float_bits(float x) {
+    uint32_t u;
+    __builtin_memcpy(&u, &x, 4);
+    return u;
+}
+// the host side (tests/emu under g++, which has no __bf16; the host pass of hipcc): integer arithmetic on the fp32 bits
+FC_HD uint32_t fc_f16_bits_rne(float x) {
+    const uint32_t u = fc_float_bits(x), sign = (u >> 16) & 0x8000u, a = u & 0x7fffffffu;
+    if (a > 0x7f800000u) return sign | 0x7e00u;                 // NaN: quiet
+    if (a >= 0x477ff000u) return sign | 0x7c00u;                // 65520 and above (the tie goes to the even 65536 = inf), inf
+    if (a >= 0x38800000u) {                                     // normal result: exponent rebiased by 112, 13 mantissa bits dropped
+        const uint32_t r = a - 0x38000000u;
+        return sign | ((r + 0xfffu + ((r >> 13) & 1u)) >> 13);
+    }
+    const int shift = 126 - (int)(a >> 23);                     // subnormal result: units of 2^-24
+    if (shift > 24) return sign;                                // below 2^-25, or 2^-25 itself (tie to the even 0)
+    const uint32_t m = (a & 0x7fffffu) | 0x800000u, q = m >> shift, rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1);
+    return sign | (q + ((rem > half || (rem == half && (q & 1u))) ? 1u : 0u));
+}
+FC_HD uint32_t fc_bf16_bits_rne(float x) {
+    const uint32_t u = fc_float_bits(x);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;   // NaN: quiet
+    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
+// two fp32 values as one word of two 16-bit elements, `lo` in the low half (the lower address); bf16: a value uniform over
+// the launch.  Device: one v_cvt_pk_f16_f32 / v_cvt_pk_bf16_f32 (never the pkrtz builtin: it rounds toward zero).
+FC_HD uint32_t fc_pack_map16(float lo, float hi, bool bf16) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint32_t w;
+    if (bf16) {
+        typedef __bf16 fc_b2_ __attribute__((ext_vector_type(2)));
+        const fc_b2_ v = {(__bf16)lo, (__bf16)hi};
+        __builtin_memcpy(&w, &v, 4);
+    } else {
+        typedef _Float16 fc_h2_ __attribute__((ext_vector_type(2)));
+        const fc_h2_ v = {(_Float16)lo, (_Float16)hi};
+        __builtin_memcpy(&w, &v, 4);
+    }
+    return w;
+#else
+    return bf16 ? (fc_bf16_bits_rne(lo) | (fc_bf16_bits_rne(hi) << 16)) : (fc_f16_bits_rne(lo) | (fc_f16_bits_rne(hi) << 16));
+#endif
+}
+// one element (the crop / pad kernels: region maps are only 2-byte aligned)
+FC_HD uint16_t fc_map16(float x, bool bf16) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint16_t h;
+    if (bf16) { const __bf16 v = (__bf16)x; __builtin_memcpy(&h, &v, 2); }
+    else { const _Float16 v = (_Float16)x; __builtin_memcpy(&h, &v, 2); }
+    return h;
+#else
+    return (uint16_t)(bf16 ? fc_bf16_bits_rne(x) : fc_f16_bits_rne(x));
 #endif
 }
 

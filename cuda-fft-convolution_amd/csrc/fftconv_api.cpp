@@ -152,7 +152,10 @@ struct Delivery {
     // kernel compacts the region into the destination (the caller's packed buffer or the staging OC)
     bool cropped = false;
     DevBuf<float>* stage = nullptr;    // staged routes: where the maps wait for their copy (OC when cropped, else O)
-    size_t oe = 0;                     // floats per delivered map
+    size_t oe = 0;                     // elements per delivered map
+    size_t eb = sizeof(float);         // bytes per element ("map_format")
+    size_t mb() const { return oe * eb; }
+    int kernel_format = FC_MAP_F32;    // what the output kernel stores: the plan's format, or fp32 into the staging a crop reads
     bool staged() const { return route == Route::Copies || route == Route::Pinned || route == Route::Ring; }
 };
 
@@ -162,7 +165,9 @@ int plan_delivery(fftconv_plan* p, const Sink& sink, int nbY, Delivery& d) {
     d.cropped = p->opt_region != 0;
     d.stage = d.cropped ? &p->OC : &p->O;
     d.oe = p->out_elems();
-    const size_t map_bytes = d.oe * sizeof(float);
+    d.eb = p->elem_bytes();
+    d.kernel_format = d.cropped ? FC_MAP_F32 : (int)p->opt_map_format;
+    const size_t map_bytes = d.mb();
     // host output: the ring for maps of at least host_min_kb (1 MiB).  Smaller ones leave by blocking copies on the plan's stream:
     // the copy threads buy them nothing (a one-shot call would start and join them for a few hundred KB), and
     // small destination buffers are heap neighbours that share pages, which the runtime pins in place from
@@ -178,7 +183,7 @@ int plan_delivery(fftconv_plan* p, const Sink& sink, int nbY, Delivery& d) {
     if (d.cropped)
         if (int rc = p->O.ensure(g.map_elems() * nbY)) return rc;
     if (d.staged())
-        if (int rc = d.stage->ensure(d.oe * nbY * (d.route == Route::Ring ? 2 : 1))) return rc;
+        if (int rc = d.stage->ensure(floats_for(d.oe * nbY * (d.route == Route::Ring ? 2 : 1), d.eb))) return rc;
     if (d.route == Route::Ring) return ring_begin(p);
     return 0;
 }
@@ -197,19 +202,27 @@ int launch_spectral_rows_batch(fftconv_plan* p, const c32* a, int kw, int ny) {
     return p->prof_end();
 }
 
+const char* const kMapFormatNames[] = {"fp32", "fp16", "bf16"};      // FC_MAP_*
+
 // output columns of ny maps: Y transformed along h into the maps at obase (or into the window of an overlap-save block)
-int launch_output_cols(fftconv_plan* p, const OutWindow* win, float* obase, int ny) {
+int launch_output_cols(fftconv_plan* p, const OutWindow* win, float* obase, int ny, int format) {
     const Geometry& g = p->g;
     if (int rc = p->prof_begin(PK_OUT_COLS, ny)) return rc;
     if (g.fast_cols.ok) {
-        FastColsArgs fa = fast_cols_args(g, p->d, p->Y.p, obase, win ? win->map_stride : g.map_elems(), ny);
+        FastColsArgs fa = fast_cols_args(g, p->d, p->Y.p, obase, win ? win->map_stride : g.map_elems(), ny, format);
         if (win) {
             fa.h_lo = win->h_lo; fa.fft_h = win->h_hi; fa.w_first = win->w_first; fa.out_pitch = win->pitch;
             fa.tiles_per_kernel = win->ncols / g.fast_cols.T; fa.ntiles = fa.tiles_per_kernel * ny;
         }
+        if (p->opt_verbose) {      // which instantiation the launch layer picks (fast_paths.hpp: fast_cols_launch_shape), and what it stores
+            static const char* const variants[] = {"row-major", "tiled", "tiled, sliced tail round", "tiled, dynamic tile queue"};
+            const FastColsShape sh = fast_cols_launch_shape(g.M, g.fast_cols.T, fa, persistent_want(g.fast_cols.lds_bytes, g.fast_cols.NT, p->num_cus));
+            FC_VERBOSE(p, "output kernel: %s intermediate, %d workgroups, %s elements", variants[(int)sh.variant], sh.grid, kMapFormatNames[format]);
+        }
         HIP_TRY(launch_fast_cols(g.M, g.fast_cols.T, fa, p->num_cus, p->stream));
     } else {
-        ColsC2RArgs ca = cols_c2r_args(g, p->t, p->d, p->Y.p, obase, g.map_elems());
+        FC_VERBOSE(p, "output kernel: generic%s, %s elements", g.bluestein_h() ? " (chirp-z)" : "", kMapFormatNames[format]);
+        ColsC2RArgs ca = cols_c2r_args(g, p->t, p->d, p->Y.p, obase, g.map_elems(), format);
         HIP_TRY(launch_cols_c2r(ca, tiles_for(g.fft_w, g.T_cols), ny, cols_threads(g), p->cols_lds(), p->stream));
     }
     return p->prof_end();
@@ -221,7 +234,7 @@ int launch_output_cols(fftconv_plan* p, const OutWindow* win, float* obase, int 
 //  FC_PIN_ONE_MAP_BYTES takes the plain copy of deliver_batch: the CPU's pass over it costs more than the runtime's pinning --
 //  one 324-KiB map: 77 against 60 us per convolve, four of them: 131 against 166, profiles/r04s_small_call_latency.txt)
 int deliver_pinned(fftconv_plan* p, const Delivery& d, float* const* out, int ny) {
-    const size_t mb = d.oe * sizeof(float);
+    const size_t mb = d.mb();
     const int per_copy = (int)std::min<size_t>((size_t)ny, (FC_PIN_OUT_BYTES / 2) / mb);
     const int nchunks = (ny + per_copy - 1) / per_copy;
     if (int rc = p->pin_out.ensure((size_t)per_copy * mb * (nchunks > 1 ? 2 : 1))) return rc;
@@ -229,7 +242,7 @@ int deliver_pinned(fftconv_plan* p, const Delivery& d, float* const* out, int ny
         if (!p->pin_out_done[h]) HIP_TRY(hipEventCreateWithFlags(&p->pin_out_done[h], hipEventDisableTiming));
     auto copy_chunk = [&](int c) -> hipError_t {
         const int j0 = c * per_copy, nj = std::min(per_copy, ny - j0);
-        hipError_t e = hipMemcpyAsync(p->pin_out.p + (size_t)(c & 1) * per_copy * mb, d.stage->p + (size_t)j0 * d.oe, (size_t)nj * mb,
+        hipError_t e = hipMemcpyAsync(p->pin_out.p + (size_t)(c & 1) * per_copy * mb, map_at(d.stage->p, (size_t)j0 * d.oe, d.eb), (size_t)nj * mb,
                                       hipMemcpyDeviceToHost, p->stream);
         if (e == hipSuccess) e = hipEventRecord(p->pin_out_done[c & 1], p->stream);
         return e;
@@ -248,10 +261,10 @@ int deliver_pinned(fftconv_plan* p, const Delivery& d, float* const* out, int ny
 // the maps [first, first + ny) are queued into `dest` (staging buffer buf of a streamed group): their way to the caller
 int deliver_batch(fftconv_plan* p, const Delivery& d, const Sink& sink, int first, int ny, int buf, const float* dest) {
     if (d.route == Route::Ring) return ring_batch_launched(p, sink, first, ny, buf, dest);
-    if (d.route == Route::Pinned && (ny > 1 || d.oe * sizeof(float) <= FC_PIN_ONE_MAP_BYTES)) return deliver_pinned(p, d, sink.ptrs + first, ny);
+    if (d.route == Route::Pinned && (ny > 1 || d.mb() <= FC_PIN_ONE_MAP_BYTES)) return deliver_pinned(p, d, sink.ptrs + first, ny);
     if (!d.staged()) return 0;         // the kernels wrote where the caller reads
     for (int j = 0; j < ny; j++)
-        HIP_TRY(hipMemcpyAsync(sink.ptrs[first + j], dest + (size_t)j * d.oe, d.oe * sizeof(float), copy_kind(sink.location, false), p->stream));
+        HIP_TRY(hipMemcpyAsync(sink.ptrs[first + j], map_at(dest, (size_t)j * d.oe, d.eb), d.mb(), copy_kind(sink.location, false), p->stream));
     if (sink.location == FFTCONV_HOST) HIP_TRY(hipStreamSynchronize(p->stream));
     return 0;
 }
@@ -274,7 +287,7 @@ int run_group_impl(fftconv_plan* p, int n, const float* dk, int kh, int kw, cons
     Delivery d;
     if (int rc = plan_delivery(p, sink, nbY, d)) return rc;
     if (p->Y.fresh)     // before anything is written into it: the tuner may keep another allocation
-        if (int rc = tune_intermediate_placement(p, sink, n, nbY, d.cropped ? p->O.p : d.staged() ? d.stage->p : sink.packed, !d.cropped && !d.staged()))
+        if (int rc = tune_intermediate_placement(p, sink, n, nbY, d.cropped ? p->O.p : d.staged() ? d.stage->p : sink.packed, !d.cropped && !d.staged(), d.kernel_format))
             return rc;
     for (int a0 = 0; a0 < n; a0 += nbA) {
         const int na = std::min(nbA, n - a0);
@@ -292,8 +305,8 @@ int run_group_impl(fftconv_plan* p, int n, const float* dk, int kh, int kw, cons
             if (d.route == Route::Ring)
                 if (int rc = ring_claim_staging(p, &buf)) return rc;
             float* dest = sink.window ? sink.window->base + (size_t)first * sink.window->map_stride            // where the maps of this batch go
-                          : d.staged() ? d.stage->p + (size_t)buf * nbY * d.oe : sink.packed + (size_t)first * d.oe;
-            if (int rc = launch_output_cols(p, sink.window, d.cropped ? p->O.p : dest, ny)) return rc;
+                          : d.staged() ? map_at(d.stage->p, (size_t)buf * nbY * d.oe, d.eb) : map_at(sink.packed, (size_t)first * d.oe, d.eb);
+            if (int rc = launch_output_cols(p, sink.window, d.cropped ? p->O.p : dest, ny, d.kernel_format)) return rc;
             if (d.cropped)
                 if (int rc = launch_region(p, p->O.p, dest, ny, p->stream)) return rc;
             if (int rc = deliver_batch(p, d, sink, first, ny, buf, dest)) return rc;
@@ -327,6 +340,7 @@ const LongOption kLongOptions[] = {
     {"batch_maps", &fftconv_plan::opt_batch_maps, 0, LONG_MAX, OPT_FORGETS},
     {"verbose", &fftconv_plan::opt_verbose, 0, 1, OPT_BOOL},
     {"flip_kernels", &fftconv_plan::opt_flip_kernels, 0, 1, OPT_BOOL | OPT_FORGETS},
+    {"map_format", &fftconv_plan::opt_map_format, FC_MAP_F32, FC_MAP_BF16, OPT_REJECT | OPT_FORGETS | OPT_RING},   // (the ring is sized for the map bytes)
     {"host_pinned", &fftconv_plan::opt_host_pinned, 0, 1, OPT_BOOL},
     {"host_min_kb", &fftconv_plan::opt_host_min_kb, 0, 1 << 30, OPT_REJECT},
     {"host_stream", &fftconv_plan::opt_host_stream, 0, 1 << 20, OPT_REJECT | OPT_RING},   // (0, 1 or 2: checked once the ring is down)
@@ -351,8 +365,11 @@ namespace fc {
 
 int launch_region(const fftconv_plan* p, const float* src, float* dst, int nmaps, hipStream_t s) {
     const Geometry& g = p->g;      // (block-wise plans: g holds the whole window)
-    if (p->opt_region == 4) HIP_TRY(launch_pad_maps(src, g.fft_h, g.fft_w, g.map_elems(), dst, p->out_h, p->out_w, p->out_elems(), nmaps, s));
-    else HIP_TRY(launch_crop_maps(src, g.fft_h, g.map_elems(), dst, p->out_h, p->out_w, p->out_elems(), p->off_h, p->off_w, nmaps, s));
+    const int format = (int)p->opt_map_format;      // of dst; src is fp32
+    FC_VERBOSE(p, "output region %ld: %d maps %s from the fp32 window into %d x %d %s maps", p->opt_region, nmaps, p->opt_region == 4 ? "padded" : "cropped",
+               p->out_h, p->out_w, kMapFormatNames[format]);
+    if (p->opt_region == 4) HIP_TRY(launch_pad_maps(src, g.fft_h, g.fft_w, g.map_elems(), dst, p->out_h, p->out_w, p->out_elems(), nmaps, s, format));
+    else HIP_TRY(launch_crop_maps(src, g.fft_h, g.map_elems(), dst, p->out_h, p->out_w, p->out_elems(), p->off_h, p->off_w, nmaps, s, format));
     return 0;
 }
 
@@ -456,6 +473,15 @@ static int plan_device_setup(fftconv_plan* p) {
     return 0;
 }
 
+// would plan_create_internal make a block-wise plan of these sizes and options?  (its own decision, on a geometry of its own)
+static bool planner_goes_blockwise(int H, int W, int F, int mkh, int mkw, const fftconv_plan_options* options) {
+    const PlanTuning tune = tuning_from(options);
+    if (tune.exact_window || options_no_blockwise(options)) return false;
+    Geometry g;
+    Tables t;
+    return !make_geometry(g, t, H, W, F, mkh, mkw, tune) || blocks_preferred(g, options);
+}
+
 // cyclic: the block plan of an overlap-save block-wise plan (PlanTuning::cyclic) -- never block-wise itself
 int fc::plan_create_internal(fftconv_plan** plan, int data_h, int data_w, int feature_dim, int max_kernel_h, int max_kernel_w, int gpu_id,
                          void* hip_stream, const fftconv_plan_options* options, bool cyclic) {
@@ -463,6 +489,14 @@ int fc::plan_create_internal(fftconv_plan** plan, int data_h, int data_w, int fe
     *plan = nullptr;
     if (data_h < 1 || data_w < 1 || feature_dim < 1) return api_fail(FFTCONV_ERR_INVALID_ARG, "Invalid data input");
     if (max_kernel_h < 1 || max_kernel_w < 1) return api_fail(FFTCONV_ERR_INVALID_ARG, "Invalid maximum kernel size");
+    // 16-bit maps ("map_format"): a value out of range, or one on sizes the planner takes block-wise, is an argument error, found
+    // before anything touches a device.  (a block plan stores fp32 whatever its options say)
+    const int map_format = (cyclic || (options && options->struct_size < kOptionsMinSize)) ? FC_MAP_F32 : options_map_format(options);
+    if (map_format != FC_MAP_F32) {
+        const char* why = map_format_error(map_format, false);
+        if (!why && planner_goes_blockwise(data_h, data_w, feature_dim, max_kernel_h, max_kernel_w, options)) why = map_format_error(map_format, true);
+        if (why) return api_fail(FFTCONV_ERR_INVALID_ARG, "%s", why);
+    }
     int ndev = 0;
     if (int rc = fftconv_device_count(&ndev)) return rc;
     if (gpu_id < 0) HIP_TRY(hipGetDevice(&gpu_id));
@@ -474,6 +508,7 @@ int fc::plan_create_internal(fftconv_plan** plan, int data_h, int data_w, int fe
     tune.cyclic = cyclic;
     if (cyclic) { tune.exact_window = false; tune.max_transform = 0; }
     p->opt_verbose = options_verbose(options) ? 1 : 0;
+    p->opt_map_format = map_format;
     p->gpu_id = gpu_id;
     p->stream = reinterpret_cast<hipStream_t>(hip_stream);
     const bool may_block = !cyclic && !options_no_blockwise(options) && !tune.exact_window;
@@ -540,10 +575,10 @@ int fftconv_plan_get_info(const fftconv_plan* plan, fftconv_plan_info* info) {
     info->gpu_id = plan->gpu_id;
     info->exact_window = g.exact_window ? 1 : 0;
     info->spectrum_bytes = g.spectrum_elems() * sizeof(c32);
-    info->map_bytes = g.map_elems() * sizeof(float);
+    info->map_bytes = g.map_elems() * plan->elem_bytes();
     info->out_h = plan->opt_region ? plan->out_h : g.fft_h;
     info->out_w = plan->opt_region ? plan->out_w : g.fft_w;
-    info->out_map_bytes = plan->out_elems() * sizeof(float);
+    info->out_map_bytes = plan->out_map_bytes();
     info->workspace_bytes = plan->A.bytes() + plan->Y.bytes() + plan->K.bytes() + plan->O.bytes() + plan->I.bytes();
     if (const TiledState* ts = plan->tiled) {     // block-wise: the window of the whole image; the spectrum is every block's
         info->spectrum_bytes = ts->spec_total() * sizeof(c32);
@@ -850,6 +885,8 @@ int fftconv_plan_synchronize(fftconv_plan* plan) {
 
 int fftconv_plan_set_option(fftconv_plan* plan, const char* name, long value) {
     if (!plan || !name) return api_fail(FFTCONV_ERR_INVALID_ARG, "NULL argument");
+    if (!strcmp(name, "map_format"))
+        if (const char* why = map_format_error(value, plan->tiled != nullptr)) return api_fail(FFTCONV_ERR_INVALID_ARG, "%s", why);
     if (plan->tiled && strcmp(name, "output_region")) {      // block-wise: options act on the block plan ("output_region": on this one, below)
         if (!strcmp(name, "verbose")) plan->opt_verbose = value != 0;
         return fftconv_plan_set_option(plan->tiled->sub, name, value);

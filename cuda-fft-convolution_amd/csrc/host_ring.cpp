@@ -13,7 +13,7 @@ int ring_begin(fftconv_plan* p) {
         p->ring->prev.valid = false;
         return 0;
     }
-    const size_t map_bytes = p->out_elems() * sizeof(float);
+    const size_t map_bytes = p->out_map_bytes();
     size_t chunk = p->opt_host_chunk_kb > 0 ? (size_t)p->opt_host_chunk_kb << 10 : (size_t)8 << 20;
     chunk = std::min(chunk, (map_bytes + 4095) / 4096 * 4096);
     chunk = std::max<size_t>(4096, chunk / 4096 * 4096);
@@ -76,17 +76,17 @@ static int ring_drain(fftconv_plan* p, const Sink& sink) {
     r->prev.valid = false;
     const int first = r->prev.first, count = r->prev.count, buf = r->prev.buf;
     const float* staging = r->prev.staging;
-    const size_t map_bytes = p->out_elems() * sizeof(float);
+    const size_t map_bytes = p->out_map_bytes();      // (the staged maps lie map_bytes apart, whatever their element size)
     if (r->nslots == 0) {   // direct: whole maps, one per host thread at a time
         for (int j = 0; j < count; j++)
-            r->submit_direct(reinterpret_cast<const char*>(staging + (size_t)j * p->out_elems()),
+            r->submit_direct(reinterpret_cast<const char*>(staging) + (size_t)j * map_bytes,
                              reinterpret_cast<char*>(sink.ptrs[first + j]), map_bytes, buf, caller_pinned(sink.ptrs[first + j]));
         return 0;
     }
     HIP_TRY(hipStreamWaitEvent(r->copy_stream, r->compute_done[buf], 0));
     for (int j = 0; j < count; j++) {
         char* dst = reinterpret_cast<char*>(sink.ptrs[first + j]);
-        const char* src = reinterpret_cast<const char*>(staging + (size_t)j * p->out_elems());
+        const char* src = reinterpret_cast<const char*>(staging) + (size_t)j * map_bytes;
         if (caller_pinned(dst)) {
             HIP_TRY(hipMemcpyAsync(dst, src, map_bytes, hipMemcpyDeviceToHost, r->copy_stream));
             continue;

@@ -40,6 +40,12 @@ __global__ void __launch_bounds__(512) k_cols_c2r(ColsC2RArgs a) {
     DevCtx ctx{(int)threadIdx.x, (int)blockDim.x};
     cols_c2r_body<BS>(ctx, reinterpret_cast<c32*>(fc_smem), a, (int)blockIdx.x, (int)blockIdx.y);
 }
+// the same with 16-bit maps (plan option "map_format"; a.out_format: fp16 or bf16)
+template <int BS>
+__global__ void __launch_bounds__(512) k_cols_c2r16(ColsC2RArgs a) {
+    DevCtx ctx{(int)threadIdx.x, (int)blockDim.x};
+    cols_c2r_body<BS, true>(ctx, reinterpret_cast<c32*>(fc_smem), a, (int)blockIdx.x, (int)blockIdx.y);
+}
 
 // Reverses every plane of `pe` floats: for a column-major kh x kw plane that is the flip along both
 // axes, kernel(end:-1:1, end:-1:1, f) of demoCudaConvolutionFFT.m:67-69.
@@ -73,6 +79,16 @@ __global__ void __launch_bounds__(256) k_crop_maps(const float* __restrict__ src
     for (int y = (int)threadIdx.x; y < dst_h; y += (int)blockDim.x) d[y] = s[y];
 }
 
+// the same into 16-bit maps (fp16 / bf16: fc_map16): the source is the fp32 full-window staging.  Region maps can have an odd
+// out_h and an odd element count, so the destination is only 2-byte aligned: one element per store.
+__global__ void __launch_bounds__(256) k_crop_maps16(const float* __restrict__ src, int src_h, size_t src_map_stride, uint16_t* __restrict__ dst,
+                                                     int dst_h, int dst_w, size_t dst_map_stride, int off_h, int off_w, int bf16) {
+    const int x = (int)blockIdx.x, map = (int)blockIdx.y;
+    const float* s = src + (size_t)map * src_map_stride + (size_t)(off_w + x) * src_h + off_h;
+    uint16_t* d = dst + (size_t)map * dst_map_stride + (size_t)x * dst_h;
+    for (int y = (int)threadIdx.x; y < dst_h; y += (int)blockDim.x) d[y] = fc_map16(s[y], bf16 != 0);
+}
+
 // Image spectrum between the engine's internal order and the reference's natural order
 // [f][FFT_W][FFT_H/2+1] (cufftExecR2C output, src/cudaFFTData.cu:90-103): natural element (x, y) of
 // plane f is internal element S[f][row_of[y]][col_of[x]]; `scale` undoes / applies the folded
@@ -102,11 +118,25 @@ __global__ void __launch_bounds__(256) k_pad_maps(const float* __restrict__ src,
     for (int y = (int)threadIdx.x; y < dst_h; y += (int)blockDim.x) d[y] = y < n ? s[y] : 0.f;
 }
 
+__global__ void __launch_bounds__(256) k_pad_maps16(const float* __restrict__ src, int src_h, int src_w, size_t src_map_stride,
+                                                    uint16_t* __restrict__ dst, int dst_h, size_t dst_map_stride, int bf16) {
+    const int x = (int)blockIdx.x, map = (int)blockIdx.y;
+    const float* s = src + (size_t)map * src_map_stride + (size_t)x * src_h;
+    uint16_t* d = dst + (size_t)map * dst_map_stride + (size_t)x * dst_h;
+    const int n = x < src_w ? src_h : 0;
+    for (int y = (int)threadIdx.x; y < dst_h; y += (int)blockDim.x) d[y] = fc_map16(y < n ? s[y] : 0.f, bf16 != 0);
+}
+
 }  // namespace
 
 hipError_t launch_pad_maps(const float* src, int src_h, int src_w, size_t src_map_stride, float* dst, int dst_h, int dst_w,
-                           size_t dst_map_stride, int nmaps, hipStream_t s) {
+                           size_t dst_map_stride, int nmaps, hipStream_t s, int format) {
     if (nmaps <= 0 || dst_h <= 0 || dst_w <= 0) return hipSuccess;
+    if (format != FC_MAP_F32) {
+        hipLaunchKernelGGL(k_pad_maps16, dim3((unsigned)dst_w, (unsigned)nmaps), dim3(256), 0, s, src, src_h, src_w, src_map_stride,
+                           reinterpret_cast<uint16_t*>(dst), dst_h, dst_map_stride, format == FC_MAP_BF16 ? 1 : 0);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(k_pad_maps, dim3((unsigned)dst_w, (unsigned)nmaps), dim3(256), 0, s, src, src_h, src_w, src_map_stride, dst, dst_h,
                        dst_map_stride);
     return hipGetLastError();
@@ -137,8 +167,13 @@ hipError_t launch_add_window(float* dst, int dst_h, int dst_w, size_t dst_map_st
 }
 
 hipError_t launch_crop_maps(const float* src, int src_h, size_t src_map_stride, float* dst, int dst_h, int dst_w, size_t dst_map_stride,
-                            int off_h, int off_w, int nmaps, hipStream_t s) {
+                            int off_h, int off_w, int nmaps, hipStream_t s, int format) {
     if (nmaps <= 0 || dst_h <= 0 || dst_w <= 0) return hipSuccess;
+    if (format != FC_MAP_F32) {
+        hipLaunchKernelGGL(k_crop_maps16, dim3((unsigned)dst_w, (unsigned)nmaps), dim3(256), 0, s, src, src_h, src_map_stride,
+                           reinterpret_cast<uint16_t*>(dst), dst_h, dst_w, dst_map_stride, off_h, off_w, format == FC_MAP_BF16 ? 1 : 0);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(k_crop_maps, dim3((unsigned)dst_w, (unsigned)nmaps), dim3(256), 0, s, src, src_h, src_map_stride, dst, dst_h, dst_w,
                        dst_map_stride, off_h, off_w);
     return hipGetLastError();
@@ -168,6 +203,8 @@ hipError_t fast_rows_multi_wgs_per_cu(int L, int nz2, const FastRowsArgs& a, int
 
 hipError_t launch_fast_cols(int M, int T, const FastColsArgs& a, int num_cus, hipStream_t s) {
     if (a.ntiles <= 0) return hipSuccess;
+    if (a.out_format != FC_MAP_F32)     // 16-bit maps: the instantiations of kernels_cols16_g<G>.hip
+        return in_first_group<FC_COL_GROUPS>([&](auto g) { return launch_fast_cols16_group<g.value>(M, T, a, num_cus, s); });
     return in_first_group<FC_COL_GROUPS>([&](auto g) { return launch_fast_cols_group<g.value>(M, T, a, num_cus, s); });
 }
 
@@ -187,7 +224,8 @@ hipError_t kernels_init() {
     const void* generic[] = {reinterpret_cast<const void*>(k_cols_r2c<0>),      reinterpret_cast<const void*>(k_cols_r2c<1>),
                              reinterpret_cast<const void*>(k_rows_fwd<0>),      reinterpret_cast<const void*>(k_rows_fwd<1>),
                              reinterpret_cast<const void*>(k_spectral_rows<0>), reinterpret_cast<const void*>(k_spectral_rows<1>),
-                             reinterpret_cast<const void*>(k_cols_c2r<0>),      reinterpret_cast<const void*>(k_cols_c2r<1>)};
+                             reinterpret_cast<const void*>(k_cols_c2r<0>),      reinterpret_cast<const void*>(k_cols_c2r<1>),
+                             reinterpret_cast<const void*>(k_cols_c2r16<0>),    reinterpret_cast<const void*>(k_cols_c2r16<1>)};
     for (const void* k : generic) {
         const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
         if (e != hipSuccess) return e;
@@ -215,6 +253,11 @@ hipError_t launch_spectral_rows(const SpectralRowsArgs& a, int rows, int kernels
 }
 hipError_t launch_cols_c2r(const ColsC2RArgs& a, int tiles, int kernels, int threads, size_t lds_bytes, hipStream_t s) {
     if (tiles <= 0 || kernels <= 0) return hipSuccess;
+    if (a.out_format != FC_MAP_F32) {
+        if (a.fd.bs_work > 0) hipLaunchKernelGGL(k_cols_c2r16<1>, dim3(tiles, kernels), dim3(threads), lds_bytes, s, a);
+        else hipLaunchKernelGGL(k_cols_c2r16<0>, dim3(tiles, kernels), dim3(threads), lds_bytes, s, a);
+        return hipGetLastError();
+    }
     if (a.fd.bs_work > 0) hipLaunchKernelGGL(k_cols_c2r<1>, dim3(tiles, kernels), dim3(threads), lds_bytes, s, a);
     else hipLaunchKernelGGL(k_cols_c2r<0>, dim3(tiles, kernels), dim3(threads), lds_bytes, s, a);
     return hipGetLastError();

@@ -18,14 +18,15 @@ hipError_t launch_flip_planes(const float* src, float* dst, int plane_elems, lon
 hipError_t launch_add_window(float* dst, int dst_h, int dst_w, size_t dst_map_stride, int y0, int x0, const float* src, int src_h,
                              int src_w, size_t src_map_stride, int nmaps, hipStream_t s);
 // dst[map] (dst_h x dst_w, contiguous) = window of src[map] at (off_h, off_w); src has src_h rows per column
+// (format: FC_MAP_* of dst -- a 16-bit dst is an opaque pointer whose stride counts 2-byte elements; src is fp32 whatever the format)
 hipError_t launch_crop_maps(const float* src, int src_h, size_t src_map_stride, float* dst, int dst_h, int dst_w, size_t dst_map_stride,
-                            int off_h, int off_w, int nmaps, hipStream_t s);
+                            int off_h, int off_w, int nmaps, hipStream_t s, int format = FC_MAP_F32);
 // natural [f][fw][ch] <-> internal image-spectrum order (see kernels.hip: k_spectrum_reorder)
 hipError_t launch_spectrum_reorder(bool to_natural, c32* S, size_t s_plane, int s_pitch, c32* nat, int fw, int ch, int planes,
                                    const int* row_of, const int* col_of, float scale, hipStream_t s);
 // dst[map] (dst_h x dst_w >= src) = src[map] in the top-left corner, zero elsewhere
 hipError_t launch_pad_maps(const float* src, int src_h, int src_w, size_t src_map_stride, float* dst, int dst_h, int dst_w,
-                           size_t dst_map_stride, int nmaps, hipStream_t s);
+                           size_t dst_map_stride, int nmaps, hipStream_t s, int format = FC_MAP_F32);
 hipError_t launch_cols_r2c(const ColsR2CArgs& a, int tiles, int planes, int threads, size_t lds_bytes, hipStream_t s);
 hipError_t launch_rows_fwd(const RowsFwdArgs& a, int rows, int threads, size_t lds_bytes, hipStream_t s);
 // specialised forward image rows (fast_rows_fwd.hpp); hipErrorInvalidValue if L has no configuration
@@ -51,6 +52,8 @@ template <int G> GroupResult launch_fast_rows_fwd_group(int L, const FastRowsFwd
 template <int G> GroupResult launch_fast_rows_multi_group(int L, int nz2, const FastRowsArgs& a, int rows, int kernels, int kernels_per_wg, hipStream_t s);
 template <int G> GroupResult fast_rows_multi_wgs_per_cu_group(int L, int nz2, const FastRowsArgs& a, int* wgs_per_cu);
 template <int G> GroupResult launch_fast_cols_group(int M, int T, const FastColsArgs& a, int num_cus, hipStream_t s);
+// (the 16-bit-map instantiations of the same configurations: kernels_cols16_g<G>.hip)
+template <int G> GroupResult launch_fast_cols16_group(int M, int T, const FastColsArgs& a, int num_cus, hipStream_t s);
 template <int G> GroupResult launch_fast_cols_fwd_group(int M, int T, bool pruned, const FastColsFwdArgs& a, int num_cus, hipStream_t s);
 template <int G> GroupResult launch_fast_cols_fwd_pair_group(int M, int T, const FastColsFwdArgs& image, const FastColsFwdArgs& kernels,
                                                              bool kernels_pruned, int num_cus, hipStream_t s);

@@ -206,9 +206,12 @@ struct ColsC2RArgs {
     const c32* tw;
     const PairEntry* pairs;
     int npairs;
+    int out_format;      // element format of the maps (fc_common.hpp: FC_MAP_*); read by the OUT16 instantiations only, where it
+                         // tells fp16 from bf16 and `out`, its stride and fft_h count 2-byte elements
 };
 
-template <int BS = -1, class Ctx>
+// OUT16: 16-bit maps -- only the store differs (rows 2n, 2n + 1 of a column as one 32-bit word; fft_h is even)
+template <int BS = -1, bool OUT16 = false, class Ctx>
 FC_HD void cols_c2r_body(const Ctx& ctx, c32* lds, const ColsC2RArgs& a, int tile, int kernel) {
     const int M = a.M, T = a.T, LP = a.lds_pitch;
     const int w0 = tile * T;
@@ -244,13 +247,17 @@ FC_HD void cols_c2r_body(const Ctx& ctx, c32* lds, const ColsC2RArgs& a, int til
     // (the merge above reads slot M, which a Bluestein transform uses as scratch: it is over before the inverse starts)
     fft_inverse<BS>(ctx, lds, LP, T, a.fd, a.tw);
     // store: out[w][2n], out[w][2n+1] = re, im of z[n]; zero-fill up to fft_h
-    float* out = a.out + (size_t)kernel * a.out_kernel_stride;
+    [[maybe_unused]] float* out = a.out + (size_t)kernel * a.out_kernel_stride;
     const int half = a.fft_h / 2;  // fft_h is a multiple of 16
     for (int idx = ctx.tid; idx < T * half; idx += ctx.nthreads) {
         int t = idx / half, n = idx - t * half;
         int w = w0 + t;
         if (w < a.fft_w) {
             c32 v = (n < M) ? lds[t * LP + n] : mk(0.f, 0.f);
+            if constexpr (OUT16) {
+                uint16_t* o16 = reinterpret_cast<uint16_t*>(a.out) + (size_t)kernel * a.out_kernel_stride + (size_t)w * a.fft_h + 2 * n;
+                *reinterpret_cast<uint32_t*>(o16) = fc_pack_map16(v.x, v.y, a.out_format == FC_MAP_BF16);
+            } else
             *reinterpret_cast<c32*>(out + (size_t)w * a.fft_h + 2 * n) = v;
         }
     }

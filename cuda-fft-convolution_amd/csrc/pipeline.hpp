@@ -278,9 +278,11 @@ inline FastRowsArgs fast_rows_args(const Geometry& g, const DeviceTables& d, con
 }
 
 // fast output columns: nk kernels of the current batch
+// (out_format: FC_MAP_* of the maps at `out`; strides count elements whatever their size)
 inline FastColsArgs fast_cols_args(const Geometry& g, const DeviceTables& d, const c32* Y, float* out,
-                                   size_t out_kernel_stride, int nk) {
+                                   size_t out_kernel_stride, int nk, int out_format = FC_MAP_F32) {
     FastColsArgs a{};
+    a.out_format = out_format;
     a.Y = Y; a.y_kernel_stride = g.y_elems_per_kernel(); a.y_pitch = g.y_pitch;
     a.out = out; a.out_kernel_stride = out_kernel_stride; a.fft_h = g.fft_h; a.fft_w = g.fft_w;
     a.h_lo = 0; a.w_first = 0; a.out_pitch = g.fft_h;
@@ -314,8 +316,9 @@ inline FastColsFwdArgs fast_cols_fwd_args(const Geometry& g, const DeviceTables&
 inline int fast_rows_nz2(const Geometry& g, int kw) { return (kw + g.fast_rows.R3 - 1) / g.fast_rows.R3; }
 
 inline ColsC2RArgs cols_c2r_args(const Geometry& g, const Tables& t, const DeviceTables& d,
-                                 const c32* Y, float* out, size_t out_kernel_stride) {
+                                 const c32* Y, float* out, size_t out_kernel_stride, int out_format = FC_MAP_F32) {
     ColsC2RArgs a{};
+    a.out_format = out_format;
     a.Y = Y; a.y_kernel_stride = g.y_elems_per_kernel(); a.y_pitch = g.y_pitch; a.wvalid = g.wout;
     a.out = out; a.out_kernel_stride = out_kernel_stride; a.fft_h = g.fft_h; a.fft_w = g.fft_w;
     a.M = g.M; a.T = g.T_cols; a.lds_pitch = g.lds_pitch;
@@ -324,5 +327,15 @@ inline ColsC2RArgs cols_c2r_args(const Geometry& g, const Tables& t, const Devic
 }
 
 inline int tiles_for(int ncols, int T) { return (ncols + T - 1) / T; }
+
+// Plan option "map_format" (fc_common.hpp: FC_MAP_*): why `value` cannot be set, or nullptr if it can.  Block-wise plans keep
+// fp32 maps: overlap-save blocks store rectangles at element offsets computed for 4-byte elements, and overlap-add sums in the maps.
+inline const char* map_format_error(long value, bool blockwise) {
+    if (value < FC_MAP_F32 || value > FC_MAP_BF16) return "map_format is 0 (fp32), 1 (fp16) or 2 (bfloat16)";
+    if (value != FC_MAP_F32 && blockwise)
+        return "map_format: 16-bit maps are not available on a block-wise plan (its blocks are stored at fp32 element offsets, or summed, in "
+               "the maps); use fp32 maps, or a one-pass plan (fftconv_plan_options.blockwise = 1)";
+    return nullptr;
+}
 
 }  // namespace fc

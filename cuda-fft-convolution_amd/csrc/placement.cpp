@@ -26,12 +26,13 @@ static int placement_auto_candidates(const fftconv_plan* p, size_t launch_map_by
 // freed.  The probes write into `out`, which the convolve that follows overwrites; they read the candidates as
 // allocated (the driver hands out zeroed memory).  Blocking (~70 ms), once per allocation: what FFTW calls
 // measuring at plan time.
-int tune_intermediate_placement(fftconv_plan* p, const Sink& sink, int n, int nbY, float* out, bool direct) {
+int tune_intermediate_placement(fftconv_plan* p, const Sink& sink, int n, int nbY, float* out, bool direct, int format) {
     const Geometry& g = p->g;
     p->Y.fresh = false;
     // (an overlap-save block's window is a rectangle inside the maps, not what the probes would write: never tuned)
     int k = sink.window ? 0 : (int)p->opt_tune_placement;
-    if (k < 0) k = placement_auto_candidates(p, (size_t)std::min(nbY, n) * g.map_elems() * sizeof(float));
+    const size_t eb = fc_map_elem_bytes(format);      // of what the output kernel writes
+    if (k < 0) k = placement_auto_candidates(p, (size_t)std::min(nbY, n) * g.map_elems() * eb);
     // (direct: the call's batches write to out + first_map * stride, and every batch's destination is probed -- an 18-GB map
     // buffer spans several placement regions; otherwise one launch into the one staging buffer)
     const size_t out_stride_per_map = direct ? p->out_elems() : 0;
@@ -72,7 +73,7 @@ int tune_intermediate_placement(fftconv_plan* p, const Sink& sink, int n, int nb
     auto launch = [&](const DevBuf<c32>& y) -> hipError_t {   // the output launches of the whole call
         for (int b = 0; b < nbatch; b++) {
             const int ny = std::min(nbY, n - b * nbY);
-            FastColsArgs fa = fast_cols_args(g, p->d, y.p, out + (size_t)b * nbY * out_stride_per_map, g.map_elems(), ny);
+            FastColsArgs fa = fast_cols_args(g, p->d, y.p, map_at(out, (size_t)b * nbY * out_stride_per_map, eb), g.map_elems(), ny, format);
             hipError_t e = launch_fast_cols(g.M, g.fast_cols.T, fa, p->num_cus, p->stream);
             if (e != hipSuccess) return e;
         }

@@ -16,10 +16,10 @@ namespace {
 // ---------------------------------------------------------------------------------------------------------
 struct CacheKey {
     int H, W, F, mkh, mkw, gpu;
-    int kernel_path, rows_group, max_transform, exact_window, blockwise;
+    int kernel_path, rows_group, max_transform, exact_window, blockwise, map_format;
     bool operator==(const CacheKey& o) const {
         return H == o.H && W == o.W && F == o.F && mkh == o.mkh && mkw == o.mkw && gpu == o.gpu && kernel_path == o.kernel_path &&
-               rows_group == o.rows_group && max_transform == o.max_transform && exact_window == o.exact_window && blockwise == o.blockwise;
+               rows_group == o.rows_group && max_transform == o.max_transform && exact_window == o.exact_window && blockwise == o.blockwise && map_format == o.map_format;
     }
 };
 struct CacheEntry {
@@ -44,11 +44,12 @@ PlanCache& plan_cache() {
 }
 
 CacheKey cache_key(int H, int W, int F, int mkh, int mkw, int gpu, const fftconv_plan_options* o) {
-    CacheKey k{H, W, F, mkh, mkw, gpu, 0, 0, 0, 0, 0};
+    CacheKey k{H, W, F, mkh, mkw, gpu, 0, 0, 0, 0, 0, 0};
     if (o && o->struct_size >= kOptionsMinSize) {
         k.kernel_path = o->kernel_path; k.rows_group = o->rows_group <= 0 ? 0 : o->rows_group;
         k.max_transform = o->max_transform > 0 ? o->max_transform : 0; k.exact_window = o->exact_window != 0;
         k.blockwise = options_no_blockwise(o) ? 1 : 0;
+        k.map_format = options_map_format(o);
     }
     return k;
 }

@@ -43,6 +43,10 @@ inline bool options_no_blockwise(const fftconv_plan_options* o) {
 inline bool options_verbose(const fftconv_plan_options* o) {
     return o && o->struct_size >= offsetof(fftconv_plan_options, verbose) + sizeof(int) && o->verbose != 0;
 }
+// (appended after `verbose`: a struct_size without the field means 0 = fp32 maps)
+inline int options_map_format(const fftconv_plan_options* o) {
+    return o && o->struct_size >= offsetof(fftconv_plan_options, map_format) + sizeof(int) ? o->map_format : 0;
+}
 inline PlanTuning tuning_from(const fftconv_plan_options* o) {
     PlanTuning t;
     if (!o || o->struct_size < kOptionsMinSize) return t;
@@ -236,6 +240,11 @@ struct fftconv_plan {
     int out_h = 0, out_w = 0, off_h = 0, off_w = 0;
     DevBuf<float> OC;  // cropped maps staged for the copy-out
     size_t out_elems() const { return opt_region ? (size_t)out_h * out_w : g.map_elems(); }   // (block-wise plans: g holds the whole window)
+    // "map_format": element format of every result map (fc_common.hpp: FC_MAP_*; one-pass plans only).  The staging buffers O / OC
+    // stay arrays of float that are sized in bytes and addressed through map_at; the full-window buffer a crop reads is always fp32.
+    long opt_map_format = 0;
+    size_t elem_bytes() const { return fc_map_elem_bytes((int)opt_map_format); }
+    size_t out_map_bytes() const { return out_elems() * elem_bytes(); }
     DevBuf<float> O;   // output staging (pointer-array / host output)
     DevBuf<float> I;   // image staging (host input)
     PinBuf pin_img, pin_k, pin_out;   // pinned host staging of small host arrays (PinBuf above)
@@ -341,6 +350,14 @@ namespace fc {
 // the reference's debug prints (src/cudaConvolutionFFT.cu:60,68,100,114,240,258), behind plan option "verbose"
 #define FC_VERBOSE(p, ...) do { if ((p)->opt_verbose) { fprintf(stderr, "fftconv: " __VA_ARGS__); fputc('\n', stderr); } } while (0)
 
+// element `elems` of a map buffer whose elements are `elem_bytes` wide (the `float*` of a 16-bit map buffer is opaque)
+inline float* map_at(float* base, size_t elems, size_t elem_bytes) {
+    return reinterpret_cast<float*>(reinterpret_cast<char*>(base) + elems * elem_bytes);
+}
+inline const float* map_at(const float* base, size_t elems, size_t elem_bytes) { return map_at(const_cast<float*>(base), elems, elem_bytes); }
+// floats that hold `elems` map elements of that width
+inline size_t floats_for(size_t elems, size_t elem_bytes) { return (elems * elem_bytes + sizeof(float) - 1) / sizeof(float); }
+
 // where the maps of a group go
 struct Sink {
     float* packed = nullptr;        // device base, maps consecutive
@@ -384,7 +401,8 @@ int ring_finish(fftconv_plan* p, const Sink& sink);
 // ---- placement tuning (placement.cpp) ----
 // before the first launch of a group of n maps into a (re)allocated intermediate: times candidate allocations of it where the plan's
 // tune_placement option (or its automatic default) says so.  direct: the output kernel writes the caller's packed maps, from `out` on
-int tune_intermediate_placement(fftconv_plan* p, const Sink& sink, int n, int nbY, float* out, bool direct);
+// format: FC_MAP_* of what the output kernel writes at `out` (fp32 into the full-window staging of a cropped region)
+int tune_intermediate_placement(fftconv_plan* p, const Sink& sink, int n, int nbY, float* out, bool direct, int format);
 
 // ---- block-wise plans (blockwise.cpp) ----
 bool blocks_preferred(const Geometry& g, const fftconv_plan_options* options);

@@ -175,10 +175,10 @@ typedef struct fftconv_plan_info {
     int gpu_id;
     int exact_window;          /* 1 if transform == window: circular modulus equals the reference's */
     size_t spectrum_bytes;     /* size of the image spectrum buffer */
-    size_t map_bytes;          /* fft_h * fft_w * sizeof(float) */
+    size_t map_bytes;          /* fft_h * fft_w elements of the plan's "map_format": 4 bytes each (fp32), or 2 */
     size_t workspace_bytes;    /* device scratch currently held */
     int out_h, out_w;          /* size of every result map: the window, or the "output_region" chosen */
-    size_t out_map_bytes;      /* out_h * out_w * sizeof(float) */
+    size_t out_map_bytes;      /* out_h * out_w elements of the plan's "map_format": what a result buffer holds per map */
 } fftconv_plan_info;
 
 /* hip_stream: hipStream_t to run on (NULL = the device's default stream). */
@@ -224,6 +224,11 @@ typedef struct fftconv_plan_options {
     int verbose;        /* 1: the plan starts with option "verbose" on (the reference's compile-time `debug`,
                          *    src/cudaConvolutionFFT.cu:9), and a one-shot call prints where its time went
                          *    (fftconv_call_timing).  (Appended in 0.3; a struct_size without it means 0.) */
+    int map_format;     /* element format of every result map: 0 (default) fp32, 1 IEEE fp16, 2 bfloat16 -- plan option
+                         *    "map_format", which see; part of the key of the one-shot entries' plan cache.  With 1 or 2 every
+                         *    `float *` that names result maps in this header (out, out_device, the members of out[]) is an
+                         *    OPAQUE pointer to out_h x out_w 16-bit elements per map.  FFTCONV_ERR_INVALID_ARG where the planner
+                         *    would make the plan block-wise (`blockwise`).  (Appended in 0.4; a struct_size without it means 0.) */
 } fftconv_plan_options;
 int fftconv_plan_create_ex(fftconv_plan **plan, int data_h, int data_w, int feature_dim,
                            int max_kernel_h, int max_kernel_w, int gpu_id, void *hip_stream,
@@ -368,6 +373,15 @@ int fftconv_plan_synchronize(fftconv_plan *plan);
              there; 0 (default): launched at once.  Read-only "prepare_pending": 1 while such a request waits),
           "verbose" (1: the sizes and launch shapes of every stage go to stderr as the work is queued -- the
  *             reference's compile-time `debug` switch, src/cudaConvolutionFFT.cu:9,60,100,114,240,258; 0 (default) silent),
+ *          "map_format" (element format of the result maps: 0 (default) fp32, 1 IEEE fp16, 2 bfloat16.  The arithmetic is fp32
+ *             up to the store of the output kernel, which converts every value once: round to nearest even, subnormal results
+ *             kept, fp16 overflow to +-inf.  Every result buffer of the plan -- host or device, packed or one pointer per map,
+ *             whatever the "output_region" -- then holds out_h x out_w 16-bit elements per map in the same column-major
+ *             order, plan_info.map_bytes / out_map_bytes count 2 bytes per element, and the `float *` of the signatures is an
+ *             opaque pointer.  Half the map memory and half the bytes of a host-output call; the output kernel moves 8C + 2P
+ *             bytes per map instead of 8C + 4P.  One-pass plans only: on a block-wise plan ("blockwise" > 0) a
+ *             non-zero value fails with FFTCONV_ERR_INVALID_ARG -- its blocks are stored at fp32 element offsets, or summed,
+ *             in the maps.  Also fftconv_plan_options.map_format; changing it forgets prepared kernels),
  *          "flip_kernels" (1: every kernel is flipped along h and w on the device before it is
  *             transformed, i.e. the plan correlates -- the "Flip Kernel (Required)" step of
  *             demoCudaConvolutionFFT.m:63-69 done here instead of in MATLAB; the reference keeps a

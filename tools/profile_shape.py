@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""Per-kernel HIP-event times of one device-resident step for arbitrary sizes: profile_shape.py H W K [filters] [F]"""
+"""Per-kernel HIP-event times of one device-resident step for arbitrary sizes: profile_shape.py H W K [filters] [F]
+Environment switches: EXACT=1 (exact_window plan), ONE_PASS=1 (never block-wise), DYN=0/1/2 (dynamic_tiles), FORMAT=1/2 (plan
+option map_format: fp16 / bf16 result maps; 0 or unset: fp32)"""
 import os, sys, time
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -10,6 +12,7 @@ n = int(sys.argv[4]) if len(sys.argv) > 4 else 64
 F = int(sys.argv[5]) if len(sys.argv) > 5 else 1
 opts = {"exact_window": 1} if os.environ.get("EXACT") else None
 if os.environ.get("ONE_PASS"): opts = dict(opts or {}, blockwise=1)      # never block-wise (A/B of the overlap-save blocks)
+FORMAT = int(os.environ.get("FORMAT") or 0)      # element format of the maps (A/B of the 16-bit output path)
 dev = torch.device("cuda", 0)
 rng = np.random.default_rng(1)
 img = torch.from_numpy(rng.random((F, W, H), dtype=np.float32)).to(dev)
@@ -17,7 +20,8 @@ ker = torch.from_numpy(rng.random((n, F, K, K), dtype=np.float32)).to(dev)
 with fc.Plan(H, W, F, K, K, options=opts) as p:
     i = p.info
     if os.environ.get("DYN"): p.set_option("dynamic_tiles", int(os.environ["DYN"]))      # tile queue of the column kernels on / off (A/B)
-    out = torch.empty((n, i.fft_w, i.fft_h), dtype=torch.float32, device=dev)
+    if FORMAT: p.set_option("map_format", FORMAT)
+    out = torch.empty((n, i.fft_w, i.fft_h), dtype=torch.int16 if FORMAT else torch.float32, device=dev)
     def step():
         p.set_image_device(img.data_ptr()); p.convolve_packed_device(n, ker.data_ptr(), K, K, out.data_ptr())
     for _ in range(30): step()
@@ -30,6 +34,6 @@ with fc.Plan(H, W, F, K, K, options=opts) as p:
     for _ in range(5): step()
     torch.cuda.synchronize()
     pr = p.profile(reset=True)
-    print("%dx%d K=%d F=%d n=%d window %dx%d transform %dx%d%s spec %d: %.1f us/step  %.1f Gpx/s | " % (H, W, K, F, n, i.fft_h, i.fft_w, i.transform_h, i.transform_w,
+    print("%s maps " % ("fp32", "fp16", "bf16")[FORMAT] + "%dx%d K=%d F=%d n=%d window %dx%d transform %dx%d%s spec %d: %.1f us/step  %.1f Gpx/s | " % (H, W, K, F, n, i.fft_h, i.fft_w, i.transform_h, i.transform_w,
           (" x%d blocks" % p.get_option("blockwise")) if p.get_option("blockwise") else "", p.get_option("specialised_kernels"), dt * 1e6, n * i.fft_h * i.fft_w / dt / 1e9) +
           "  ".join("%s %.1f us x%d" % (k, v["ms"] / max(1, v["launches"]) * 1e3, v["launches"] // 5) for k, v in pr.items()))

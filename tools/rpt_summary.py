@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Register / spill / occupancy table of every kernel from the build's csrc/*.rpt files
 (hipcc -Rpass-analysis=kernel-resource-usage, written by csrc/Makefile).
-usage: rpt_summary.py [--all] [substring ...]     (default: kernels that spill or use scratch)"""
+usage: rpt_summary.py [--all] [substring ...]     (default: kernels that spill or use scratch)
+e.g. rpt_summary.py --all k_fast_cols16 k_cols_c2r16 k_crop_maps16 k_pad_maps16     (the 16-bit-map kernels, plan option "map_format")"""
 import glob, os, re, subprocess, sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
