@@ -120,7 +120,8 @@ EXPORTED_SYMBOLS = (
     "fftconv_plan_use_spectrum_buffer", "fftconv_plan_export_spectrum", "fftconv_plan_import_spectrum",
     "fftconv_plan_convolve", "fftconv_plan_convolve_packed", "fftconv_plan_prepare_kernels_packed",
     "fftconv_plan_synchronize", "fftconv_plan_set_stream",
-    "fftconv_plan_set_option", "fftconv_plan_get_option", "fftconv_plan_get_profile", "fftconv_fft_data", "fftconv_conv_fft_data",
+    "fftconv_plan_set_option", "fftconv_plan_set_output_rect", "fftconv_plan_get_option", "fftconv_plan_get_profile",
+    "fftconv_fft_data", "fftconv_conv_fft_data",
     "fftconv_multi_create", "fftconv_multi_destroy", "fftconv_multi_set_image", "fftconv_multi_import_spectrum",
     "fftconv_multi_convolve", "fftconv_multi_set_option", "fftconv_multi_get_option",
     "fftconv_multi_shard", "fftconv_multi_size", "fftconv_multi_plan", "fftconv_convolution_fft_multi",
@@ -191,6 +192,7 @@ def load_library():
     lib.fftconv_plan_synchronize.argtypes = [vp]
     lib.fftconv_plan_set_stream.argtypes = [vp, vp]
     lib.fftconv_plan_set_option.argtypes = [vp, ctypes.c_char_p, ctypes.c_long]
+    lib.fftconv_plan_set_output_rect.argtypes = [vp, ci, ci, ci, ci]
     lib.fftconv_plan_get_option.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_long)]
     lib.fftconv_plan_get_profile.argtypes = [vp, ctypes.POINTER(Profile), ci]
     lib.fftconv_fft_data.argtypes = [vp, ci, ci, ci, ci, ci, ci, ctypes.POINTER(vp)]
@@ -473,6 +475,12 @@ class Plan:
 
     def set_option(self, name, value):
         _check(self._lib.fftconv_plan_set_option(self._h, name.encode(), int(value)))
+        _check(self._lib.fftconv_plan_get_info(self._h, ctypes.byref(self.info)))
+
+    def set_output_rect(self, off_h, off_w, out_h, out_w):
+        """every result map becomes rows [off_h, off_h + out_h) of columns [off_w, off_w + out_w) of the FFT_H x FFT_W window
+        (dense, column-major); info.out_h / out_w / out_map_bytes follow, option "output_region" then reads 5"""
+        _check(self._lib.fftconv_plan_set_output_rect(self._h, int(off_h), int(off_w), int(out_h), int(out_w)))
         _check(self._lib.fftconv_plan_get_info(self._h, ctypes.byref(self.info)))
 
     def get_option(self, name):

@@ -182,6 +182,13 @@ struct FastColsArgs {
     // element format of the maps (fc_common.hpp: FC_MAP_*).  Read by the 16-bit instantiations only (OUT16 below), where it
     // tells fp16 from bf16; the fp32 instantiations never look at it.
     int out_format;
+    // RECT instantiations only (plan entry fftconv_plan_set_output_rect; fast_paths.hpp: fast_cols_rect_launch_shape fills these
+    // in): the maps are the dense rectangle rows [h_lo, fft_h) of columns [rect_w_lo, rect_w_lo + rect_w_n) of the window, any
+    // parity of every bound: row h of column w at out + (w - rect_w_lo) * out_pitch + (h - h_lo), out_pitch = fft_h - h_lo.
+    // The launch covers the tiles that hold a column of the rectangle (w_first / tiles_per_kernel); rect_wide: every row pair
+    // (2n, 2n + 1) of the rectangle is whole and lands on an address aligned for the pair (h_lo, the pitch and the element
+    // offset of `out` all even), so a pair goes out in one store as in the plain kernel; 0: one element per store.
+    int rect_w_lo, rect_w_n, rect_wide;
 };
 
 template <class C>
@@ -258,8 +265,14 @@ FC_HD int pair_of_unit(int u) {
 // OUT16: the maps hold 16-bit elements (g.out_format: fp16 or bf16, uniform over the launch).  Only the store of C4 differs: a
 // thread's complex value is rows 2n, 2n + 1 of a column, converted and stored as ONE 32-bit word (out_pitch and h_lo are even:
 // the word is aligned).  A template parameter for the same reason as DYN: the fp32 kernel keeps its code and its registers.
-template <class C, bool TILED, bool SLICED = false, bool DYN = false, bool OUT16 = false, class Ctx>
+// RECT (tiled intermediate, unsliced): the maps are a dense rectangle of the window with bounds of any parity (FastColsArgs:
+// rect_*).  Again only C4 differs: columns of an edge tile outside the rectangle are neither transformed in stage 1 nor
+// stored, and a store is never wider than its address is known to be aligned -- the pair store where g.rect_wide says every
+// pair is whole and aligned (uniform over the launch), element stores otherwise (a pair then straddles two destination
+// words, and the first / last stored row of a column may be half a pair).
+template <class C, bool TILED, bool SLICED = false, bool DYN = false, bool OUT16 = false, bool RECT = false, class Ctx>
 FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int nwg) {
+    static_assert(!RECT || (TILED && !SLICED), "the rectangle store exists for unsliced launches on the tiled intermediate");
     static_assert(!SLICED || TILED, "column slices exist for the tiled intermediate only");
     static_assert(!(SLICED && DYN), "the sliced tail round is dealt statically");
     static_assert(!SLICED || (C::T & (C::T - 1)) == 0, "column slices: the tile width must be a power of two (slices of whole column pairs)");
@@ -552,8 +565,9 @@ FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int
         [[maybe_unused]] float* out = g.out + (size_t)kernel * g.out_kernel_stride;
         [[maybe_unused]] uint16_t* out16 = reinterpret_cast<uint16_t*>(g.out) + (size_t)kernel * g.out_kernel_stride;
         [[maybe_unused]] const bool out_bf16 = g.out_format == FC_MAP_BF16;
-        const int pair_lo = g.h_lo >> 1;                                 // complex pairs [pair_lo, pair_lo + nout) of a column are stored
-        const unsigned nout = (unsigned)((g.fft_h - g.h_lo) >> 1);
+        [[maybe_unused]] const int pair_lo = g.h_lo >> 1;                // complex pairs [pair_lo, pair_lo + nout) of a column are stored
+        [[maybe_unused]] const unsigned nout = (unsigned)((g.fft_h - g.h_lo) >> 1);
+        [[maybe_unused]] const unsigned nrows = (unsigned)(g.fft_h - g.h_lo);   // RECT: rows [h_lo, h_lo + nrows) of a column are stored
         ctx.phase([&](int t, [[maybe_unused]] State& st) {
             // the next tile's gather (issued in C1) has had two stages to arrive: take it off the
             // memory counter now, so that landing it does not wait for the stores below
@@ -575,6 +589,7 @@ FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int
                 const int idx = t + NT * r;
                 bool mine1 = idx < C::NB1 * T;
                 if constexpr (SLICED) mine1 = mine1 && idx / C::NB1 >= cur_lo && idx / C::NB1 < cur_hi;
+                if constexpr (RECT) mine1 = mine1 && (unsigned)(w0 + idx / C::NB1 - g.rect_w_lo) < (unsigned)g.rect_w_n;
                 if (mine1) {
                     const int col = idx / C::NB1, j = idx % C::NB1;
                     const c32* p = lds + col * LP + j;
@@ -587,7 +602,39 @@ FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int
                         v[c] = cmulc(p[c * C::S1], pw[c]);
                     });
                     Dft<R1, +1>::run(v);
-                    if constexpr (OUT16) {
+                    if constexpr (RECT) {
+                        // element (h - h_lo) of the column's run of the dense map; hr = row 2n of the pair, relative to h_lo
+                        const size_t cbase = (size_t)(w0 + col - g.rect_w_lo) * g.out_pitch;
+                        if constexpr (OUT16) {
+                            uint16_t* o = out16 + cbase;
+                            static_for<0, R1>([&](auto a_) {
+                                constexpr int a = decltype(a_)::value;
+                                const int hr = 2 * (j + a * m1) - g.h_lo;
+                                if ((unsigned)(hr + 1) <= nrows) {     // rows hr, hr + 1: at least one of them is in [0, nrows)
+                                    if (g.rect_wide) {
+                                        FC_STREAM_STORE4(o + hr, fc_pack_map16(v[a].x, v[a].y, out_bf16));
+                                    } else {
+                                        if (hr >= 0) FC_STREAM_STORE_ELEM(o + hr, fc_map16(v[a].x, out_bf16));
+                                        if ((unsigned)(hr + 1) < nrows) FC_STREAM_STORE_ELEM(o + hr + 1, fc_map16(v[a].y, out_bf16));
+                                    }
+                                }
+                            });
+                        } else {
+                            float* o = out + cbase;
+                            static_for<0, R1>([&](auto a_) {
+                                constexpr int a = decltype(a_)::value;
+                                const int hr = 2 * (j + a * m1) - g.h_lo;
+                                if ((unsigned)(hr + 1) <= nrows) {     // rows hr, hr + 1: at least one of them is in [0, nrows)
+                                    if (g.rect_wide) {
+                                        FC_STREAM_STORE(reinterpret_cast<c32*>(o + hr), v[a]);
+                                    } else {
+                                        if (hr >= 0) FC_STREAM_STORE_ELEM(o + hr, v[a].x);
+                                        if ((unsigned)(hr + 1) < nrows) FC_STREAM_STORE_ELEM(o + hr + 1, v[a].y);
+                                    }
+                                }
+                            });
+                        }
+                    } else if constexpr (OUT16) {
                         uint32_t* o = reinterpret_cast<uint32_t*>(out16 + (size_t)(w0 + col) * g.out_pitch);
                         static_for<0, R1>([&](auto a_) {
                             constexpr int a = decltype(a_)::value;

@@ -489,6 +489,37 @@ inline void fast_cols_visit_variant(FastColsVariant v, F&& f) {
     else f(no{}, no{}, no{});
 }
 
+// Rectangle store (fast_cols.hpp: RECT; plan entry fftconv_plan_set_output_rect): the output kernel writes the dense maps of
+// rows [off_h, off_h + out_h) of columns [off_w, off_w + out_w) of the window itself.  Instantiated for the tiled intermediate,
+// unsliced, static deal and dynamic queue.  Two configurations are NOT built, because their rectangle kernels would spill
+// registers (M = 544: 10-12 VGPRs where the plain kernel spills none; M = 2080: one more than the plain kernel's 4 with 16-bit
+// maps -- the own kernels of the 1088 / 4160 windows, which only exact_window plans run): their plans crop the staged
+// window, as every plan without the specialised kernel does.
+constexpr bool fast_cols_rect_built(int M) { return M != 544 && M != 2080; }
+inline bool fast_cols_rect_available(int M, bool y_tiled) { return y_tiled && fast_cols_lookup(M).ok && fast_cols_rect_built(M); }
+// The launch of nk rectangle maps: `a` as fast_cols_args gives it for nk whole windows, with `out` the first dense
+// rectangle map and out_kernel_stride the elements between two of them (>= out_h * out_w).  Only the tiles that hold a column
+// of the rectangle are launched (the others are never gathered or transformed); the pair store is kept where every pair of
+// rows is whole and aligned -- off_h, out_h, the map stride and the element offset of `out` from a pair boundary all even --
+// which is uniform over the launch.  The rectangle must lie inside the window (pipeline.hpp: output_rect_error).
+inline FastColsShape fast_cols_rect_launch_shape(int T, const FastColsArgs& a, int off_h, int off_w, int out_h, int out_w, int want) {
+    FastColsShape r{a.queue ? FastColsVariant::TILED_DYN : FastColsVariant::TILED, a, 0};
+    const int nk = a.tiles_per_kernel > 0 ? a.ntiles / a.tiles_per_kernel : 0;
+    const int tile_lo = off_w / T, tile_hi = (off_w + out_w + T - 1) / T;
+    r.a.h_lo = off_h; r.a.fft_h = off_h + out_h; r.a.out_pitch = out_h;
+    r.a.w_first = tile_lo * T; r.a.tiles_per_kernel = tile_hi - tile_lo; r.a.ntiles = r.a.tiles_per_kernel * nk;
+    r.a.rect_w_lo = off_w; r.a.rect_w_n = out_w;
+    const size_t elem = fc_map_elem_bytes(a.out_format);
+    r.a.rect_wide = (off_h % 2 == 0 && out_h % 2 == 0 && a.out_kernel_stride % 2 == 0 && reinterpret_cast<uintptr_t>(a.out) % (2 * elem) == 0) ? 1 : 0;
+    r.a.tail_first = r.a.tail_tiles = r.a.slice_shift = 0;
+    r.grid = r.a.ntiles < want ? r.a.ntiles : want;
+    if (r.variant == FastColsVariant::TILED_DYN) {
+        r.a.queue_shift = 0;
+        while ((16 << r.a.queue_shift) <= r.grid) r.a.queue_shift++;
+    }
+    return r;
+}
+
 struct FastColsTables {
     Plan1D plan;                   // radices (R1, R2, R3)
     std::vector<c32> tw1, tw2;

@@ -57,6 +57,14 @@
 #define FC_STREAM_STORE4(ptr, val) (*reinterpret_cast<uint32_t*>(ptr) = (uint32_t)(val))
 #endif
 
+// The same for ONE map element (a float, or a 16-bit value): the rectangle store of the output kernel where a pair of rows is
+// not known to be aligned for a wider store.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define FC_STREAM_STORE_ELEM(ptr, val) __builtin_nontemporal_store((val), (ptr))
+#else
+#define FC_STREAM_STORE_ELEM(ptr, val) (*(ptr) = (val))
+#endif
+
 // 16-byte load of data this kernel reads once.  A plain load, not a streaming (nontemporal) one:
 // the output kernel gathers 64-byte halves of 128-byte lines whose other halves are gathered by a
 // neighbouring CU of the same XCD, and a plain load keeps the line in that XCD's L2 for it (27.4

@@ -151,7 +151,9 @@ struct Delivery {
     // a region other than the whole window: the output kernel writes the window into O, a crop
     // kernel compacts the region into the destination (the caller's packed buffer or the staging OC)
     bool cropped = false;
-    DevBuf<float>* stage = nullptr;    // staged routes: where the maps wait for their copy (OC when cropped, else O)
+    // the caller's rectangle, stored by the output kernel itself (fftconv_plan::rect_direct): no full window, no crop, no O
+    bool rect = false;
+    DevBuf<float>* stage = nullptr;    // staged routes: where the maps wait for their copy (OC for region maps, else O)
     size_t oe = 0;                     // elements per delivered map
     size_t eb = sizeof(float);         // bytes per element ("map_format")
     size_t mb() const { return oe * eb; }
@@ -162,8 +164,9 @@ struct Delivery {
 int plan_delivery(fftconv_plan* p, const Sink& sink, int nbY, Delivery& d) {
     const Geometry& g = p->g;
     if (sink.window && !g.fast_cols.ok) return api_fail(FFTCONV_ERR_INVALID_ARG, "an output window needs the specialised output kernel");
-    d.cropped = p->opt_region != 0;
-    d.stage = d.cropped ? &p->OC : &p->O;
+    d.rect = !sink.window && p->rect_direct();
+    d.cropped = p->opt_region != 0 && !d.rect;
+    d.stage = (d.cropped || d.rect) ? &p->OC : &p->O;
     d.oe = p->out_elems();
     d.eb = p->elem_bytes();
     d.kernel_format = d.cropped ? FC_MAP_F32 : (int)p->opt_map_format;
@@ -204,11 +207,31 @@ int launch_spectral_rows_batch(fftconv_plan* p, const c32* a, int kw, int ny) {
 
 const char* const kMapFormatNames[] = {"fp32", "fp16", "bf16"};      // FC_MAP_*
 
+}  // namespace
+
+namespace fc {
+// the launch that stores ny maps of the plan's rectangle (fftconv_plan::rect_direct) from the intermediate y, dense from `out` on
+FastColsShape output_rect_shape(const fftconv_plan* p, const c32* y, float* out, int ny, int format) {
+    const Geometry& g = p->g;
+    const FastColsArgs fa = fast_cols_args(g, p->d, y, out, p->out_elems(), ny, format);
+    return fast_cols_rect_launch_shape(g.fast_cols.T, fa, p->off_h, p->off_w, p->out_h, p->out_w,
+                                       persistent_want(g.fast_cols.lds_bytes, g.fast_cols.NT, p->num_cus));
+}
+}  // namespace fc
+
+namespace {
+
 // output columns of ny maps: Y transformed along h into the maps at obase (or into the window of an overlap-save block)
-int launch_output_cols(fftconv_plan* p, const OutWindow* win, float* obase, int ny, int format) {
+// (rect: the dense maps of the plan's rectangle, stored by the output kernel itself -- Delivery::rect)
+int launch_output_cols(fftconv_plan* p, const OutWindow* win, float* obase, int ny, int format, bool rect) {
     const Geometry& g = p->g;
     if (int rc = p->prof_begin(PK_OUT_COLS, ny)) return rc;
-    if (g.fast_cols.ok) {
+    if (rect) {
+        const FastColsShape sh = output_rect_shape(p, p->Y.p, obase, ny, format);
+        FC_VERBOSE(p, "output kernel: tiled rectangle, %d workgroups, %s elements, rows [%d, %d) of columns [%d, %d)", sh.grid, kMapFormatNames[format],
+                   p->off_h, p->off_h + p->out_h, p->off_w, p->off_w + p->out_w);
+        HIP_TRY(launch_fast_cols_rect(g.M, g.fast_cols.T, sh, p->stream));
+    } else if (g.fast_cols.ok) {
         FastColsArgs fa = fast_cols_args(g, p->d, p->Y.p, obase, win ? win->map_stride : g.map_elems(), ny, format);
         if (win) {
             fa.h_lo = win->h_lo; fa.fft_h = win->h_hi; fa.w_first = win->w_first; fa.out_pitch = win->pitch;
@@ -306,7 +329,7 @@ int run_group_impl(fftconv_plan* p, int n, const float* dk, int kh, int kw, cons
                 if (int rc = ring_claim_staging(p, &buf)) return rc;
             float* dest = sink.window ? sink.window->base + (size_t)first * sink.window->map_stride            // where the maps of this batch go
                           : d.staged() ? map_at(d.stage->p, (size_t)buf * nbY * d.oe, d.eb) : map_at(sink.packed, (size_t)first * d.oe, d.eb);
-            if (int rc = launch_output_cols(p, sink.window, d.cropped ? p->O.p : dest, ny, d.kernel_format)) return rc;
+            if (int rc = launch_output_cols(p, sink.window, d.cropped ? p->O.p : dest, ny, d.kernel_format, d.rect)) return rc;
             if (d.cropped)
                 if (int rc = launch_region(p, p->O.p, dest, ny, p->stream)) return rc;
             if (int rc = deliver_batch(p, d, sink, first, ny, buf, dest)) return rc;
@@ -350,6 +373,7 @@ const LongOption kLongOptions[] = {
     {"tuned_candidates", &fftconv_plan::tuned_candidates, 0, 0, OPT_GET_ONLY},
     {"tuned_best", &fftconv_plan::tuned_best, 0, 0, OPT_GET_ONLY},
     {"output_region", &fftconv_plan::opt_region, 0, 0, OPT_GET_ONLY},
+    {"rect_store", &fftconv_plan::opt_rect_store, 0, 1, OPT_BOOL},
     {"dynamic_tiles", &fftconv_plan::opt_dynamic_tiles, 0, 0, OPT_GET_ONLY},
     {"defer_prepare", &fftconv_plan::opt_defer_prepare, 0, 0, OPT_GET_ONLY},
 };
@@ -366,7 +390,10 @@ namespace fc {
 int launch_region(const fftconv_plan* p, const float* src, float* dst, int nmaps, hipStream_t s) {
     const Geometry& g = p->g;      // (block-wise plans: g holds the whole window)
     const int format = (int)p->opt_map_format;      // of dst; src is fp32
-    FC_VERBOSE(p, "output region %ld: %d maps %s from the fp32 window into %d x %d %s maps", p->opt_region, nmaps, p->opt_region == 4 ? "padded" : "cropped",
+    if (p->opt_region == 5)
+        FC_VERBOSE(p, "output rectangle: %d maps cropped from the fp32 window, rows [%d, %d) of columns [%d, %d), into %s maps", nmaps, p->off_h,
+                   p->off_h + p->out_h, p->off_w, p->off_w + p->out_w, kMapFormatNames[format]);
+    else FC_VERBOSE(p, "output region %ld: %d maps %s from the fp32 window into %d x %d %s maps", p->opt_region, nmaps, p->opt_region == 4 ? "padded" : "cropped",
                p->out_h, p->out_w, kMapFormatNames[format]);
     if (p->opt_region == 4) HIP_TRY(launch_pad_maps(src, g.fft_h, g.fft_w, g.map_elems(), dst, p->out_h, p->out_w, p->out_elems(), nmaps, s, format));
     else HIP_TRY(launch_crop_maps(src, g.fft_h, g.map_elems(), dst, p->out_h, p->out_w, p->out_elems(), p->off_h, p->off_w, nmaps, s, format));
@@ -887,7 +914,7 @@ int fftconv_plan_set_option(fftconv_plan* plan, const char* name, long value) {
     if (!plan || !name) return api_fail(FFTCONV_ERR_INVALID_ARG, "NULL argument");
     if (!strcmp(name, "map_format"))
         if (const char* why = map_format_error(value, plan->tiled != nullptr)) return api_fail(FFTCONV_ERR_INVALID_ARG, "%s", why);
-    if (plan->tiled && strcmp(name, "output_region")) {      // block-wise: options act on the block plan ("output_region": on this one, below)
+    if (plan->tiled && strcmp(name, "output_region") && strcmp(name, "rect_store")) {      // block-wise: options act on the block plan ("output_region", "rect_store": on this one, below)
         if (!strcmp(name, "verbose")) plan->opt_verbose = value != 0;
         return fftconv_plan_set_option(plan->tiled->sub, name, value);
     }
@@ -949,6 +976,7 @@ int fftconv_plan_set_option(fftconv_plan* plan, const char* name, long value) {
         else if (value == 2) { oh = g.H; ow = g.W; fh = (g.max_kh - 1) / 2; fw = (g.max_kw - 1) / 2; }
         else if (value == 3) { oh = g.H - g.max_kh + 1; ow = g.W - g.max_kw + 1; fh = g.max_kh - 1; fw = g.max_kw - 1; }
         else if (value == 4) { oh = fft_size_pow2(g.H + g.max_kh - 1); ow = fft_size_pow2(g.W + g.max_kw - 1); }
+        else if (value == 5) return api_fail(FFTCONV_ERR_INVALID_ARG, "output_region 5 (a rectangle of the window) is set with fftconv_plan_set_output_rect");
         else if (value != 0) return api_fail(FFTCONV_ERR_INVALID_ARG, "output_region is 0 (window), 1 (full), 2 (same), 3 (valid) or 4 (pow2 window)");
         if (oh < 1 || ow < 1) return api_fail(FFTCONV_ERR_INVALID_ARG, "output_region %ld is empty for %dx%d data and %dx%d kernels", value, g.H, g.W, g.max_kh, g.max_kw);
         if (int rc = use_device(plan)) return rc;
@@ -962,8 +990,27 @@ int fftconv_plan_set_option(fftconv_plan* plan, const char* name, long value) {
     return api_fail(FFTCONV_ERR_INVALID_ARG, "unknown option '%s'", name);
 }
 
+int fftconv_plan_set_output_rect(fftconv_plan* plan, int off_h, int off_w, int out_h, int out_w) {
+    if (!plan) return api_fail(FFTCONV_ERR_INVALID_ARG, "plan is NULL");
+    const Geometry& g = plan->g;      // (block-wise plans: the whole image's window)
+    if (const char* why = output_rect_error(off_h, off_w, out_h, out_w, g.fft_h, g.fft_w))
+        return api_fail(FFTCONV_ERR_INVALID_ARG, "%s (rows [%d, %d) of columns [%d, %d) asked of the %d x %d window)", why, off_h, off_h + out_h, off_w,
+                        off_w + out_w, g.fft_h, g.fft_w);
+    if (int rc = use_device(plan)) return rc;
+    HIP_TRY(hipStreamSynchronize(plan->stream));
+    plan->release_ring();          // sized for the map bytes
+    plan->opt_region = 5; plan->out_h = out_h; plan->out_w = out_w; plan->off_h = off_h; plan->off_w = off_w;
+    return 0;
+}
+
 int fftconv_plan_get_option(fftconv_plan* plan, const char* name, long* value) {
     if (!plan || !name || !value) return api_fail(FFTCONV_ERR_INVALID_ARG, "null argument");
+    // the caller's rectangle (fftconv_plan_set_output_rect), read-only: its offsets (0 without one), and whether the output
+    // kernel stores it itself with the plan's current settings
+    if (!strcmp(name, "rect_off_h")) { *value = plan->opt_region == 5 ? plan->off_h : 0; return 0; }
+    if (!strcmp(name, "rect_off_w")) { *value = plan->opt_region == 5 ? plan->off_w : 0; return 0; }
+    if (!strcmp(name, "rect_direct")) { *value = plan->rect_direct() ? 1 : 0; return 0; }
+    if (!strcmp(name, "rect_store")) { *value = plan->opt_rect_store; return 0; }
     if (!strcmp(name, "blockwise")) { *value = plan->tiled ? plan->tiled->nblk : 0; return 0; }   // read-only: number of blocks (0 = one pass)
     if (!strcmp(name, "overlap_save")) { *value = plan->tiled && plan->tiled->save ? 1 : 0; return 0; }   // read-only: blocks stored by the output kernel (1) or summed (0)
     if (plan->tiled && strcmp(name, "output_region")) return fftconv_plan_get_option(plan->tiled->sub, name, value);

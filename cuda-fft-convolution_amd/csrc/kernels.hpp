@@ -38,6 +38,8 @@ hipError_t launch_fast_rows_multi(int L, int nz2, const FastRowsArgs& a, int row
 // how many workgroups of that kernel a CU holds at once (hipOccupancyMaxActiveBlocksPerMultiprocessor)
 hipError_t fast_rows_multi_wgs_per_cu(int L, int nz2, const FastRowsArgs& a, int* wgs_per_cu);
 hipError_t launch_fast_cols(int M, int T, const FastColsArgs& a, int num_cus, hipStream_t s);
+// the rectangle store of the output kernel (fast_cols.hpp: RECT): `shape` from fast_cols_rect_launch_shape (fast_paths.hpp)
+hipError_t launch_fast_cols_rect(int M, int T, const FastColsShape& shape, hipStream_t s);
 hipError_t launch_fast_cols_fwd(int M, int T, bool pruned, const FastColsFwdArgs& a, int num_cus, hipStream_t s);
 // image columns (full variant) and kernel columns (pruned or full) of one plan in ONE launch (kernels_cols_fwd.hip)
 hipError_t launch_fast_cols_fwd_pair(int M, int T, const FastColsFwdArgs& image, const FastColsFwdArgs& kernels, bool kernels_pruned,
@@ -54,6 +56,9 @@ template <int G> GroupResult fast_rows_multi_wgs_per_cu_group(int L, int nz2, co
 template <int G> GroupResult launch_fast_cols_group(int M, int T, const FastColsArgs& a, int num_cus, hipStream_t s);
 // (the 16-bit-map instantiations of the same configurations: kernels_cols16_g<G>.hip)
 template <int G> GroupResult launch_fast_cols16_group(int M, int T, const FastColsArgs& a, int num_cus, hipStream_t s);
+// (the rectangle store, fp32 and 16-bit maps: kernels_cols_rect_g<G>.hip, kernels_cols_rect16_g<G>.hip)
+template <int G> GroupResult launch_fast_cols_rect_group(int M, int T, const FastColsShape& shape, hipStream_t s);
+template <int G> GroupResult launch_fast_cols_rect16_group(int M, int T, const FastColsShape& shape, hipStream_t s);
 template <int G> GroupResult launch_fast_cols_fwd_group(int M, int T, bool pruned, const FastColsFwdArgs& a, int num_cus, hipStream_t s);
 template <int G> GroupResult launch_fast_cols_fwd_pair_group(int M, int T, const FastColsFwdArgs& image, const FastColsFwdArgs& kernels,
                                                              bool kernels_pruned, int num_cus, hipStream_t s);

@@ -338,4 +338,13 @@ inline const char* map_format_error(long value, bool blockwise) {
     return nullptr;
 }
 
+// fftconv_plan_set_output_rect: why rows [off_h, off_h + out_h) of columns [off_w, off_w + out_w) are not a rectangle of the
+// fft_h x fft_w window, or nullptr if they are.  (Sums in 64 bits: the arguments are any ints.)
+inline const char* output_rect_error(long off_h, long off_w, long out_h, long out_w, int fft_h, int fft_w) {
+    if (out_h < 1 || out_w < 1) return "output rectangle: out_h and out_w must be at least 1";
+    if (off_h < 0 || off_w < 0) return "output rectangle: off_h and off_w must not be negative";
+    if (off_h + out_h > fft_h || off_w + out_w > fft_w) return "output rectangle: it must lie inside the window";
+    return nullptr;
+}
+
 }  // namespace fc

@@ -32,7 +32,10 @@ int tune_intermediate_placement(fftconv_plan* p, const Sink& sink, int n, int nb
     // (an overlap-save block's window is a rectangle inside the maps, not what the probes would write: never tuned)
     int k = sink.window ? 0 : (int)p->opt_tune_placement;
     const size_t eb = fc_map_elem_bytes(format);      // of what the output kernel writes
-    if (k < 0) k = placement_auto_candidates(p, (size_t)std::min(nbY, n) * g.map_elems() * eb);
+    // (a plan whose output kernel stores the caller's rectangle itself -- rect_direct -- is probed with exactly that launch:
+    // `out` is sized for the dense rectangles, full-window probes would overrun it)
+    const bool rect = !sink.window && p->rect_direct();
+    if (k < 0) k = placement_auto_candidates(p, (size_t)std::min(nbY, n) * (rect ? p->out_elems() : g.map_elems()) * eb);
     // (direct: the call's batches write to out + first_map * stride, and every batch's destination is probed -- an 18-GB map
     // buffer spans several placement regions; otherwise one launch into the one staging buffer)
     const size_t out_stride_per_map = direct ? p->out_elems() : 0;
@@ -73,8 +76,14 @@ int tune_intermediate_placement(fftconv_plan* p, const Sink& sink, int n, int nb
     auto launch = [&](const DevBuf<c32>& y) -> hipError_t {   // the output launches of the whole call
         for (int b = 0; b < nbatch; b++) {
             const int ny = std::min(nbY, n - b * nbY);
-            FastColsArgs fa = fast_cols_args(g, p->d, y.p, map_at(out, (size_t)b * nbY * out_stride_per_map, eb), g.map_elems(), ny, format);
-            hipError_t e = launch_fast_cols(g.M, g.fast_cols.T, fa, p->num_cus, p->stream);
+            float* dest = map_at(out, (size_t)b * nbY * out_stride_per_map, eb);
+            hipError_t e;
+            if (rect) {
+                e = launch_fast_cols_rect(g.M, g.fast_cols.T, output_rect_shape(p, y.p, dest, ny, format), p->stream);
+            } else {
+                FastColsArgs fa = fast_cols_args(g, p->d, y.p, dest, g.map_elems(), ny, format);
+                e = launch_fast_cols(g.M, g.fast_cols.T, fa, p->num_cus, p->stream);
+            }
             if (e != hipSuccess) return e;
         }
         return hipSuccess;

@@ -236,8 +236,13 @@ struct fftconv_plan {
     long opt_flip_kernels = 0;
     // "output_region": which part of the padded window a map holds (MAX_KERNEL sizes K):
     // 0 window FFT_H x FFT_W (the reference), 1 full (DATA + K - 1), 2 same (DATA, centred), 3 valid (DATA - K + 1)
+    // 5: the caller's rectangle (fftconv_plan_set_output_rect): rows [off_h, off_h + out_h) of columns [off_w, off_w + out_w)
     long opt_region = 0;
     int out_h = 0, out_w = 0, off_h = 0, off_w = 0;
+    // "rect_store" 1: the specialised output kernel stores the rectangle of region 5 itself (fast_cols.hpp: RECT) where it can --
+    // rect_direct(); 0, and every plan it cannot serve: the window goes through the fp32 staging O and is cropped like regions 1-3
+    long opt_rect_store = 1;
+    bool rect_direct() const { return opt_region == 5 && opt_rect_store && !tiled && fast_cols_rect_available(g.M, g.y_tiled()); }
     DevBuf<float> OC;  // cropped maps staged for the copy-out
     size_t out_elems() const { return opt_region ? (size_t)out_h * out_w : g.map_elems(); }   // (block-wise plans: g holds the whole window)
     // "map_format": element format of every result map (fc_common.hpp: FC_MAP_*; one-pass plans only).  The staging buffers O / OC
@@ -385,6 +390,9 @@ int run_group(fftconv_plan* p, int n, const float* dk, int kh, int kw, const Sin
 // cyclic: the block plan of an overlap-save block-wise plan (PlanTuning::cyclic) -- never block-wise itself
 int plan_create_internal(fftconv_plan** plan, int data_h, int data_w, int feature_dim, int max_kernel_h, int max_kernel_w, int gpu_id,
                          void* hip_stream, const fftconv_plan_options* options, bool cyclic);
+
+// the launch that stores ny maps of the plan's rectangle (fftconv_plan::rect_direct) from the intermediate y, dense from `out` on
+FastColsShape output_rect_shape(const fftconv_plan* p, const c32* y, float* out, int ny, int format);
 
 // ---- host-output streaming (host_ring.cpp) ----
 // A streamed group (run_group, host maps of at least host_min_kb) has two staging buffers on the device: batch b is computed into

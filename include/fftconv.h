@@ -368,7 +368,13 @@ int fftconv_plan_synchronize(fftconv_plan *plan);
  *             DATA - K + 1, no zero padding involved; 4 "pow2 window" = fftconv_fft_size_pow2(DATA + K - 1)
  *             per dimension, the window the reference's unused computeFFTsize would give
  *             (src/cudaConvFFTData.h:67-94): the convolution in its top-left corner, zeros elsewhere.
- *             Result buffers then hold out_h x out_w floats (fftconv_plan_get_info)),
+ *             Result buffers then hold out_h x out_w floats (fftconv_plan_get_info).  Reads 5 after
+ *             fftconv_plan_set_output_rect, a rectangle of the caller's; setting 0..4 replaces the rectangle, 5 itself is
+ *             set through that entry only),
+ *          "rect_store" (1 (default): the output kernel stores the rectangle of fftconv_plan_set_output_rect itself where the
+ *             plan has the kernel for it; 0: the window goes through the fp32 staging and is cropped like regions 1-3.
+ *             Read-only beside it: "rect_direct" (1 if, with the plan's current settings, the output kernel will store the
+ *             rectangle itself), "rect_off_h" / "rect_off_w" (the rectangle's offsets; 0 without one)),
  *          "defer_prepare" (1: fftconv_plan_prepare_kernels_packed records its request instead of launching it, see
              there; 0 (default): launched at once.  Read-only "prepare_pending": 1 while such a request waits),
           "verbose" (1: the sizes and launch shapes of every stage go to stderr as the work is queued -- the
@@ -387,6 +393,18 @@ int fftconv_plan_synchronize(fftconv_plan *plan);
  *             demoCudaConvolutionFFT.m:63-69 done here instead of in MATLAB; the reference keeps a
  *             conjugate-product variant commented out, src/cudaConvFFTData.cuh:42-45,63). */
 int fftconv_plan_set_option(fftconv_plan *plan, const char *name, long value);
+/* Every result map of the plan becomes rows [off_h, off_h + out_h) of columns [off_w, off_w + out_w) of the FFT_H x FFT_W
+ * window, column-major and dense (pitch out_h), in the plan's "map_format", on every delivery route: a region of interest, a
+ * strip per consumer, or "same" / "valid" for kernels smaller than MAX_KERNEL.  out_h, out_w >= 1, offsets >= 0 and the
+ * rectangle inside the window, else FFTCONV_ERR_INVALID_ARG (the previous setting stays).  Acts like setting "output_region"
+ * (which then reads 5): the plan's stream is synchronised, and plan_info.out_h / out_w / out_map_bytes follow.  On a one-pass
+ * plan with the specialised output kernel and the tiled intermediate (kernel_path 0) that kernel stores the rectangle itself:
+ * only the column tiles that hold a column of it are transformed, nothing but the rectangle is written (8C + 4P' bytes per
+ * map for a rectangle of P' elements) and no full-window staging is allocated.  Every other plan -- generic or
+ * Bluestein output kernel, kernel_path 1 or 2, block-wise, option "rect_store" 0, and the two specialised transforms whose rectangle
+ * kernel is not built because it would spill registers (1088 and 4160 points along h: exact_window plans of the 1088- / 4160-row
+ * windows) -- computes the window and crops it; read-only option "rect_direct" tells which. */
+int fftconv_plan_set_output_rect(fftconv_plan *plan, int off_h, int off_w, int out_h, int out_w);
 /* Current value of an option, plus read-only ones: "tuned_candidates" (allocations tried by the last placement tuning)
  * and "tuned_best" (index of the one kept), "blockwise" (blocks of a block-wise plan, 0 = one pass), "overlap_save" (1: the blocks are stored by the output kernel),
  * "rows_slots_per_cu" (workgroups of the multi-map row kernel a CU holds at once: what the walk length is chosen for),

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Per-kernel HIP-event times of one device-resident step for arbitrary sizes: profile_shape.py H W K [filters] [F]
 Environment switches: EXACT=1 (exact_window plan), ONE_PASS=1 (never block-wise), DYN=0/1/2 (dynamic_tiles), FORMAT=1/2 (plan
-option map_format: fp16 / bf16 result maps; 0 or unset: fp32)"""
+option map_format: fp16 / bf16 result maps; 0 or unset: fp32), REGION=1..4 (plan option output_region), RECT=same | valid | off_h,off_w,out_h,out_w
+(fftconv_plan_set_output_rect: the "same" / "valid" rectangle of the K x K kernels, or any rectangle of the window), RECT_STORE=0/1 (plan
+option rect_store: 0 stages the window and crops the rectangle, the A/B partner of the output kernel's own rectangle store)"""
 import os, sys, time
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -21,7 +23,17 @@ with fc.Plan(H, W, F, K, K, options=opts) as p:
     i = p.info
     if os.environ.get("DYN"): p.set_option("dynamic_tiles", int(os.environ["DYN"]))      # tile queue of the column kernels on / off (A/B)
     if FORMAT: p.set_option("map_format", FORMAT)
-    out = torch.empty((n, i.fft_w, i.fft_h), dtype=torch.int16 if FORMAT else torch.float32, device=dev)
+    region = ""
+    if os.environ.get("REGION"):
+        p.set_option("output_region", int(os.environ["REGION"])); region = " output_region %s" % os.environ["REGION"]
+    if os.environ.get("RECT"):
+        r = os.environ["RECT"]
+        rect = ((K - 1) // 2, (K - 1) // 2, H, W) if r == "same" else (K - 1, K - 1, H - K + 1, W - K + 1) if r == "valid" else tuple(int(x) for x in r.split(","))
+        if os.environ.get("RECT_STORE"): p.set_option("rect_store", int(os.environ["RECT_STORE"]))
+        p.set_output_rect(*rect)
+        region = " rectangle %s (rect_direct %d)" % (rect, p.get_option("rect_direct"))
+    i = p.info
+    out = torch.empty((n, i.out_w, i.out_h), dtype=torch.int16 if FORMAT else torch.float32, device=dev)
     def step():
         p.set_image_device(img.data_ptr()); p.convolve_packed_device(n, ker.data_ptr(), K, K, out.data_ptr())
     for _ in range(30): step()
@@ -34,6 +46,6 @@ with fc.Plan(H, W, F, K, K, options=opts) as p:
     for _ in range(5): step()
     torch.cuda.synchronize()
     pr = p.profile(reset=True)
-    print("%s maps " % ("fp32", "fp16", "bf16")[FORMAT] + "%dx%d K=%d F=%d n=%d window %dx%d transform %dx%d%s spec %d: %.1f us/step  %.1f Gpx/s | " % (H, W, K, F, n, i.fft_h, i.fft_w, i.transform_h, i.transform_w,
+    print("%s maps " % ("fp32", "fp16", "bf16")[FORMAT] + "%dx%d K=%d F=%d n=%d window %dx%d%s transform %dx%d%s spec %d: %.1f us/step  %.1f Gpx/s | " % (H, W, K, F, n, i.fft_h, i.fft_w, region, i.transform_h, i.transform_w,
           (" x%d blocks" % p.get_option("blockwise")) if p.get_option("blockwise") else "", p.get_option("specialised_kernels"), dt * 1e6, n * i.fft_h * i.fft_w / dt / 1e9) +
           "  ".join("%s %.1f us x%d" % (k, v["ms"] / max(1, v["launches"]) * 1e3, v["launches"] // 5) for k, v in pr.items()))
