@@ -86,6 +86,25 @@ struct FastRowsArgs {
     unsigned long long* timeline;  // FC_ROWS_TIMELINE builds only: per-phase wall-clock stamps of one workgroup (else unused)
 };
 
+// Slot u = t + NT * ROUND of a phase with NB butterflies per row: the workgroup's row rr, the butterfly w within that row, and
+// whether the slot exists.  One row per workgroup (the lengths 2560 ... 6144, and 1088): rr = 0 and w = u, no division by NB and no row
+// arithmetic at all, and the bound is compared only in a round that can run past it -- index work the row kernel used to
+// repeat for every map (the vector unit that bounds it issues these as it does the butterflies).
+// (DIV: the general form whatever RPW.)
+template <int RPW, int NB, int NT, int ROUND, bool DIV = false>
+FC_HD bool row_slot(int u, int& rr, int& w) {
+    if constexpr (RPW == 1 && !DIV) {
+        rr = 0;
+        w = u;
+        if constexpr (NT * (ROUND + 1) <= NB) return true;
+        else return u < NB;
+    } else {
+        rr = u / NB;
+        w = u - rr * NB;
+        return rr < RPW;
+    }
+}
+
 // p[c] = w^c, c in [1, R)
 template <int R>
 FC_HD void power_chain(c32 w, c32 (&p)[R]) {
@@ -94,6 +113,20 @@ FC_HD void power_chain(c32 w, c32 (&p)[R]) {
     static_for<2, R>([&](auto c_) {
         constexpr int c = decltype(c_)::value;
         if constexpr (c % 2 == 0) p[c] = cmul(p[c / 2], p[c / 2]);
+        else p[c] = cmul(p[c - 1], w);
+    });
+}
+
+// The same chain from its even powers w^2, w^4, ... (even[k] = w^(2k + 2), taken from a power_chain of the same w): every
+// p[c] is the very product power_chain forms, so the two agree to the bit.  The odd powers hang off the kept ones one
+// product deep (power_chain: up to log2 R + 1 dependent products).
+template <int R>
+FC_HD void power_chain_from_even(c32 w, const c32* even, c32 (&p)[R]) {
+    p[0] = mk(1.f, 0.f);
+    if constexpr (R > 1) p[1] = w;
+    static_for<2, R>([&](auto c_) {
+        constexpr int c = decltype(c_)::value;
+        if constexpr (c % 2 == 0) p[c] = even[c / 2 - 1];
         else p[c] = cmul(p[c - 1], w);
     });
 }

@@ -22,13 +22,32 @@
 
 namespace fc {
 
+// Does the walk keep the even powers of the stage-1 twiddle (w^2, w^4, ...: R1 / 2 - 1 values per round) in registers instead of
+// forming the whole chain again for every map?  Where the registers are there: one row per workgroup, F = 1 (the F > 1 walk
+// holds a feature sum besides), at most FC_ROWS_KEEP_REGS registers of them, and a stage 3 of 14 to 24 points: these kernels
+// run three or four waves per SIMD with registers to spare, whereas 4160 = 8.20.26 spills 24 registers with the powers kept and
+// 1088 = 8.17.8 drops from five waves to four (the build's *.rpt files, tools/rpt_summary.py).
+#ifndef FC_ROWS_KEEP_REGS
+#define FC_ROWS_KEEP_REGS 18
+#endif
+template <class C, bool MULTIF>
+constexpr bool row_multi_keeps_even_powers() {
+    return !MULTIF && C::RPW == 1 && C::R1 >= 4 && 2 * (C::R1 / 2 - 1) * C::RND1 <= FC_ROWS_KEEP_REGS && C::R3 >= 14 && C::R3 <= 24;
+}
+
 template <class C, bool MULTIF = false>
 struct RowMultiState {
+    static constexpr bool KEEP = row_multi_keeps_even_powers<C, MULTIF>();
+    static constexpr int NEVEN = C::R1 / 2 - 1;
     c32 s[C::R3];        // image spectrum of this thread's stage-3 butterfly (F = 1: whole walk; MULTIF: one step)
     c32 acc[MULTIF ? C::R3 : 1];   // feature sum of the current map (MULTIF)
     c32 x[C::RND1];      // kernel row of the current / next map
     c32 w1[C::RND1];     // stage-1 base twiddle w_L^j of this thread's butterflies (same for every map)
-    int yoff[C::RND1];   // tiled intermediate: element offset of this thread's rows (same for every map)
+    c32 w1even[KEEP ? C::RND1 * NEVEN : 1];   // KEEP: its even powers, round by round
+    // where this thread's stage-1 outputs go within a map (same for every map).  LINEAR: the BYTE offset of output 0 of round r's
+    // butterfly, row and column summed once; else the element offset of the row
+    int yoff[C::RND1];
+    int xoff;            // one row per workgroup: byte offset of this thread's round-0 element in a kernel row
 };
 
 // columns per tile of the tiled intermediate (pipeline.hpp: Geometry::y_tile_w)
@@ -51,15 +70,26 @@ FC_HD void fast_rows_multi_body(Ctx& ctx, c32* lds, const FastRowsArgs& g, int g
     const int row0 = group * RPW;
     const bool tiled = g.y_row_of != nullptr;
 
+    // st.x is zeroed once (below) and only the lanes that hold a kernel element ever load into it: no zero is materialised per map
     auto load_x = [&](int t, State& st, int kernel, int f) {
         const c32* abase = g.A + (size_t)kernel * g.a_kernel_stride + (MULTIF ? (size_t)f * g.a_feat_stride : 0);
         static_for<0, C::RND1>([&](auto r_) {
             constexpr int r = decltype(r_)::value;
             int u = t + NT * r;
             if constexpr (MULTIF) FC_OPAQUE(u);   // F > 1: index arithmetic recomputed per step, not hoisted out of the walk and spilled
-            const int rr = u / C::NB1, j = u - rr * C::NB1;
+            int rr, j;
+            const bool slot = row_slot<RPW, C::NB1, NT, r>(u, rr, j);
             const int row = row0 + rr;
-            st.x[r] = (rr < RPW && row < rows && j < kw) ? abase[(size_t)row * g.a_pitch + j] : mk(0.f, 0.f);
+            if (slot && row < rows && j < kw) {
+                if constexpr (RPW == 1) {
+                    // one row per workgroup: the uniform row address, the thread's 32-bit byte offset and the round as an immediate --
+                    // the load takes all three as they are (FC_OPAQUE, in place and free: see the stores of P5)
+                    FC_OPAQUE(st.xoff);
+                    st.x[r] = *reinterpret_cast<const c32*>(reinterpret_cast<const char*>(abase + (size_t)row * g.a_pitch) + (size_t)(unsigned)st.xoff + (size_t)(NT * r) * sizeof(c32));
+                } else {
+                    st.x[r] = abase[(size_t)row * g.a_pitch + j];
+                }
+            }
         });
     };
     // MULTIF, P3: register pairs [H0, H1) of feature f's image-spectrum row for stage-3 butterfly q of row rr (zeros past the last row)
@@ -78,24 +108,48 @@ FC_HD void fast_rows_multi_body(Ctx& ctx, c32* lds, const FastRowsArgs& g, int g
         }
     };
 
+    // p[c] = w1^c of round r's butterfly
+    auto stage1_chain = [&](auto r_, State& st, c32 (&p)[R1]) {
+        constexpr int r = decltype(r_)::value;
+        if constexpr (State::KEEP) power_chain_from_even<R1>(st.w1[r], &st.w1even[r * State::NEVEN], p);
+        else power_chain<R1>(st.w1[r], p);
+    };
+
     // once per workgroup: stage-2 twiddles into LDS, first kernel row, image-spectrum row
     ctx.phase_nosync([&](int t, State& st) {
         fc_tw2_fill<R2, R3, NT>(tw2, g.tw2, t);
+        static_for<0, C::RND1>([&](auto r_) { st.x[decltype(r_)::value] = mk(0.f, 0.f); });
+        st.xoff = t * (int)sizeof(c32);
         load_x(t, st, kernel0, 0);
         // loaded once: inside the walk a global load in P5 would have to be waited for together
         // with the stores issued just before it (one in-order memory counter)
         static_for<0, C::RND1>([&](auto r_) {
             constexpr int r = decltype(r_)::value;
             const int u = t + NT * r;
-            const int rr = u / C::NB1, j = u - rr * C::NB1;
+            int rr, j;
+            const bool slot = row_slot<RPW, C::NB1, NT, r>(u, rr, j);
             const int row = row0 + rr;
-            const bool live = rr < RPW && row < rows;
+            const bool live = slot && row < rows;
             st.w1[r] = live ? g.tw1[j] : mk(1.f, 0.f);
-            st.yoff[r] = live ? (tiled ? (g.y_row_of[row] << g.y_tile_shift) : row * g.y_pitch) : 0;
+            if constexpr (State::KEEP) {
+                c32 p[R1];
+                power_chain<R1>(st.w1[r], p);
+                static_for<0, State::NEVEN>([&](auto k_) {
+                    constexpr int k = decltype(k_)::value;
+                    st.w1even[r * State::NEVEN + k] = p[2 * k + 2];
+                });
+            }
+            const int yrow = live ? (tiled ? (g.y_row_of[row] << g.y_tile_shift) : row * g.y_pitch) : 0;
+            if constexpr (LINEAR) {
+                auto col = [&](int w) { return tiled ? (w >> g.y_tile_shift) * g.y_tile_elems + (w & ((1 << g.y_tile_shift) - 1)) : w; };
+                st.yoff[r] = live ? (int)((unsigned)(yrow + col(j)) * (unsigned)sizeof(c32)) : 0;
+            } else {
+                st.yoff[r] = yrow;
+            }
         });
         if constexpr (!MULTIF) {
-            const int rr = t / C::NB3, q = t - rr * C::NB3;
-            if (rr < RPW && row0 + rr < rows) {
+            int rr, q;
+            if (row_slot<RPW, C::NB3, NT, 0>(t, rr, q) && row0 + rr < rows) {
                 const c32* srow = g.S + (size_t)(row0 + rr) * g.s_pitch;
                 static_for<0, R3 / 2>([&](auto h_) {
                     constexpr int h = decltype(h_)::value;
@@ -125,11 +179,13 @@ FC_HD void fast_rows_multi_body(Ctx& ctx, c32* lds, const FastRowsArgs& g, int g
                 constexpr int r = decltype(r_)::value;
                 int u = t + NT * r;
                 if constexpr (MULTIF) FC_OPAQUE(u);
-                const int rr = u / C::NB1, j = u - rr * C::NB1;
-                if (rr < RPW && j < kw) {
+                int rr, j;
+                // (F > 1, where this phase runs for every feature, keeps the general form of the slot: 1088 = 8.17.8 comes out with 109
+                // instead of 95 registers, four waves per SIMD instead of five, with the short form in THIS phase -- and only in this one)
+                if (row_slot<RPW, C::NB1, NT, r, MULTIF>(u, rr, j) && j < kw) {
                     c32* buf = lds + rr * LR;
                     c32 p[R1];
-                    power_chain<R1>(st.w1[r], p);
+                    stage1_chain(r_, st, p);
                     buf[j] = st.x[r];
                     static_for<1, R1>([&](auto c_) {
                         constexpr int c = decltype(c_)::value;
@@ -150,8 +206,8 @@ FC_HD void fast_rows_multi_body(Ctx& ctx, c32* lds, const FastRowsArgs& g, int g
                 constexpr int r = decltype(r_)::value;
                 int u = t + NT * r;
                 if constexpr (MULTIF) FC_OPAQUE(u);
-                const int rr = u / C::NB2, w = u - rr * C::NB2;
-                if (rr < RPW) {
+                int rr, w;
+                if (row_slot<RPW, C::NB2, NT, r>(u, rr, w)) {
                     const int c1 = w / R3, b = w - c1 * R3;
                     c32* p = lds + rr * LR + c1 * S1 + b;
                     c32 v[R2];
@@ -176,8 +232,8 @@ FC_HD void fast_rows_multi_body(Ctx& ctx, c32* lds, const FastRowsArgs& g, int g
         ctx.phase([&](int t_, State& st) {
             int t = t_;
             if constexpr (MULTIF) FC_OPAQUE(t);
-            const int rr = t / C::NB3, q = t - rr * C::NB3;
-            if (rr < RPW) {
+            int rr, q;
+            if (row_slot<RPW, C::NB3, NT, 0>(t, rr, q)) {
                 // MULTIF: this feature's image-spectrum row.  Only its first S_EARLY register pairs are requested
                 // ahead of the forward butterfly, the rest right after it: with the whole row in flight beside the
                 // radix-22 butterfly (its in-register composite form needs ~70 registers of its own) and the feature
@@ -259,8 +315,8 @@ FC_HD void fast_rows_multi_body(Ctx& ctx, c32* lds, const FastRowsArgs& g, int g
                 constexpr int r = decltype(r_)::value;
                 int u = t + NT * r;
                 if constexpr (MULTIF) FC_OPAQUE(u);
-                const int rr = u / C::NB2, w = u - rr * C::NB2;
-                if (rr < RPW) {
+                int rr, w;
+                if (row_slot<RPW, C::NB2, NT, r>(u, rr, w)) {
                     const int c1 = w / R3, b = w - c1 * R3;
                     c32* p = lds + rr * LR + c1 * S1 + b;
                     c32 v[R2];
@@ -288,8 +344,8 @@ FC_HD void fast_rows_multi_body(Ctx& ctx, c32* lds, const FastRowsArgs& g, int g
             FC_WAIT_VMEM();
             // LINEAR: the R1 outputs of a butterfly are m1 columns apart; when that is a whole number
             // of layout tiles (or the intermediate is row-major) and nothing is cropped, output a
-            // sits at base + a * stride: a scalar base, one 32-bit add per store, no 64-bit tile
-            // arithmetic (a fifth of this kernel's VALU instructions; a cropped window adds a compare)
+            // sits at base + a * stride: a scalar base per output, the thread's 32-bit offset, no 64-bit tile
+            // arithmetic (once a fifth of this kernel's VALU instructions; a cropped window adds a compare)
             // Where m1 is an odd number of HALF tiles (2112 = 8.12.22: 264 columns = 16.5 tiles; 288 = 4.6.12: 72) the even and the
             // odd outputs form two such chains, 2 * m1 columns apart each: two bases instead of one (round 4: cfg5 and cfg1 had
             // run the general form below until then).
@@ -298,20 +354,24 @@ FC_HD void fast_rows_multi_body(Ctx& ctx, c32* lds, const FastRowsArgs& g, int g
                 constexpr bool TWO_CHAINS = (m1 % FC_Y_TILE_W) != 0;
                 constexpr int SA = TWO_CHAINS ? 2 : 1;            // outputs a and a + SA are SA * m1 columns = whole tiles apart
                 const unsigned stride_b = (unsigned)((tiled ? ((SA * m1) >> g.y_tile_shift) * g.y_tile_elems : SA * m1) * (int)sizeof(c32));
+                // The store of output a: the uniform address yb + (a / SA) * stride_b, formed on the scalar unit, plus the thread's
+                // 32-bit byte offset of its chain (State::yoff, summed once per walk) -- the scalar-base + vector-offset form of the
+                // store, no vector add per store.  (stride_b is a launch argument: it cannot be the store's immediate, and at cfg3's
+                // tile stride it would not fit one.)  A cropped window compares the thread's column against wout - a * m1.
                 static_for<0, C::RND1>([&](auto r_) {
                     constexpr int r = decltype(r_)::value;
                     int u = t + NT * r;
-                    FC_OPAQUE(u);
-                    const int rr = u / C::NB1, j = u - rr * C::NB1;
-                    if (rr < RPW && row0 + rr < rows) {
+                    FC_OPAQUE(u);   // the twiddle chain is recomputed per map, not kept (spilled) across the loop
+                    int rr, j;
+                    if (row_slot<RPW, C::NB1, NT, r>(u, rr, j) && row0 + rr < rows) {
                         const c32* buf = lds + rr * LR;
                         c32 p[R1];
                         c32 v[R1];
                         if constexpr (FC_ROWSM_DBG & 1) {
                             static_for<0, R1>([&](auto c_) { v[decltype(c_)::value] = st.s[decltype(c_)::value]; });
-                            if (m + 1 < nk && j < kw) power_chain<R1>(st.w1[r], p);
+                            if (m + 1 < nk && j < kw) stage1_chain(r_, st, p);
                         } else {
-                        power_chain<R1>(st.w1[r], p);
+                        stage1_chain(r_, st, p);
                         v[0] = buf[j];
                         static_for<1, R1>([&](auto c_) {
                             constexpr int c = decltype(c_)::value;
@@ -319,25 +379,27 @@ FC_HD void fast_rows_multi_body(Ctx& ctx, c32* lds, const FastRowsArgs& g, int g
                         });
                         Dft<R1, +1>::run(v);
                         }
-                        const int jo = tiled ? (j >> g.y_tile_shift) * g.y_tile_elems + (j & ((1 << g.y_tile_shift) - 1)) : j;
-                        const unsigned off0 = (unsigned)(st.yoff[r] + jo) * (unsigned)sizeof(c32);
-                        unsigned off1 = off0;                      // base of the odd outputs (TWO_CHAINS)
+                        // (FC_OPAQUE on the offset, in place and free: its zero-extension stays beside the store instead of being
+                        // hoisted out of the walk as a 64-bit pair, which the store could only take through a 64-bit vector add)
+                        // TWO_CHAINS: the odd chain starts m1 = k tiles + h columns further on -- the same tile row k (+ 1 where the
+                        // column wraps into the next tile) and h columns on (or TL - h back): one of two uniform distances
+                        int yoff1 = 0;
                         if constexpr (TWO_CHAINS) {
-                            const int j1 = j + m1;
-                            const int jo1 = tiled ? (j1 >> g.y_tile_shift) * g.y_tile_elems + (j1 & ((1 << g.y_tile_shift) - 1)) : j1;
-                            off1 = (unsigned)(st.yoff[r] + jo1) * (unsigned)sizeof(c32);
+                            const int TL = 1 << g.y_tile_shift, h = m1 & (TL - 1), k = m1 >> g.y_tile_shift;
+                            const int near = tiled ? k * g.y_tile_elems + h : m1, far = tiled ? (k + 1) * g.y_tile_elems + h - TL : m1;
+                            yoff1 = st.yoff[r] + (((j & (TL - 1)) + h >= TL) ? far : near) * (int)sizeof(c32);
                         }
+                        auto store = [&](auto a_) {
+                            constexpr int a = decltype(a_)::value;
+                            int& base = (TWO_CHAINS && (a & 1)) ? yoff1 : st.yoff[r];
+                            FC_OPAQUE(base);
+                            FC_ROWSM_STORE(reinterpret_cast<c32*>(yb + (size_t)((unsigned)(a / SA) * stride_b) + (size_t)(unsigned)base), v[a]);
+                        };
                         if (g.wout >= L) {   // nothing cropped (uniform)
-                            static_for<0, R1>([&](auto a_) {
-                                constexpr int a = decltype(a_)::value;
-                                const unsigned base = (TWO_CHAINS && (a & 1)) ? off1 : off0;
-                                FC_ROWSM_STORE(reinterpret_cast<c32*>(yb + (size_t)(base + (unsigned)(a / SA) * stride_b)), v[a]);
-                            });
+                            static_for<0, R1>(store);
                         } else {             // cropped window (cfg4: 4160 columns of the 4224 transform)
                             static_for<0, R1>([&](auto a_) {
-                                constexpr int a = decltype(a_)::value;
-                                const unsigned base = (TWO_CHAINS && (a & 1)) ? off1 : off0;
-                                if (j + a * m1 < g.wout) FC_ROWSM_STORE(reinterpret_cast<c32*>(yb + (size_t)(base + (unsigned)(a / SA) * stride_b)), v[a]);
+                                if (j < g.wout - decltype(a_)::value * m1) store(a_);
                             });
                         }
                         if (m + 1 < nk && j < kw) {   // forward stage 1 of the next map into the cells just read
@@ -356,12 +418,13 @@ FC_HD void fast_rows_multi_body(Ctx& ctx, c32* lds, const FastRowsArgs& g, int g
                 constexpr int r = decltype(r_)::value;
                 int u = t + NT * r;
                 FC_OPAQUE(u);   // twiddle chains and store offsets are recomputed per map, not kept (spilled) across the loop
-                const int rr = u / C::NB1, j = u - rr * C::NB1;
+                int rr, j;
+                const bool slot = row_slot<RPW, C::NB1, NT, r>(u, rr, j);
                 const int row = row0 + rr;
-                if (rr < RPW && row < rows) {
+                if (slot && row < rows) {
                     const c32* buf = lds + rr * LR;
                     c32 p[R1];
-                    power_chain<R1>(st.w1[r], p);
+                    stage1_chain(r_, st, p);
                     c32 v[R1];
                     v[0] = buf[j];
                     static_for<1, R1>([&](auto c_) {
