@@ -510,20 +510,9 @@ FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int
             if constexpr (SLICED) { if (col < cur_lo || col >= cur_hi) return; }
             c32* p = lds + col * LP + C::run_of_thread(q);
             c32 v[R3];
-            static_for<0, R3 / 2>([&](auto h_) {
-                constexpr int h = decltype(h_)::value;
-                c32x2 w = *reinterpret_cast<const c32x2*>(p + 2 * h);
-                v[2 * h] = w.a;
-                v[2 * h + 1] = w.b;
-            });
+            run_load<R3>(p, v);
             Dft<R3, +1>::run(v);
-            static_for<0, R3 / 2>([&](auto h_) {
-                constexpr int h = decltype(h_)::value;
-                c32x2 w;
-                w.a = v[2 * h];
-                w.b = v[2 * h + 1];
-                *reinterpret_cast<c32x2*>(p + 2 * h) = w;
-            });
+            run_store<R3>(p, v);
         });
 
         FC_COLS_STAMP(2);
@@ -544,18 +533,7 @@ FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int
                 if (mine2) {
                     const int col = idx / C::NB2, u = idx % C::NB2;
                     const int c1 = u / R3, b = u % R3;
-                    c32* p = lds + col * LP + c1 * C::S1 + b;
-                    c32 v[R2];
-                    v[0] = p[0];
-                    static_for<1, R2>([&](auto c_) {
-                        constexpr int c = decltype(c_)::value;
-                        v[c] = cmulc(p[c * R3], tw2[(c - 1) * R3 + b]);
-                    });
-                    Dft<R2, +1>::run(v);
-                    static_for<0, R2>([&](auto a_) {
-                        constexpr int a = decltype(a_)::value;
-                        p[a * R3] = v[a];
-                    });
+                    inv_stage2<R2, R3>(lds + col * LP + c1 * C::S1 + b, Tw2Plain<R2, R3>{tw2, b});
                 }
             });
         });
@@ -596,44 +574,31 @@ FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int
                     c32 pw[R1];
                     power_chain<R1>(tw1[j], pw);
                     c32 v[R1];
-                    v[0] = p[0];
-                    static_for<1, R1>([&](auto c_) {
-                        constexpr int c = decltype(c_)::value;
-                        v[c] = cmulc(p[c * C::S1], pw[c]);
-                    });
-                    Dft<R1, +1>::run(v);
+                    inv_stage1_in<R1, C::S1>(p, 0, pw, v);
                     if constexpr (RECT) {
                         // element (h - h_lo) of the column's run of the dense map; hr = row 2n of the pair, relative to h_lo
                         const size_t cbase = (size_t)(w0 + col - g.rect_w_lo) * g.out_pitch;
-                        if constexpr (OUT16) {
-                            uint16_t* o = out16 + cbase;
-                            static_for<0, R1>([&](auto a_) {
-                                constexpr int a = decltype(a_)::value;
-                                const int hr = 2 * (j + a * m1) - g.h_lo;
-                                if ((unsigned)(hr + 1) <= nrows) {     // rows hr, hr + 1: at least one of them is in [0, nrows)
-                                    if (g.rect_wide) {
-                                        FC_STREAM_STORE4(o + hr, fc_pack_map16(v[a].x, v[a].y, out_bf16));
-                                    } else {
-                                        if (hr >= 0) FC_STREAM_STORE_ELEM(o + hr, fc_map16(v[a].x, out_bf16));
-                                        if ((unsigned)(hr + 1) < nrows) FC_STREAM_STORE_ELEM(o + hr + 1, fc_map16(v[a].y, out_bf16));
-                                    }
+                        // (the two element classes differ in the pointer, the pair store and the conversion: one predicated block)
+                        std::conditional_t<OUT16, uint16_t, float>* o;
+                        if constexpr (OUT16) o = out16 + cbase;
+                        else o = out + cbase;
+                        auto elem = [&](float x) {
+                            if constexpr (OUT16) return fc_map16(x, out_bf16);
+                            else return x;
+                        };
+                        static_for<0, R1>([&](auto a_) {
+                            constexpr int a = decltype(a_)::value;
+                            const int hr = 2 * (j + a * m1) - g.h_lo;
+                            if ((unsigned)(hr + 1) <= nrows) {     // rows hr, hr + 1: at least one of them is in [0, nrows)
+                                if (g.rect_wide) {
+                                    if constexpr (OUT16) FC_STREAM_STORE4(o + hr, fc_pack_map16(v[a].x, v[a].y, out_bf16));
+                                    else FC_STREAM_STORE(reinterpret_cast<c32*>(o + hr), v[a]);
+                                } else {
+                                    if (hr >= 0) FC_STREAM_STORE_ELEM(o + hr, elem(v[a].x));
+                                    if ((unsigned)(hr + 1) < nrows) FC_STREAM_STORE_ELEM(o + hr + 1, elem(v[a].y));
                                 }
-                            });
-                        } else {
-                            float* o = out + cbase;
-                            static_for<0, R1>([&](auto a_) {
-                                constexpr int a = decltype(a_)::value;
-                                const int hr = 2 * (j + a * m1) - g.h_lo;
-                                if ((unsigned)(hr + 1) <= nrows) {     // rows hr, hr + 1: at least one of them is in [0, nrows)
-                                    if (g.rect_wide) {
-                                        FC_STREAM_STORE(reinterpret_cast<c32*>(o + hr), v[a]);
-                                    } else {
-                                        if (hr >= 0) FC_STREAM_STORE_ELEM(o + hr, v[a].x);
-                                        if ((unsigned)(hr + 1) < nrows) FC_STREAM_STORE_ELEM(o + hr + 1, v[a].y);
-                                    }
-                                }
-                            });
-                        }
+                            }
+                        });
                     } else if constexpr (OUT16) {
                         uint32_t* o = reinterpret_cast<uint32_t*>(out16 + (size_t)(w0 + col) * g.out_pitch);
                         static_for<0, R1>([&](auto a_) {

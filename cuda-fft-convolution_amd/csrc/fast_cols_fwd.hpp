@@ -99,12 +99,7 @@ FC_HD void fast_cols_fwd_body(Ctx& ctx, c32* lds, const FastColsFwdArgs& g, int 
                         const c32 z = sample(in + (size_t)(c0 + col) * g.in_col_pitch, j);
                         c32 p[R1];
                         power_chain<R1>(tw1[j], p);
-                        c32* q = lds + col * LP + j;
-                        q[0] = z;
-                        static_for<1, R1>([&](auto c_) {
-                            constexpr int c = decltype(c_)::value;
-                            q[c * C::S1] = cmul(z, p[c]);
-                        });
+                        fwd_stage1_out_pruned<R1, C::S1>(lds + col * LP + j, 0, z, p);
                     }
                 }
             } else {
@@ -156,13 +151,7 @@ FC_HD void fast_cols_fwd_body(Ctx& ctx, c32* lds, const FastColsFwdArgs& g, int 
                             v[a] = p[a * R3];
                         }
                     });
-                    if constexpr (PRUNED) Dft<R2, -1>::template run_nz<NZ2>(v);
-                    else Dft<R2, -1>::run(v);
-                    p[0] = v[0];
-                    static_for<1, R2>([&](auto c_) {
-                        constexpr int c = decltype(c_)::value;
-                        p[c * R3] = cmul(v[c], tw2[(c - 1) * R3 + b]);
-                    });
+                    fwd_stage2_out<R2, R3, NZ2>(p, v, Tw2Plain<R2, R3>{tw2, b});
                 }
             });
         });
@@ -172,20 +161,9 @@ FC_HD void fast_cols_fwd_body(Ctx& ctx, c32* lds, const FastColsFwdArgs& g, int 
             const int col = t / C::NB3, q = t % C::NB3;
             c32* p = lds + col * LP + C::run_of_thread(q);
             c32 v[R3];
-            static_for<0, R3 / 2>([&](auto h_) {
-                constexpr int h = decltype(h_)::value;
-                c32x2 w = *reinterpret_cast<const c32x2*>(p + 2 * h);
-                v[2 * h] = w.a;
-                v[2 * h + 1] = w.b;
-            });
+            run_load<R3>(p, v);
             Dft<R3, -1>::run(v);
-            static_for<0, R3 / 2>([&](auto h_) {
-                constexpr int h = decltype(h_)::value;
-                c32x2 w;
-                w.a = v[2 * h];
-                w.b = v[2 * h + 1];
-                *reinterpret_cast<c32x2*>(p + 2 * h) = w;
-            });
+            run_store<R3>(p, v);
         });
 
         // F4: split the packed transform into the spectrum of the real columns, in place

@@ -423,13 +423,11 @@ inline bool fast_cols_slice_plan(int M, int T, int want, FastColsArgs& a, int& g
 // ---- Launch decisions: which instantiation a launch runs, with which arguments, on what grid.  Plain host code: the launchers
 // ---- (kernels_*.inc) and the CPU tier's runners (tests/emu/emu_runners.hpp) both call these, so neither can drift from the other.
 
-// Row kernel: f(std::bool_constant<LINEAR>{}), LINEAR as fast_rows_multi_linear says.  (m1 a whole number of HALF layout tiles:
-// LINEAR whatever the intermediate's layout -- the other variant is not built, so f is not instantiated for it)
+// Row kernel: f(std::bool_constant<LINEAR>{}) -- LINEAR is true for every configuration (RowCfg asserts that m1 is a whole number
+// of half layout tiles), so there is nothing left to decide at run time and one instantiation per configuration
 template <class Cfg, class F>
-inline void fast_rows_visit_linear(const FastRowsArgs& a, F&& f) {
-    if constexpr ((2 * Cfg::m1) % FC_Y_TILE_W == 0) f(std::true_type{});
-    else if (fast_rows_multi_linear(a, Cfg::L, Cfg::m1)) f(std::true_type{});
-    else f(std::false_type{});
+inline void fast_rows_visit_linear(const FastRowsArgs&, F&& f) {
+    f(std::true_type{});
 }
 // Row kernels: `groups` workgroups of RPW rows by `walks` of per_wg kernels (the F = 1 grid; the forward rows use the groups alone);
 // `flat`: the 1-D grid of the F > 1 walk, groups rounded up to whole rounds of the 8 XCDs

@@ -24,8 +24,12 @@
 #include "butterflies.hpp"
 #include "fc_common.hpp"
 #include "fc_instrument.hpp"
+#include "fft_stages.hpp"
 
 namespace fc {
+
+// columns per tile of the tiled intermediate (pipeline.hpp: Geometry::y_tile_w)
+constexpr int FC_Y_TILE_W = 16, FC_Y_TILE_SHIFT = 4;
 
 // RPW rows of length L are transformed side by side by one workgroup of NT threads (short rows:
 // several per workgroup so that every stage still fills the lanes).
@@ -52,6 +56,9 @@ struct RowCfg {
     static_assert(RPW * NB3 <= NT, "one stage-3 butterfly per thread");
     static_assert(R3 % 2 == 0, "register-order layout pairs stage-3 elements");
     static_assert((R3 * 8) % 16 == 0 && (S1 * 8) % 16 == 0, "stage-3 runs must be 16-byte aligned");
+    // the spectral-row kernel stores the R1 outputs of a stage-1 butterfly, m1 columns apart, as one or two chains of equal
+    // strides in the tiled intermediate (fast_rows_multi.hpp, P5) -- the only form of that phase there is
+    static_assert((2 * m1) % FC_Y_TILE_W == 0, "m1 must be a whole number of half layout tiles");
 };
 
 // position of element (q, a) of the register-order layout

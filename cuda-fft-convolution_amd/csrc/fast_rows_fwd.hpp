@@ -50,12 +50,7 @@ FC_HD void fast_rows_fwd_body(Ctx& ctx, c32* lds, const FastRowsFwdArgs& g, int 
                 Dft<R1, -1>::run(v);
                 c32 p[R1];
                 power_chain<R1>(g.tw1[j], p);
-                c32* buf = lds + rr * LR;
-                buf[j] = v[0];
-                static_for<1, R1>([&](auto c_) {
-                    constexpr int c = decltype(c_)::value;
-                    buf[c * S1 + j] = cmul(v[c], p[c]);
-                });
+                fwd_stage1_out<R1, S1>(lds + rr * LR, j, v, p);
             }
         });
     });
@@ -74,12 +69,7 @@ FC_HD void fast_rows_fwd_body(Ctx& ctx, c32* lds, const FastRowsFwdArgs& g, int 
                     constexpr int a = decltype(a_)::value;
                     v[a] = p[a * R3];
                 });
-                Dft<R2, -1>::run(v);
-                p[0] = v[0];
-                fc_tw2_each<R2>(tw2, b, [&](auto c_, c32 w) {
-                    constexpr int c = decltype(c_)::value;
-                    p[c * R3] = cmul(v[c], w);
-                });
+                fwd_stage2_out<R2, R3, R2>(p, v, Tw2Paired<R2>{tw2, b});
             }
         });
     });
@@ -92,12 +82,7 @@ FC_HD void fast_rows_fwd_body(Ctx& ctx, c32* lds, const FastRowsFwdArgs& g, int 
         if (rr < RPW && row < rows) {
             const c32* p = lds + rr * LR + (q / R2) * S1 + (q % R2) * R3;
             c32 v[R3];
-            static_for<0, R3 / 2>([&](auto h_) {
-                constexpr int h = decltype(h_)::value;
-                c32x2 w = *reinterpret_cast<const c32x2*>(p + 2 * h);
-                v[2 * h] = w.a;
-                v[2 * h + 1] = w.b;
-            });
+            run_load<R3>(p, v);
             Dft<R3, -1>::run(v);
             c32* dst = g.S + (size_t)row * g.pitch;
             static_for<0, R3 / 2>([&](auto h_) {

@@ -44,24 +44,18 @@ struct RowMultiState {
     c32 x[C::RND1];      // kernel row of the current / next map
     c32 w1[C::RND1];     // stage-1 base twiddle w_L^j of this thread's butterflies (same for every map)
     c32 w1even[KEEP ? C::RND1 * NEVEN : 1];   // KEEP: its even powers, round by round
-    // where this thread's stage-1 outputs go within a map (same for every map).  LINEAR: the BYTE offset of output 0 of round r's
-    // butterfly, row and column summed once; else the element offset of the row
+    // where this thread's stage-1 outputs go within a map (same for every map): the BYTE offset of output 0 of round r's
+    // butterfly, row and column summed once (see P5)
     int yoff[C::RND1];
     int xoff;            // one row per workgroup: byte offset of this thread's round-0 element in a kernel row
 };
 
-// columns per tile of the tiled intermediate (pipeline.hpp: Geometry::y_tile_w)
-constexpr int FC_Y_TILE_W = 16, FC_Y_TILE_SHIFT = 4;
-
-// LINEAR (chosen by the launcher with fast_rows_multi_linear): see P5.
-inline bool fast_rows_multi_linear(const FastRowsArgs& g, int L, int m1) {
-    const bool tiled = g.y_row_of != nullptr;
-    (void)L;
-    return !tiled || ((2 * m1) & ((1 << g.y_tile_shift) - 1)) == 0;     // whole tiles, or half tiles (two chains: even / odd outputs)
-}
-
+// LINEAR: always true (fast_rows_visit_linear, fast_paths.hpp).  It once chose between two forms of P5; the other one (per-output
+// tile arithmetic, for an m1 that is no whole number of half layout tiles) had no configuration and is gone: RowCfg asserts
+// the condition.  The argument itself is still to be deleted, together with the visitor and the argument of the two kernels.
 template <class C, int NZ2, bool LINEAR, bool MULTIF = false, class Ctx>
 FC_HD void fast_rows_multi_body(Ctx& ctx, c32* lds, const FastRowsArgs& g, int group, int kernel0, int nk, int rows) {
+    static_assert(LINEAR, "the row kernel has one form of its last phase");
     constexpr int L = C::L, R1 = C::R1, R2 = C::R2, R3 = C::R3, NT = C::NT, m1 = C::m1, RPW = C::RPW, S1 = C::S1, LR = C::LR;
     using State = RowMultiState<C, MULTIF>;
     const int nF = MULTIF ? g.F : 1;
@@ -140,12 +134,8 @@ FC_HD void fast_rows_multi_body(Ctx& ctx, c32* lds, const FastRowsArgs& g, int g
                 });
             }
             const int yrow = live ? (tiled ? (g.y_row_of[row] << g.y_tile_shift) : row * g.y_pitch) : 0;
-            if constexpr (LINEAR) {
-                auto col = [&](int w) { return tiled ? (w >> g.y_tile_shift) * g.y_tile_elems + (w & ((1 << g.y_tile_shift) - 1)) : w; };
-                st.yoff[r] = live ? (int)((unsigned)(yrow + col(j)) * (unsigned)sizeof(c32)) : 0;
-            } else {
-                st.yoff[r] = yrow;
-            }
+            auto col = [&](int w) { return tiled ? (w >> g.y_tile_shift) * g.y_tile_elems + (w & ((1 << g.y_tile_shift) - 1)) : w; };
+            st.yoff[r] = live ? (int)((unsigned)(yrow + col(j)) * (unsigned)sizeof(c32)) : 0;
         });
         if constexpr (!MULTIF) {
             int rr, q;
@@ -186,11 +176,7 @@ FC_HD void fast_rows_multi_body(Ctx& ctx, c32* lds, const FastRowsArgs& g, int g
                     c32* buf = lds + rr * LR;
                     c32 p[R1];
                     stage1_chain(r_, st, p);
-                    buf[j] = st.x[r];
-                    static_for<1, R1>([&](auto c_) {
-                        constexpr int c = decltype(c_)::value;
-                        buf[c * S1 + j] = cmul(st.x[r], p[c]);
-                    });
+                    fwd_stage1_out_pruned<R1, S1>(buf, j, st.x[r], p);
                 }
             });
         });
@@ -216,12 +202,7 @@ FC_HD void fast_rows_multi_body(Ctx& ctx, c32* lds, const FastRowsArgs& g, int g
                         if constexpr (a < NZ2) v[a] = (a * R3 + b < kw) ? p[a * R3] : mk(0.f, 0.f);
                         else v[a] = mk(0.f, 0.f);
                     });
-                    Dft<R2, -1>::template run_nz<NZ2>(v);   // inputs a >= NZ2 are structural zeros
-                    p[0] = v[0];
-                    fc_tw2_each<R2>(tw2, b, [&](auto c_, c32 w) {
-                        constexpr int c = decltype(c_)::value;
-                        p[c * R3] = cmul(v[c], w);
-                    });
+                    fwd_stage2_out<R2, R3, NZ2>(p, v, Tw2Paired<R2>{tw2, b});   // inputs a >= NZ2 are structural zeros
                 }
             });
         });
@@ -248,26 +229,13 @@ FC_HD void fast_rows_multi_body(Ctx& ctx, c32* lds, const FastRowsArgs& g, int g
                 if constexpr (MULTIF && 0 < S_EARLY) load_s(st, f, rr, q, IC<0>{}, IC<S_EARLY>{});
                 c32* p = lds + rr * LR + (q / R2) * S1 + (q % R2) * R3;     // run c of stage-1 block c1: q = c1 * R2 + c
                 c32 v[R3];
-                static_for<0, R3 / 2>([&](auto h_) {
-                    constexpr int h = decltype(h_)::value;
-                    c32x2 w = *reinterpret_cast<const c32x2*>(p + 2 * h);
-                    v[2 * h] = w.a;
-                    v[2 * h + 1] = w.b;
-                });
+                run_load<R3>(p, v);
                 if constexpr (MULTIF) {
                     // The R3 LDS cells this thread has just read are its own until the next barrier: the
                     // feature sum is parked there while the butterfly runs beside the in-flight image row
                     // (sum + image row + butterfly do not fit the register file together: 58-100 spilled
                     // registers otherwise) and comes back, pair by pair, into the accumulation.
-                    if (f > 0) {
-                        static_for<0, R3 / 2>([&](auto h_) {
-                            constexpr int h = decltype(h_)::value;
-                            c32x2 w;
-                            w.a = st.acc[2 * h];
-                            w.b = st.acc[2 * h + 1];
-                            *reinterpret_cast<c32x2*>(p + 2 * h) = w;
-                        });
-                    }
+                    if (f > 0) run_store<R3>(p, st.acc);
                     FC_SCHED_FENCE();
                 }
                 Dft<R3, -1>::run(v);
@@ -296,13 +264,7 @@ FC_HD void fast_rows_multi_body(Ctx& ctx, c32* lds, const FastRowsArgs& g, int g
                 }
                 if (!MULTIF || last_f) {
                     Dft<R3, +1>::run(v);
-                    static_for<0, R3 / 2>([&](auto h_) {
-                        constexpr int h = decltype(h_)::value;
-                        c32x2 w;
-                        w.a = v[2 * h];
-                        w.b = v[2 * h + 1];
-                        *reinterpret_cast<c32x2*>(p + 2 * h) = w;
-                    });
+                    run_store<R3>(p, v);
                 }
             }
         });
@@ -318,18 +280,7 @@ FC_HD void fast_rows_multi_body(Ctx& ctx, c32* lds, const FastRowsArgs& g, int g
                 int rr, w;
                 if (row_slot<RPW, C::NB2, NT, r>(u, rr, w)) {
                     const int c1 = w / R3, b = w - c1 * R3;
-                    c32* p = lds + rr * LR + c1 * S1 + b;
-                    c32 v[R2];
-                    v[0] = p[0];
-                    fc_tw2_each<R2>(tw2, b, [&](auto c_, c32 w) {
-                        constexpr int c = decltype(c_)::value;
-                        v[c] = cmulc(p[c * R3], w);
-                    });
-                    Dft<R2, +1>::run(v);
-                    static_for<0, R2>([&](auto a_) {
-                        constexpr int a = decltype(a_)::value;
-                        p[a * R3] = v[a];
-                    });
+                    inv_stage2<R2, R3>(lds + rr * LR + c1 * S1 + b, Tw2Paired<R2>{tw2, b});
                 }
             });
         });
@@ -342,113 +293,61 @@ FC_HD void fast_rows_multi_body(Ctx& ctx, c32* lds, const FastRowsArgs& g, int g
             // the next kernel row (prefetched after P1) has had three phases to arrive: take it off
             // the memory counter before the store burst, or the next P1 would wait for these stores
             FC_WAIT_VMEM();
-            // LINEAR: the R1 outputs of a butterfly are m1 columns apart; when that is a whole number
-            // of layout tiles (or the intermediate is row-major) and nothing is cropped, output a
-            // sits at base + a * stride: a scalar base per output, the thread's 32-bit offset, no 64-bit tile
-            // arithmetic (once a fifth of this kernel's VALU instructions; a cropped window adds a compare)
+            // The R1 outputs of a butterfly are m1 columns apart, and m1 is a whole number of layout tiles or of HALF tiles (RowCfg
+            // asserts it), so whether the intermediate is tiled or row-major, output a sits at base + a * stride: a scalar base per
+            // output, the thread's 32-bit offset, no 64-bit tile arithmetic (once a fifth of this kernel's VALU instructions; a
+            // cropped window adds a compare).
             // Where m1 is an odd number of HALF tiles (2112 = 8.12.22: 264 columns = 16.5 tiles; 288 = 4.6.12: 72) the even and the
-            // odd outputs form two such chains, 2 * m1 columns apart each: two bases instead of one (round 4: cfg5 and cfg1 had
-            // run the general form below until then).
-            if constexpr (LINEAR) {
-                char* yb = reinterpret_cast<char*>(ybase);
-                constexpr bool TWO_CHAINS = (m1 % FC_Y_TILE_W) != 0;
-                constexpr int SA = TWO_CHAINS ? 2 : 1;            // outputs a and a + SA are SA * m1 columns = whole tiles apart
-                const unsigned stride_b = (unsigned)((tiled ? ((SA * m1) >> g.y_tile_shift) * g.y_tile_elems : SA * m1) * (int)sizeof(c32));
-                // The store of output a: the uniform address yb + (a / SA) * stride_b, formed on the scalar unit, plus the thread's
-                // 32-bit byte offset of its chain (State::yoff, summed once per walk) -- the scalar-base + vector-offset form of the
-                // store, no vector add per store.  (stride_b is a launch argument: it cannot be the store's immediate, and at cfg3's
-                // tile stride it would not fit one.)  A cropped window compares the thread's column against wout - a * m1.
-                static_for<0, C::RND1>([&](auto r_) {
-                    constexpr int r = decltype(r_)::value;
-                    int u = t + NT * r;
-                    FC_OPAQUE(u);   // the twiddle chain is recomputed per map, not kept (spilled) across the loop
-                    int rr, j;
-                    if (row_slot<RPW, C::NB1, NT, r>(u, rr, j) && row0 + rr < rows) {
-                        const c32* buf = lds + rr * LR;
-                        c32 p[R1];
-                        c32 v[R1];
-                        if constexpr (FC_ROWSM_DBG & 1) {
-                            static_for<0, R1>([&](auto c_) { v[decltype(c_)::value] = st.s[decltype(c_)::value]; });
-                            if (m + 1 < nk && j < kw) stage1_chain(r_, st, p);
-                        } else {
-                        stage1_chain(r_, st, p);
-                        v[0] = buf[j];
-                        static_for<1, R1>([&](auto c_) {
-                            constexpr int c = decltype(c_)::value;
-                            v[c] = cmulc(buf[c * S1 + j], p[c]);
-                        });
-                        Dft<R1, +1>::run(v);
-                        }
-                        // (FC_OPAQUE on the offset, in place and free: its zero-extension stays beside the store instead of being
-                        // hoisted out of the walk as a 64-bit pair, which the store could only take through a 64-bit vector add)
-                        // TWO_CHAINS: the odd chain starts m1 = k tiles + h columns further on -- the same tile row k (+ 1 where the
-                        // column wraps into the next tile) and h columns on (or TL - h back): one of two uniform distances
-                        int yoff1 = 0;
-                        if constexpr (TWO_CHAINS) {
-                            const int TL = 1 << g.y_tile_shift, h = m1 & (TL - 1), k = m1 >> g.y_tile_shift;
-                            const int near = tiled ? k * g.y_tile_elems + h : m1, far = tiled ? (k + 1) * g.y_tile_elems + h - TL : m1;
-                            yoff1 = st.yoff[r] + (((j & (TL - 1)) + h >= TL) ? far : near) * (int)sizeof(c32);
-                        }
-                        auto store = [&](auto a_) {
-                            constexpr int a = decltype(a_)::value;
-                            int& base = (TWO_CHAINS && (a & 1)) ? yoff1 : st.yoff[r];
-                            FC_OPAQUE(base);
-                            FC_ROWSM_STORE(reinterpret_cast<c32*>(yb + (size_t)((unsigned)(a / SA) * stride_b) + (size_t)(unsigned)base), v[a]);
-                        };
-                        if (g.wout >= L) {   // nothing cropped (uniform)
-                            static_for<0, R1>(store);
-                        } else {             // cropped window (cfg4: 4160 columns of the 4224 transform)
-                            static_for<0, R1>([&](auto a_) {
-                                if (j < g.wout - decltype(a_)::value * m1) store(a_);
-                            });
-                        }
-                        if (m + 1 < nk && j < kw) {   // forward stage 1 of the next map into the cells just read
-                            c32* wbuf = lds + rr * LR;
-                            wbuf[j] = st.x[r];
-                            static_for<1, R1>([&](auto c_) {
-                                constexpr int c = decltype(c_)::value;
-                                wbuf[c * S1 + j] = cmul(st.x[r], p[c]);
-                            });
-                        }
-                    }
-                    FC_SCHED_FENCE();
-                });
-            } else
+            // odd outputs form two such chains, 2 * m1 columns apart each: two bases instead of one.
+            char* yb = reinterpret_cast<char*>(ybase);
+            constexpr bool TWO_CHAINS = (m1 % FC_Y_TILE_W) != 0;
+            constexpr int SA = TWO_CHAINS ? 2 : 1;            // outputs a and a + SA are SA * m1 columns = whole tiles apart
+            const unsigned stride_b = (unsigned)((tiled ? ((SA * m1) >> g.y_tile_shift) * g.y_tile_elems : SA * m1) * (int)sizeof(c32));
+            // The store of output a: the uniform address yb + (a / SA) * stride_b, formed on the scalar unit, plus the thread's
+            // 32-bit byte offset of its chain (State::yoff, summed once per walk) -- the scalar-base + vector-offset form of the
+            // store, no vector add per store.  (stride_b is a launch argument: it cannot be the store's immediate, and at cfg3's
+            // tile stride it would not fit one.)  A cropped window compares the thread's column against wout - a * m1.
             static_for<0, C::RND1>([&](auto r_) {
                 constexpr int r = decltype(r_)::value;
                 int u = t + NT * r;
-                FC_OPAQUE(u);   // twiddle chains and store offsets are recomputed per map, not kept (spilled) across the loop
+                FC_OPAQUE(u);   // the twiddle chain is recomputed per map, not kept (spilled) across the loop
                 int rr, j;
-                const bool slot = row_slot<RPW, C::NB1, NT, r>(u, rr, j);
-                const int row = row0 + rr;
-                if (slot && row < rows) {
+                if (row_slot<RPW, C::NB1, NT, r>(u, rr, j) && row0 + rr < rows) {
                     const c32* buf = lds + rr * LR;
                     c32 p[R1];
-                    stage1_chain(r_, st, p);
                     c32 v[R1];
-                    v[0] = buf[j];
-                    static_for<1, R1>([&](auto c_) {
-                        constexpr int c = decltype(c_)::value;
-                        v[c] = cmulc(buf[c * S1 + j], p[c]);
-                    });
-                    Dft<R1, +1>::run(v);
-                    c32* yrow = ybase + st.yoff[r];
-                    static_for<0, R1>([&](auto a_) {
+                    if constexpr (FC_ROWSM_DBG & 1) {
+                        static_for<0, R1>([&](auto c_) { v[decltype(c_)::value] = st.s[decltype(c_)::value]; });
+                        if (m + 1 < nk && j < kw) stage1_chain(r_, st, p);
+                    } else {
+                    stage1_chain(r_, st, p);
+                    inv_stage1_in<R1, S1>(buf, j, p, v);
+                    }
+                    // (FC_OPAQUE on the offset, in place and free: its zero-extension stays beside the store instead of being
+                    // hoisted out of the walk as a 64-bit pair, which the store could only take through a 64-bit vector add)
+                    // TWO_CHAINS: the odd chain starts m1 = k tiles + h columns further on -- the same tile row k (+ 1 where the
+                    // column wraps into the next tile) and h columns on (or TL - h back): one of two uniform distances
+                    int yoff1 = 0;
+                    if constexpr (TWO_CHAINS) {
+                        const int TL = 1 << g.y_tile_shift, h = m1 & (TL - 1), k = m1 >> g.y_tile_shift;
+                        const int near = tiled ? k * g.y_tile_elems + h : m1, far = tiled ? (k + 1) * g.y_tile_elems + h - TL : m1;
+                        yoff1 = st.yoff[r] + (((j & (TL - 1)) + h >= TL) ? far : near) * (int)sizeof(c32);
+                    }
+                    auto store = [&](auto a_) {
                         constexpr int a = decltype(a_)::value;
-                        int w = j + a * m1;
-                        if (w < g.wout) {
-                            if (tiled) FC_ROWSM_STORE(&yrow[(size_t)(w >> g.y_tile_shift) * g.y_tile_elems + (w & ((1 << g.y_tile_shift) - 1))], v[a]);
-                            else FC_ROWSM_STORE(&yrow[w], v[a]);
-                        }
-                    });
-                    if (m + 1 < nk && j < kw) {   // forward stage 1 of the next map into the cells just read
-                        c32* wbuf = lds + rr * LR;
-                        wbuf[j] = st.x[r];
-                        static_for<1, R1>([&](auto c_) {
-                            constexpr int c = decltype(c_)::value;
-                            wbuf[c * S1 + j] = cmul(st.x[r], p[c]);
+                        int& base = (TWO_CHAINS && (a & 1)) ? yoff1 : st.yoff[r];
+                        FC_OPAQUE(base);
+                        FC_ROWSM_STORE(reinterpret_cast<c32*>(yb + (size_t)((unsigned)(a / SA) * stride_b) + (size_t)(unsigned)base), v[a]);
+                    };
+                    if (g.wout >= L) {   // nothing cropped (uniform)
+                        static_for<0, R1>(store);
+                    } else {             // cropped window (cfg4: 4160 columns of the 4224 transform)
+                        static_for<0, R1>([&](auto a_) {
+                            if (j < g.wout - decltype(a_)::value * m1) store(a_);
                         });
                     }
+                    if (m + 1 < nk && j < kw)     // forward stage 1 of the next map into the cells just read
+                        fwd_stage1_out_pruned<R1, S1>(lds + rr * LR, j, st.x[r], p);
                 }
                 FC_SCHED_FENCE();
             });

@@ -56,16 +56,6 @@ struct DevPhaseCtx {
         f((int)threadIdx.x, st);
         if (!NOSYNC) __syncthreads();
     }
-    // value the accessor designates in lane (this ^ 8): DPP row_ror:8 (rotate by 8 within each
-    // row of 16 lanes), no LDS involved
-    template <class Acc>
-    __device__ __forceinline__ c32 peer8(int, Acc&& acc) {
-        const c32 v = acc(st);
-        c32 r;
-        r.x = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v.x), 0x128, 0xf, 0xf, false));
-        r.y = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v.y), 0x128, 0xf, 0xf, false));
-        return r;
-    }
 };
 
 }  // namespace

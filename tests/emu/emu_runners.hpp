@@ -34,11 +34,6 @@ struct HostPhaseCtx {
     void phase_dbg(F&& f) {
         for (int t = 0; t < NT; t++) f(t, st[t]);
     }
-    // the GPU's lane exchange (DPP row_ror:8): the peer's value was produced in an earlier phase
-    template <class Acc>
-    c32 peer8(int t, Acc&& acc) {
-        return acc(st[t ^ 8]);
-    }
 };
 
 struct EmuFastRows {
