@@ -488,6 +488,11 @@ class Plan:
         _check(self._lib.fftconv_plan_get_option(self._h, name.encode(), ctypes.byref(v)))
         return int(v.value)
 
+    def refresh_info(self):
+        """reads `info` again from the plan and returns it (a call that raised has not refreshed it)"""
+        _check(self._lib.fftconv_plan_get_info(self._h, ctypes.byref(self.info)))
+        return self.info
+
     def profile(self, reset=True):
         pr = Profile()
         _check(self._lib.fftconv_plan_get_profile(self._h, ctypes.byref(pr), 1 if reset else 0))

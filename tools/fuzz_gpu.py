@@ -7,6 +7,10 @@ and a set of plan options (kernel path, walk length, forced block-wise plans, ba
 host copy-out machinery), runs it through the C ABI and compares every map with oracle/ (bar: 1e-5 of the map's maximum; the
 north-star bar is 1e-4).  A failing case prints the line that reproduces it (--seed S --only I) and the run exits non-zero.
 
+Every case builds a fresh plan and sets its options once, before the image.  Options, formats, regions, rectangles, streams and
+kernel preparation changed on a LIVE plan between convolves are tools/plan_walk.py's job (tests/plan_walk.py); the draw here
+stays as it is, because tests/test_gpu_parity.py::test_fuzz_slice pins its seeds.
+
     python tools/fuzz_gpu.py --seconds 240 --seed 1        # as many cases as fit
     python tools/fuzz_gpu.py --cases 40 --seed 7           # what tests/test_gpu_parity.py::test_fuzz_slice runs
 """
