@@ -116,7 +116,7 @@ EXPORTED_SYMBOLS = (
     "fftconv_cache_configure", "fftconv_cache_clear", "fftconv_cache_stats", "fftconv_last_call_timing",
     "fftconv_plan_create", "fftconv_plan_create_ex",
     "fftconv_plan_is_live", "fftconv_plan_destroy", "fftconv_plan_get_info",
-    "fftconv_plan_set_image", "fftconv_plan_spectrum", "fftconv_plan_mark_spectrum_valid",
+    "fftconv_plan_set_image", "fftconv_plan_set_images", "fftconv_plan_spectrum", "fftconv_plan_mark_spectrum_valid",
     "fftconv_plan_use_spectrum_buffer", "fftconv_plan_export_spectrum", "fftconv_plan_import_spectrum",
     "fftconv_plan_convolve", "fftconv_plan_convolve_packed", "fftconv_plan_prepare_kernels_packed",
     "fftconv_plan_synchronize", "fftconv_plan_set_stream",
@@ -181,6 +181,7 @@ def load_library():
     lib.fftconv_plan_destroy.argtypes = [vp]
     lib.fftconv_plan_get_info.argtypes = [vp, ctypes.POINTER(PlanInfo)]
     lib.fftconv_plan_set_image.argtypes = [vp, vp, ci]
+    lib.fftconv_plan_set_images.argtypes = [vp, vp, ci, ci]
     lib.fftconv_plan_spectrum.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(cs)]
     lib.fftconv_plan_mark_spectrum_valid.argtypes = [vp]
     lib.fftconv_plan_use_spectrum_buffer.argtypes = [vp, vp, cs]
@@ -334,6 +335,7 @@ class Plan:
                                                 int(maxKernelW), int(gpuId), ctypes.c_void_p(int(stream) or None), oref))
         self.info = PlanInfo()
         _check(self._lib.fftconv_plan_get_info(self._h, ctypes.byref(self.info)))
+        self._images = 1       # images a convolve covers: what the image entries below last gave the plan (images())
 
     # -- lifetime
     def destroy(self):
@@ -360,12 +362,40 @@ class Plan:
         if d.shape != (self.info.data_h, self.info.data_w, self.info.feature_dim):
             raise FFTConvError(-1, "Invalid data input: shape %s does not match the plan" % (d.shape,))
         _check(self._lib.fftconv_plan_set_image(self._h, ctypes.c_void_p(d.ctypes.data), HOST))
+        self._images = 1
 
     def set_image_device(self, ptr):
         _check(self._lib.fftconv_plan_set_image(self._h, ctypes.c_void_p(int(ptr)), DEVICE))
+        self._images = 1
+
+    def set_images(self, data):
+        """a batch of images: host numpy H x W x F x B float32 in Fortran order (H x W x B where the plan's F is 1).  Every
+        following convolve then returns B * n maps, image-major (fftconv_plan_set_images); set_image returns to one image."""
+        a = np.asarray(data)
+        if a.dtype != np.float32:
+            raise FFTConvError(-1, "data must be single (float32), got %s" % a.dtype)
+        i = self.info
+        if a.ndim == 3 and i.feature_dim == 1:
+            a = a[:, :, None, :]
+        if a.ndim != 4 or a.shape[:3] != (i.data_h, i.data_w, i.feature_dim) or a.shape[3] < 1:
+            raise FFTConvError(-1, "Invalid data input: shape %s is not H x W x F x B of the plan" % (a.shape,))
+        a = np.asfortranarray(a)
+        _check(self._lib.fftconv_plan_set_images(self._h, ctypes.c_void_p(a.ctypes.data), int(a.shape[3]), HOST))
+        self._images = int(a.shape[3])
+
+    def images(self):
+        """images a convolve of this plan covers (its lists hold images() * n maps): what set_images last gave it, else 1.  Kept
+        by this object; the library's own count is get_option("images") (0 while the plan has no image)."""
+        return self._images
+
+    def set_images_device(self, ptr, n):
+        """n images back to back in device memory ([b][f][w][h] floats)"""
+        _check(self._lib.fftconv_plan_set_images(self._h, ctypes.c_void_p(int(ptr)), int(n), DEVICE))
+        self._images = int(n)
 
     def spectrum(self):
-        """(device pointer, bytes) of the image spectrum buffer (for the RCCL broadcast)."""
+        """(device pointer, bytes) of the image spectrum buffer (for the RCCL broadcast); a plan holding B images: all B spectra,
+        image b at b * info.spectrum_bytes."""
         p, n = ctypes.c_void_p(None), ctypes.c_size_t(0)
         _check(self._lib.fftconv_plan_spectrum(self._h, ctypes.byref(p), ctypes.byref(n)))
         return p.value, n.value
@@ -386,10 +416,13 @@ class Plan:
         if a.shape != (i.feature_dim, i.fft_w, i.fft_h // 2 + 1):
             raise FFTConvError(-1, "spectrum must be [F][FFT_W][FFT_H/2+1], got %s" % (a.shape,))
         _check(self._lib.fftconv_plan_import_spectrum(self._h, ctypes.c_void_p(a.ctypes.data), HOST))
+        self._images = 1
 
     def use_spectrum_buffer(self, ptr, nbytes):
-        """keep the image spectrum in caller-owned device memory (e.g. a torch tensor)"""
+        """keep the image spectrum in caller-owned device memory (e.g. a torch tensor); the plan then holds no image until
+        set_image / set_images / mark_spectrum_valid (one image)"""
         _check(self._lib.fftconv_plan_use_spectrum_buffer(self._h, ctypes.c_void_p(int(ptr) or None), int(nbytes)))
+        self._images = 1
 
     def mark_spectrum_valid(self):
         _check(self._lib.fftconv_plan_mark_spectrum_valid(self._h))
@@ -409,17 +442,18 @@ class Plan:
         _check(self._lib.fftconv_plan_get_info(self._h, ctypes.byref(self.info)))   # out_h / out_w follow "output_region"
         oh, ow = self.info.out_h, self.info.out_w
         dt = MAP_DTYPES[self.get_option("map_format")]
+        nmaps = n * self.images()      # a plan holding B images: the flat image-major list, map b * n + k
         if out is None:
-            outs = [np.empty((oh, ow), dtype=dt, order="F") for _ in range(n)]
+            outs = [np.empty((oh, ow), dtype=dt, order="F") for _ in range(nmaps)]
         else:
             outs = list(out)
-            if len(outs) != n:
-                raise FFTConvError(-1, "out must hold one buffer per kernel")
+            if len(outs) != nmaps:
+                raise FFTConvError(-1, "out must hold one buffer per kernel (and per image the plan holds)")
             for o in outs:
                 if (o.dtype != dt or o.shape != (oh, ow)
                         or not o.flags.f_contiguous or not o.flags.writeable):
                     raise FFTConvError(-1, "out buffers must be writable out_h x out_w %s in Fortran order" % dt.name)
-        optr = (ctypes.c_void_p * n)(*[o.ctypes.data for o in outs])
+        optr = (ctypes.c_void_p * nmaps)(*[o.ctypes.data for o in outs])
         _check(self._lib.fftconv_plan_convolve(self._h, n, kptr, kh, kw, HOST, optr, HOST))
         return outs
 
@@ -445,11 +479,12 @@ class Plan:
             ks.append(a)
             ptrs.append(a.ctypes.data), khs.append(a.shape[0]), kws.append(a.shape[1])
         n = len(ptrs)
-        if len(out_ptrs) != n:
-            raise FFTConvError(-1, "out_ptrs must hold one device pointer per kernel")
+        nmaps = n * self.images()      # (a plan holding B images: B * n pointers, image-major)
+        if len(out_ptrs) != nmaps:
+            raise FFTConvError(-1, "out_ptrs must hold one device pointer per kernel (and per image the plan holds)")
         _check(self._lib.fftconv_plan_convolve(self._h, n, (ctypes.c_void_p * n)(*ptrs), (ctypes.c_int * n)(*khs),
                                                (ctypes.c_int * n)(*kws), int(kernel_location),
-                                               (ctypes.c_void_p * n)(*[int(o) for o in out_ptrs]), DEVICE))
+                                               (ctypes.c_void_p * nmaps)(*[int(o) for o in out_ptrs]), DEVICE))
 
     def convolve_packed_device(self, n, kernels_ptr, kh, kw, out_ptr):
         """n equally sized kernels packed in device memory -> n maps packed in device memory (info.out_map_bytes each:

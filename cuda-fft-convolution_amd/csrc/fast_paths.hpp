@@ -437,6 +437,43 @@ inline FastRowsGrid fast_rows_grid(int rows, int rpw, int kernels, int per_wg) {
     return {groups, walks, 8 * ((groups + 7) / 8) * walks};
 }
 
+// ---- Image batches (fftconv_plan_set_images): a launch of the spectral-row kernels covers `images` image spectra times the
+// ---- kernels_per_image kernels of the launch.  The image coordinate is resolved by the __global__ wrappers with the functions
+// ---- below -- scalar arithmetic on the uniform bases of the by-value arguments -- and the specialised bodies run unchanged on
+// ---- ONE image (the generic body is handed the image in its map slot: rows_generic_slot).
+// ---- Written once: the wrappers (kernels_rows_multi.inc, kernels.hip) and the CPU tier (tests/image_batch_host) call this text.
+struct RowsWalk { int image, group, kernel0, nk; };   // kernels [kernel0, kernel0 + nk) of one image, for row group `group`
+FC_HD int rows_images(int images) { return images > 1 ? images : 1; }
+// F = 1 and the generic kernels: a 3-D grid (row group, walk, image) -- blockIdx.z is the image; the grid has exactly the
+// walks of fast_rows_grid, so nk >= 1
+FC_HD RowsWalk rows_walk_3d(int bx, int by, int bz, int kernels_per_image, int per_wg) {
+    const int kernel0 = by * per_wg;
+    return {bz, bx, kernel0, kernels_per_image - kernel0 < per_wg ? kernels_per_image - kernel0 : per_wg};
+}
+// F > 1: the XCD-aware 1-D grid of k_fast_rows_multi_f.  Blocks b and b + 8 share an XCD, XCD x walks the row groups x, x + 8, ...
+// with the (image, walk) pair fastest and the image the slower of the two: the workgroups that read the same F rows of one
+// image's spectrum still sit side by side on one L2.  `walks`: walks per image.  group >= groups: the padding of the last round
+// of XCDs, no work.
+FC_HD RowsWalk rows_walk_flat(int b, int groups, int walks, int images, int kernels_per_image, int per_wg) {
+    const int xcd = b & 7, sq = b >> 3;
+    const int per_group = walks * rows_images(images);
+    const int gl = sq / per_group;
+    const int iw = sq - gl * per_group;
+    const int image = iw / walks;
+    const int walk = iw - image * walks;
+    const int kernel0 = walk * per_wg;
+    return {image, gl * 8 + xcd, kernel0, kernels_per_image - kernel0 < per_wg ? kernels_per_image - kernel0 : per_wg};
+}
+// generic kernel (kernels_body.hpp: spectral_rows_body), grid (row, kernel of the image, image): the map's slot in Y, which the
+// body splits again with SpectralRowsArgs::kernels_per_image
+FC_HD int rows_generic_slot(int by, int bz, int kernels_per_image) { return bz * kernels_per_image + by; }
+// the bases of one image of the launch: its spectrum, and its kernels_per_image slots of the intermediate (in place, in the
+// wrapper's by-value copy of the arguments)
+FC_HD void rows_shift_to_image(const c32*& S, c32*& Y, int image, size_t s_image_stride, int kernels_per_image, size_t y_kernel_stride) {
+    S += (size_t)image * s_image_stride;
+    Y += (size_t)(image * kernels_per_image) * y_kernel_stride;
+}
+
 // Persistent column kernels: as many workgroups as fit at once (LDS-limited), one or two per CU ...
 inline int persistent_want(size_t lds_bytes, int nt, int num_cus) {
     const int by_lds = (int)(FC_LDS_BUDGET / lds_bytes), by_threads = 768 / nt;

@@ -91,6 +91,13 @@ struct FastRowsArgs {
     int y_tile_elems;        // (M+1) * TL
     int y_tile_shift;        // log2(TL)
     unsigned long long* timeline;  // FC_ROWS_TIMELINE builds only: per-phase wall-clock stamps of one workgroup (else unused)
+    // Image batches (fftconv_plan_set_images): a launch covers `images` image spectra, s_image_stride c32 apart from S on, times
+    // kernels_per_image kernels; the maps of image b sit in the slots [b * kernels_per_image, (b + 1) * kernels_per_image) of Y.
+    // Read by the __global__ wrappers only (fast_paths.hpp: rows_shift_to_image), which shift S and Y in their by-value copy and
+    // hand the body the arguments of ONE image; all zero (one image) where nobody sets them.
+    size_t s_image_stride;
+    int images;
+    int kernels_per_image;
 };
 
 // Slot u = t + NT * ROUND of a phase with NB butterflies per row: the workgroup's row rr, the butterfly w within that row, and

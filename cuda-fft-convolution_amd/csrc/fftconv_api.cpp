@@ -69,6 +69,9 @@ BatchSizes batch_sizes(const fftconv_plan* p, int n, int kw) {
     // on a grid that still fills the chip), capped at 5 GiB of intermediate
     b.nbY = (int)p->opt_batch_maps;
     if (b.nbY <= 0) b.nbY = (int)std::max<size_t>(1, std::min<size_t>(64, ((size_t)5120 << 20) / y_bytes));
+    // a plan holding several images: the same bound on the maps of a launch, which may then span images (pipeline.hpp: cut_launches);
+    // the kernels per launch and per chunk below do not depend on the images held (prepared column spectra survive set_images)
+    b.nbM = (int)std::min<long>(b.nbY, (long)n * p->images_held());
     b.nbY = std::min(b.nbY, n);
     // kernels per column-spectrum chunk.  auto: one chunk per launch of the row kernel -- the chunk (138 MB for
     // 64 kernels at cfg3) is then still in the 256-MB Infinity Cache when the row kernel prefetches its rows
@@ -191,16 +194,21 @@ int plan_delivery(fftconv_plan* p, const Sink& sink, int nbY, Delivery& d) {
     return 0;
 }
 
-// spectral rows of ny maps: the column spectra at `a` times the image spectrum, transformed along w into Y
-int launch_spectral_rows_batch(fftconv_plan* p, const c32* a, int kw, int ny) {
+// spectral rows of nb x nk maps: the nk column spectra at `a` times the spectra of the images [b0, b0 + nb), transformed along w into
+// the slots (b - b0) * nk + k of Y -- one launch, the image is a grid coordinate of the kernels (pipeline.hpp: rows_args_set_images;
+// fast_paths.hpp: rows_walk_3d, rows_walk_flat, rows_shift_to_image, rows_generic_slot)
+int launch_spectral_rows_batch(fftconv_plan* p, const c32* a, int kw, int b0, int nb, int nk) {
     const Geometry& g = p->g;
-    if (int rc = p->prof_begin(PK_SPECTRAL, ny)) return rc;
-    if (g.fast_rows.ok) {   // (a walk of one map per workgroup where the multi-map walk is off: rows_group_for)
-        FastRowsArgs fa = fast_rows_args(g, p->d, a, kw, p->spec(), p->Y.p);
-        HIP_TRY(launch_fast_rows_multi(g.Lw, fast_rows_nz2(g, kw), fa, g.rows, ny, g.rows_group_for(ny, p->num_cus), p->stream));
+    const c32* s = p->spec() + (size_t)b0 * g.spectrum_elems();
+    if (int rc = p->prof_begin(PK_SPECTRAL, (long)nb * nk)) return rc;
+    if (g.fast_rows.ok) {   // (a walk of one map per workgroup where the multi-map walk is off: rows_group_for; a walk never crosses an image)
+        FastRowsArgs fa = fast_rows_args(g, p->d, a, kw, s, p->Y.p);
+        rows_args_set_images(fa, g, nb, nk);
+        HIP_TRY(launch_fast_rows_multi(g.Lw, fast_rows_nz2(g, kw), fa, g.rows, nk, g.rows_group_for(nk, p->num_cus), p->stream));
     } else {
-        SpectralRowsArgs sa = spectral_rows_args(g, p->t, p->d, a, kw, p->spec(), p->Y.p);
-        HIP_TRY(launch_spectral_rows(sa, g.rows, ny, rows_threads(g), p->rows_lds(), p->stream));
+        SpectralRowsArgs sa = spectral_rows_args(g, p->t, p->d, a, kw, s, p->Y.p);
+        rows_args_set_images(sa, g, nb, nk);
+        HIP_TRY(launch_spectral_rows(sa, g.rows, nk, rows_threads(g), p->rows_lds(), p->stream));
     }
     return p->prof_end();
 }
@@ -301,7 +309,9 @@ int run_group_impl(fftconv_plan* p, int n, const float* dk, int kh, int kw, cons
     if (int rc = check_kernel_size(p, kh, kw)) return rc;
     if (int rc = flush_pending_prepare(p)) return rc;
     const BatchSizes bs = batch_sizes(p, n, kw);
-    const int nbY = bs.nbY, nbA = bs.nbA;
+    // (a plan holding B images: the maps are the (image, kernel) grid, image-major, and nbY bounds the maps of a launch over it)
+    const int B = p->images_held(), image_stride = sink.image_stride > 0 ? sink.image_stride : n;
+    const int nbY = bs.nbM, nbA = bs.nbA;
     FC_VERBOSE(p, "Kernel size: h=%d, w=%d", kh, kw);                 // src/cudaConvolutionFFT.cu:240
     FC_VERBOSE(p, "N Kernel: %d (maps per launch %d, kernels per column-spectrum chunk %d, %s)", n, nbY, nbA,
                (sink.packed || sink.window) ? "packed device output" : sink.location == FFTCONV_HOST ? "host output" : "device output");   // :68
@@ -309,21 +319,27 @@ int run_group_impl(fftconv_plan* p, int n, const float* dk, int kh, int kw, cons
     if (int rc = p->Y.ensure(g.y_elems_per_kernel() * nbY)) return rc;
     Delivery d;
     if (int rc = plan_delivery(p, sink, nbY, d)) return rc;
-    if (p->Y.fresh)     // before anything is written into it: the tuner may keep another allocation
-        if (int rc = tune_intermediate_placement(p, sink, n, nbY, d.cropped ? p->O.p : d.staged() ? d.stage->p : sink.packed, !d.cropped && !d.staged(), d.kernel_format))
+    if (p->Y.fresh) {   // before anything is written into it: the tuner may keep another allocation
+        // (several images: no automatic tuning -- the tuner's probe launches are shaped for the maps of one image)
+        if (B > 1 && p->opt_tune_placement < 0) p->Y.fresh = false;
+        else if (int rc = tune_intermediate_placement(p, sink, n * B, nbY, d.cropped ? p->O.p : d.staged() ? d.stage->p : sink.packed, !d.cropped && !d.staged(), d.kernel_format))
             return rc;
-    for (int a0 = 0; a0 < n; a0 += nbA) {
-        const int na = std::min(nbA, n - a0);
-        const bool have_cols = a0 == 0 && p->prepared == KernelSet{dk, n, kh, kw, p->stream};
-        p->prepared.dk = nullptr;   // A is about to be consumed / overwritten
-        if (!have_cols)
-            if (int rc = launch_kernel_cols(p, dk, a0, na, kh, kw)) return rc;
-        for (int y0 = 0; y0 < na; y0 += nbY) {
-            const int ny = std::min(nbY, na - y0), first = a0 + y0;
+    }
+    LaunchCutter cutter(B, n, image_stride, nbA, nbY);
+    for (LaunchRect l; cutter.next(l);) {
+        if (l.chunk_start) {
+            const bool have_cols = l.a0 == 0 && p->prepared == KernelSet{dk, n, kh, kw, p->stream};
+            p->prepared.dk = nullptr;   // A is about to be consumed / overwritten
+            if (!have_cols)
+                if (int rc = launch_kernel_cols(p, dk, l.a0, l.na, kh, kw)) return rc;
+        }
+        {
+            const int ny = l.ny(), first = l.first(image_stride);
+            if (B > 1) FC_VERBOSE(p, "images %d..%d x kernels %d..%d", l.b0, l.b0 + l.nb - 1, l.k0, l.k0 + l.nk - 1);
             FC_VERBOSE(p, "maps %d..%d: spectral rows (%s, %d rows x %d points, %d maps per workgroup), output columns (%s, %d-point, %d columns per tile)",
-                       first, first + ny - 1, g.fast_rows.ok ? "specialised" : "generic", g.rows, g.Lw, g.rows_group_for(ny, p->num_cus),
+                       first, first + ny - 1, g.fast_rows.ok ? "specialised" : "generic", g.rows, g.Lw, g.rows_group_for(l.nk, p->num_cus),
                        g.fast_cols.ok ? "specialised" : "generic", g.M, g.fast_cols.ok ? g.fast_cols.T : g.T_cols);
-            if (int rc = launch_spectral_rows_batch(p, p->A.p + (size_t)y0 * bs.per_a, kw, ny)) return rc;
+            if (int rc = launch_spectral_rows_batch(p, p->A.p + (size_t)(l.k0 - l.a0) * bs.per_a, kw, l.b0, l.nb, l.nk)) return rc;
             int buf = 0;
             if (d.route == Route::Ring)
                 if (int rc = ring_claim_staging(p, &buf)) return rc;
@@ -617,17 +633,28 @@ int fftconv_plan_get_info(const fftconv_plan* plan, fftconv_plan_info* info) {
     return 0;
 }
 
-int fftconv_plan_set_image(fftconv_plan* plan, const float* data, int location) {
+// Zero-pad + forward transform of nimg images back to back at `data` ([b][f][w][h]): ONE forward pass over nimg * F planes -- the
+// spectra land [b][f][row][s_pitch] in the spectrum buffer, so the column and row kernels run as for one image with more planes
+// and rows, and the launch count is that of one image.
+static int set_images_impl(fftconv_plan* plan, const float* data, int nimg, int location) {
+    if (nimg < 1) return api_fail(FFTCONV_ERR_INVALID_ARG, "n_images must be at least 1 (got %d)", nimg);
     if (!plan || !data) return api_fail(FFTCONV_ERR_INVALID_ARG, "Invalid data input");
     if (location != FFTCONV_HOST && location != FFTCONV_DEVICE) return api_fail(FFTCONV_ERR_INVALID_ARG, "bad location");
     fftconv_plan* p = plan;
     const Geometry& g = p->g;
+    if (p->tiled && nimg > 1)
+        return api_fail(FFTCONV_ERR_INVALID_ARG, "a block-wise plan (%d blocks) holds one image: its block spectra are kept per image; "
+                        "call fftconv_plan_set_image per image, or create a one-pass plan (fftconv_plan_options.blockwise = 1)", p->tiled->nblk);
+    if (!p->tiled && p->Sx && p->Sx_bytes < (size_t)nimg * g.spectrum_elems() * sizeof(c32))
+        return api_fail(FFTCONV_ERR_INVALID_ARG, "the caller's spectrum buffer (fftconv_plan_use_spectrum_buffer) holds %zu bytes, %d images need %zu",
+                        p->Sx_bytes, nimg, (size_t)nimg * g.spectrum_elems() * sizeof(c32));
     if (int rc = use_device(p)) return rc;
     if (p->tiled) return tiled_set_image(p, data, location);
+    const int planes = nimg * g.F;
     const float* dimg = data;
     bool image_pinned = false;      // the caller's array has been consumed by the CPU: no wait for the GPU at the end
     if (location == FFTCONV_HOST) {
-        const size_t n = (size_t)g.H * g.W * g.F;
+        const size_t n = (size_t)g.H * g.W * planes;      // (the pinned staging takes a whole batch of at most 1 MiB)
         if (p->opt_host_pinned && n * sizeof(float) <= FC_PIN_IMAGE_BYTES) {
             if (int rc = p->pin_img.ensure(n * sizeof(float))) return rc;
             if (int rc = p->pin_img.wait()) return rc;
@@ -648,6 +675,7 @@ int fftconv_plan_set_image(fftconv_plan* plan, const float* data, int location) 
     }
     FC_VERBOSE(p, "Using GPU : %d", p->gpu_id);                                                    // src/cudaConvolutionFFT.cu:87
     FC_VERBOSE(p, "Data size: h=%d, w=%d, f=%d", g.H, g.W, g.F);                                   // :100
+    if (nimg > 1) FC_VERBOSE(p, "Images: %d (one forward pass over %d planes)", nimg, planes);
     char chirp[96] = "";          // windows that do not factor into the radices: Bluestein transforms on longer work lengths
     if (g.bluestein_h() || g.bluestein_w()) {
         char hs[32] = "", ws[32] = "";
@@ -658,13 +686,15 @@ int fftconv_plan_set_image(fftconv_plan* plan, const float* data, int location) 
     FC_VERBOSE(p, "FFT size: h=%d, w=%d (internal transform %d x %d, %s column pass, %s row pass, %s intermediate%s)", g.fft_h, g.fft_w, g.Lh, g.Lw,   // :114
                g.fast_fwd ? "specialised" : "generic", g.fast_rows.ok ? "specialised" : "generic", g.y_tiled() ? "tiled" : "row-major", chirp);
     // (with the fast row kernel the w-pass stores the spectrum directly in that kernel's register order)
-    if (int rc = p->ensure_spectrum()) return rc;
+    p->have_image = false;      // (until the new spectra are queued: a larger batch reallocates the plan's own buffer)
+    p->n_images = 0;
+    if (int rc = p->ensure_spectrum(nimg)) return rc;
     c32* sgen = p->spec();
     if (p->deferred.on && p->deferred.stream != p->stream)
         if (int rc = flush_pending_prepare(p)) return rc;
-    if (int rc = p->prof_begin(PK_IMAGE_COLS, g.F)) return rc;
+    if (int rc = p->prof_begin(PK_IMAGE_COLS, planes)) return rc;
     if (g.fast_fwd) {
-        FastColsFwdArgs fa = fast_cols_fwd_args(g, p->d, dimg, (size_t)g.H * g.W, g.H, g.H, g.W, g.F, sgen,
+        FastColsFwdArgs fa = fast_cols_fwd_args(g, p->d, dimg, (size_t)g.H * g.W, g.H, g.H, g.W, planes, sgen,
                                                 (size_t)g.rows * g.s_pitch, g.s_pitch, false);
         if (p->deferred.on) {
             // the deferred kernel-column pass of fftconv_plan_prepare_kernels_packed and the image's column pass: ONE launch
@@ -679,23 +709,27 @@ int fftconv_plan_set_image(fftconv_plan* plan, const float* data, int location) 
             HIP_TRY(launch_fast_cols_fwd(g.M, g.fast_cols.T, false, fa, p->num_cus, p->stream));
     } else {
         ColsR2CArgs ia = image_cols_args(g, p->t, p->d, dimg, sgen);
-        HIP_TRY(launch_cols_r2c(ia, tiles_for(g.W, g.T_cols), g.F, cols_threads(g), p->cols_lds(), p->stream));
+        HIP_TRY(launch_cols_r2c(ia, tiles_for(g.W, g.T_cols), planes, cols_threads(g), p->cols_lds(), p->stream));
     }
     if (int rc = p->prof_end()) return rc;
     if (image_pinned)
         if (int rc = p->pin_img.mark(p->stream)) return rc;      // the column pass (or the copy) is the last reader
-    if (int rc = p->prof_begin(PK_IMAGE_ROWS, g.F)) return rc;
+    if (int rc = p->prof_begin(PK_IMAGE_ROWS, planes)) return rc;
     if (g.fast_rows.ok) {
-        HIP_TRY(launch_fast_rows_fwd(g.Lw, fast_rows_fwd_args(g, p->d, sgen), g.F * g.rows, p->stream));
+        HIP_TRY(launch_fast_rows_fwd(g.Lw, fast_rows_fwd_args(g, p->d, sgen), planes * g.rows, p->stream));
     } else {
         RowsFwdArgs ra = image_rows_args(g, p->t, p->d, sgen);
-        HIP_TRY(launch_rows_fwd(ra, g.F * g.rows, rows_threads(g), g.rows_fwd_lds_bytes(), p->stream));
+        HIP_TRY(launch_rows_fwd(ra, planes * g.rows, rows_threads(g), g.rows_fwd_lds_bytes(), p->stream));
     }
     if (int rc = p->prof_end()) return rc;
     if (location == FFTCONV_HOST && !image_pinned) HIP_TRY(hipStreamSynchronize(p->stream));
     p->have_image = true;
+    p->n_images = nimg;
     return 0;
 }
+
+int fftconv_plan_set_image(fftconv_plan* plan, const float* data, int location) { return set_images_impl(plan, data, 1, location); }
+int fftconv_plan_set_images(fftconv_plan* plan, const float* data, int n_images, int location) { return set_images_impl(plan, data, n_images, location); }
 
 int fftconv_plan_spectrum(fftconv_plan* plan, void** device_ptr, size_t* bytes) {
     if (!plan) return api_fail(FFTCONV_ERR_INVALID_ARG, "plan is NULL");
@@ -707,9 +741,10 @@ int fftconv_plan_spectrum(fftconv_plan* plan, void** device_ptr, size_t* bytes) 
         if (bytes) *bytes = ts->spec_total() * sizeof(c32);
         return 0;
     }
+    // (a plan holding B images: the whole buffer, image b at b * plan_info.spectrum_bytes)
     if (int rc = plan->ensure_spectrum()) return rc;
     if (device_ptr) *device_ptr = plan->spec();
-    if (bytes) *bytes = plan->g.spectrum_elems() * sizeof(c32);
+    if (bytes) *bytes = plan->g.spectrum_elems() * sizeof(c32) * (size_t)plan->images_held();
     return 0;
 }
 
@@ -722,6 +757,9 @@ static int spectrum_exchange(fftconv_plan* p, float* spectrum, int location, boo
         return api_fail(FFTCONV_ERR_UNSUPPORTED_SIZE,
                     "this plan transforms %dx%d, not the %dx%d window: create it with fftconv_plan_options.exact_window = 1 to exchange "
                     "spectra in the reference's order", g.Lh, g.Lw, g.fft_h, g.fft_w);
+    if (p->have_image && p->n_images > 1)
+        return api_fail(FFTCONV_ERR_INVALID_ARG, "the plan holds %d images (fftconv_plan_set_images): the spectrum in the reference's order is "
+                        "exchanged for one image -- call fftconv_plan_set_image first", p->n_images);
     if (to_natural && !p->have_image) return api_fail(FFTCONV_ERR_NO_IMAGE, "no image spectrum: call fftconv_plan_set_image first");
     if (int rc = use_device(p)) return rc;
     if (int rc = p->ensure_spectrum()) return rc;
@@ -744,7 +782,7 @@ static int spectrum_exchange(fftconv_plan* p, float* spectrum, int location, boo
         if (to_natural) HIP_TRY(hipMemcpyAsync(spectrum, nat, n * sizeof(c32), hipMemcpyDeviceToHost, p->stream));
         HIP_TRY(hipStreamSynchronize(p->stream));
     }
-    if (!to_natural) p->have_image = true;
+    if (!to_natural) { p->have_image = true; p->n_images = 1; }
     return 0;
 }
 
@@ -765,8 +803,11 @@ int fftconv_plan_use_spectrum_buffer(fftconv_plan* plan, void* device_ptr, size_
         plan->tiled->have_image = false;
         return 0;
     }
+    // (need: one image; fftconv_plan_set_images checks the size again for its batch)
     plan->Sx = reinterpret_cast<c32*>(device_ptr);
+    plan->Sx_bytes = device_ptr ? bytes : 0;
     plan->have_image = false;
+    plan->n_images = 0;
     return 0;
 }
 
@@ -779,6 +820,7 @@ int fftconv_plan_mark_spectrum_valid(fftconv_plan* plan) {
     }
     if (!plan->spec()) return api_fail(FFTCONV_ERR_NO_IMAGE, "the plan has no spectrum buffer yet (fftconv_plan_spectrum / fftconv_plan_use_spectrum_buffer)");
     plan->have_image = true;
+    if (plan->n_images < 1) plan->n_images = 1;
     return 0;
 }
 
@@ -849,6 +891,9 @@ int fftconv_plan_convolve(fftconv_plan* plan, int n_kernel, const float* const* 
         if (!kernels[k] || !out[k]) return api_fail(FFTCONV_ERR_INVALID_ARG, "kernel or output %d is NULL", k);
         if (int rc = check_kernel_size(p, kernel_h[k], kernel_w[k])) return rc;
     }
+    // (a plan holding B images: out[] has B * n_kernel entries, image-major -- out[b * n_kernel + k] is image b (x) kernel k)
+    for (long m = n_kernel; m < (long)n_kernel * p->images_held(); m++)
+        if (!out[m]) return api_fail(FFTCONV_ERR_INVALID_ARG, "output %ld is NULL (the plan holds %d images: %ld maps)", m, p->n_images, (long)n_kernel * p->n_images);
     // groups of consecutive kernels of equal size
     for (int k0 = 0, k1; k0 < n_kernel; k0 = k1) {
         k1 = same_size_run_end(kernel_h, kernel_w, k0, n_kernel);
@@ -874,6 +919,7 @@ int fftconv_plan_convolve(fftconv_plan* plan, int n_kernel, const float* const* 
         Sink sink;
         sink.ptrs = out + k0;
         sink.location = out_location;
+        sink.image_stride = n_kernel;
         const int rcg = run_group(p, n, dk, kh, kw, sink);
         if (kernels_pinned) {      // (whatever the group's outcome: the launches that read the buffer are in the stream)
             if (rcg) (void)keep_error([&] { return p->pin_k.mark(p->stream); });
@@ -1013,6 +1059,8 @@ int fftconv_plan_get_option(fftconv_plan* plan, const char* name, long* value) {
     if (!strcmp(name, "rect_store")) { *value = plan->opt_rect_store; return 0; }
     if (!strcmp(name, "blockwise")) { *value = plan->tiled ? plan->tiled->nblk : 0; return 0; }   // read-only: number of blocks (0 = one pass)
     if (!strcmp(name, "overlap_save")) { *value = plan->tiled && plan->tiled->save ? 1 : 0; return 0; }   // read-only: blocks stored by the output kernel (1) or summed (0)
+    // read-only: the images the plan holds -- fftconv_plan_set_images' count, 1 after fftconv_plan_set_image, 0 before any image
+    if (!strcmp(name, "images")) { *value = plan->tiled ? (plan->tiled->have_image ? 1 : 0) : (plan->have_image ? plan->images_held() : 0); return 0; }
     if (plan->tiled && strcmp(name, "output_region")) return fftconv_plan_get_option(plan->tiled->sub, name, value);
     if (const LongOption* o = find_option(name, OPT_SET_ONLY)) { *value = plan->*(o->member); return 0; }
     if (!strcmp(name, "rows_group")) { *value = plan->g.rows_group; return 0; }

@@ -32,7 +32,10 @@ __global__ void __launch_bounds__(512) k_rows_fwd(RowsFwdArgs a) {
 template <int BS>
 __global__ void __launch_bounds__(512) k_spectral_rows(SpectralRowsArgs a) {
     DevCtx ctx{(int)threadIdx.x, (int)blockDim.x};
-    spectral_rows_body<BS>(ctx, reinterpret_cast<c32*>(fc_smem), a, (int)blockIdx.x, (int)blockIdx.y);
+    // blockIdx.z: the image of a batch.  The body takes it folded into the map slot (rows_generic_slot): shifting S and Y here
+    // needs a private copy of the arguments, and the stage table in it (FftDesc, indexed at run time) then lives in scratch.
+    // (a.kernels_per_image is what the body splits the slot with; 0 -- nobody set it -- is one image, blockIdx.z = 0)
+    spectral_rows_body<BS>(ctx, reinterpret_cast<c32*>(fc_smem), a, (int)blockIdx.x, rows_generic_slot((int)blockIdx.y, (int)blockIdx.z, a.kernels_per_image));
 }
 
 template <int BS>
@@ -194,6 +197,7 @@ hipError_t launch_fast_rows_fwd(int L, const FastRowsFwdArgs& a, int rows, hipSt
 hipError_t launch_fast_rows_multi(int L, int nz2, const FastRowsArgs& a, int rows, int kernels, int kernels_per_wg, hipStream_t s) {
     if (rows <= 0 || kernels <= 0) return hipSuccess;
     if (a.F < 1 || kernels_per_wg < 1) return hipErrorInvalidValue;
+    if (a.images > 1 && a.kernels_per_image != kernels) return hipErrorInvalidValue;   // (image batches: `kernels` counts per image)
     return in_first_group<FC_ROW_GROUPS>([&](auto g) { return launch_fast_rows_multi_group<g.value>(L, nz2, a, rows, kernels, kernels_per_wg, s); });
 }
 
@@ -255,8 +259,12 @@ hipError_t launch_rows_fwd(const RowsFwdArgs& a, int rows, int threads, size_t l
 }
 hipError_t launch_spectral_rows(const SpectralRowsArgs& a, int rows, int kernels, int threads, size_t lds_bytes, hipStream_t s) {
     if (rows <= 0 || kernels <= 0) return hipSuccess;
-    if (a.fd.bs_work > 0) hipLaunchKernelGGL(k_spectral_rows<1>, dim3(rows, kernels), dim3(threads), lds_bytes, s, a);
-    else hipLaunchKernelGGL(k_spectral_rows<0>, dim3(rows, kernels), dim3(threads), lds_bytes, s, a);
+    // (image batches: `kernels` per image, a.images images -- a.kernels_per_image places an image's maps in Y)
+    // (where it is set at all it must be the launch's kernel count: the body splits every slot with it)
+    if ((a.images > 1 || a.kernels_per_image != 0) && a.kernels_per_image != kernels) return hipErrorInvalidValue;
+    const dim3 grid(rows, kernels, rows_images(a.images));
+    if (a.fd.bs_work > 0) hipLaunchKernelGGL(k_spectral_rows<1>, grid, dim3(threads), lds_bytes, s, a);
+    else hipLaunchKernelGGL(k_spectral_rows<0>, grid, dim3(threads), lds_bytes, s, a);
     return hipGetLastError();
 }
 hipError_t launch_cols_c2r(const ColsC2RArgs& a, int tiles, int kernels, int threads, size_t lds_bytes, hipStream_t s) {

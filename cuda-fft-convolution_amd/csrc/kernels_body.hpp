@@ -153,6 +153,11 @@ struct SpectralRowsArgs {
     const c32* tw;
     int acc_in_y;        // F > 1: the feature sum accumulates in this kernel's row of Y (global memory) instead of
                          // LDS -- Bluestein rows whose work buffer and accumulator do not fit the LDS together
+    // image batches, as FastRowsArgs (fast_rows.hpp); all zero = one image.  Here the body resolves the image itself, from the
+    // map slot it is handed as `kernel` (see there)
+    size_t s_image_stride;
+    int images;
+    int kernels_per_image;
 };
 
 // lds: the work buffer (fft_work_length c32: Lw, or the Bluestein work length), for F > 1 followed by an Lw-c32
@@ -162,12 +167,16 @@ template <int BS = -1, class Ctx>
 FC_HD void spectral_rows_body(const Ctx& ctx, c32* lds, const SpectralRowsArgs& a, int row, int kernel) {
     const int L = a.fd.L;
     c32* buf = lds;
+    // Image batches (a.kernels_per_image > 0): `kernel` is the map's slot in Y, image * kernels_per_image + kernel of the image
+    // (rows_generic_slot); the slot places the row in Y as ever, the image picks the spectrum, the remainder the kernel
+    const int image = a.kernels_per_image > 0 ? kernel / a.kernels_per_image : 0;
+    const int ka = kernel - image * a.kernels_per_image;
     c32* yrow = a.Y + (size_t)kernel * a.y_kernel_stride + (size_t)row * a.y_pitch;
     // (in Y: every thread reads back only the elements it wrote itself, and the row is overwritten by the store below)
     c32* acc = a.acc_in_y ? yrow : lds + fft_work_length(a.fd);
     for (int f = 0; f < a.F; f++) {
-        const c32* arow = a.A + (size_t)kernel * a.a_kernel_stride + (size_t)f * a.a_feat_stride + (size_t)row * a.a_pitch;
-        const c32* srow = a.S + (size_t)f * a.s_feat_stride + (size_t)row * a.s_pitch;
+        const c32* arow = a.A + (size_t)ka * a.a_kernel_stride + (size_t)f * a.a_feat_stride + (size_t)row * a.a_pitch;
+        const c32* srow = a.S + (size_t)image * a.s_image_stride + (size_t)f * a.s_feat_stride + (size_t)row * a.s_pitch;
         for (int x = ctx.tid; x < L; x += ctx.nthreads) buf[x] = (x < a.kw) ? arow[x] : mk(0.f, 0.f);
         ctx.sync();
         fft_forward<BS>(ctx, buf, L, 1, a.fd, a.tw);

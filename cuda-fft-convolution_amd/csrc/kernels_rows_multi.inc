@@ -8,11 +8,12 @@ namespace {
 
 template <class Cfg, int NZ2, bool LINEAR>
 __global__ void __launch_bounds__(Cfg::NT, 3) k_fast_rows_multi(FastRowsArgs a, int rows, int kernels, int per_wg) {
-    const int group = (int)blockIdx.x;
-    const int kernel0 = (int)blockIdx.y * per_wg;
-    const int nk = kernels - kernel0 < per_wg ? kernels - kernel0 : per_wg;
+    // (`kernels`: the kernels per image of the launch; blockIdx.z: the image of a batch -- its spectrum and its slots of the
+    //  intermediate are two scalar multiply-adds on the uniform bases, the body sees one image)
+    const RowsWalk w = rows_walk_3d((int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, kernels, per_wg);
+    rows_shift_to_image(a.S, a.Y, w.image, a.s_image_stride, kernels, a.y_kernel_stride);
     DevPhaseCtx<RowMultiState<Cfg>> ctx;
-    fast_rows_multi_body<Cfg, NZ2, LINEAR>(ctx, reinterpret_cast<c32*>(fc_smem), a, group, kernel0, nk, rows);
+    fast_rows_multi_body<Cfg, NZ2, LINEAR>(ctx, reinterpret_cast<c32*>(fc_smem), a, w.group, w.kernel0, w.nk, rows);
 }
 
 // (Keep the F > 1 kernels in THIS translation unit: compiled in one of their own -- tried for the build time --
@@ -21,18 +22,15 @@ __global__ void __launch_bounds__(Cfg::NT, 3) k_fast_rows_multi(FastRowsArgs a, 
 // F > 1: the walk over (map, feature) pairs.  XCD-aware 1-D grid as k_fast_rows' order 2: blocks b and b + 8
 // share an XCD (round-robin dispatch; a speed assumption only), XCD x walks row groups x, x + 8, ... with the
 // walk index fastest, so the workgroups that need the same F image-spectrum rows run side by side on one L2.
+// Image batches: the walk index runs over (image, walk) pairs, the image the slower of the two (fast_paths.hpp: rows_walk_flat);
+// `kernels` and `walks` count per image, a.images is the number of images of the launch.
 template <class Cfg, int NZ2, bool LINEAR>
 __global__ void __launch_bounds__(Cfg::NT, 3) k_fast_rows_multi_f(FastRowsArgs a, int rows, int kernels, int per_wg, int groups, int walks) {
-    const int b = (int)blockIdx.x;
-    const int xcd = b & 7, sq = b >> 3;
-    const int gl = sq / walks;
-    const int walk = sq - gl * walks;
-    const int group = gl * 8 + xcd;
-    if (group >= groups) return;
-    const int kernel0 = walk * per_wg;
-    const int nk = kernels - kernel0 < per_wg ? kernels - kernel0 : per_wg;
+    const RowsWalk w = rows_walk_flat((int)blockIdx.x, groups, walks, a.images, kernels, per_wg);
+    if (w.group >= groups) return;
+    rows_shift_to_image(a.S, a.Y, w.image, a.s_image_stride, kernels, a.y_kernel_stride);
     DevPhaseCtx<RowMultiState<Cfg, true>> ctx;
-    fast_rows_multi_body<Cfg, NZ2, LINEAR, true>(ctx, reinterpret_cast<c32*>(fc_smem), a, group, kernel0, nk, rows);
+    fast_rows_multi_body<Cfg, NZ2, LINEAR, true>(ctx, reinterpret_cast<c32*>(fc_smem), a, w.group, w.kernel0, w.nk, rows);
 }
 
 // resident workgroups per CU of the F = 1 multi-map kernel a launch with these arguments would use (the runtime's
@@ -61,9 +59,10 @@ struct FastRowsMultiLauncher {
     void go() {
         const size_t lds = (size_t)Cfg::LDS_ELEMS * sizeof(c32);
         const FastRowsGrid g = fast_rows_grid(rows, Cfg::RPW, kernels, per_wg);
+        const int images = rows_images(a.images);      // (`kernels`: per image)
         fast_rows_visit_linear<Cfg>(a, [&](auto linear) {
-            if (a.F > 1) err = launch_lds<k_fast_rows_multi_f<Cfg, NZ2, linear.value>>(dim3(g.flat), Cfg::NT, lds, s, a, rows, kernels, per_wg, g.groups, g.walks);
-            else err = launch_lds<k_fast_rows_multi<Cfg, NZ2, linear.value>>(dim3(g.groups, g.walks), Cfg::NT, lds, s, a, rows, kernels, per_wg);
+            if (a.F > 1) err = launch_lds<k_fast_rows_multi_f<Cfg, NZ2, linear.value>>(dim3(g.flat * images), Cfg::NT, lds, s, a, rows, kernels, per_wg, g.groups, g.walks);
+            else err = launch_lds<k_fast_rows_multi<Cfg, NZ2, linear.value>>(dim3(g.groups, g.walks, images), Cfg::NT, lds, s, a, rows, kernels, per_wg);
         });
     }
 };

@@ -313,6 +313,61 @@ inline FastColsFwdArgs fast_cols_fwd_args(const Geometry& g, const DeviceTables&
     return a;
 }
 
+// Image batches: the image coordinate of a spectral-row launch (FastRowsArgs / SpectralRowsArgs) -- `images` spectra from a.S on,
+// one per spectrum_elems, times the nk kernels of the launch
+template <class Args>
+inline void rows_args_set_images(Args& a, const Geometry& g, int images, int nk) {
+    a.s_image_stride = g.spectrum_elems(); a.images = images; a.kernels_per_image = nk;
+}
+
+// Launch cutting of a convolve on a plan that holds B images: the maps are the (image, kernel) grid, image-major -- map
+// b * image_stride + k is image b (x) kernel k of the group (image_stride: the kernels of the whole call, >= n).  One spectral-row /
+// output launch covers a rectangle of that grid, images [b0, b0 + nb) x kernels [k0, k0 + nk), whose maps sit in the slots
+// (b - b0) * nk + (k - k0) of the intermediate and must be consecutive in the output: one image x a kernel range, or several
+// whole images x every kernel of the call -- the latter only where the column-spectrum chunk holds all of them.  The kernels'
+// column spectra are produced per chunk of nbA kernels (`chunk_start`: this launch is the first of its chunk); a launch has at
+// most nbY maps.  B = 1 gives the (first, ny) sequence of a one-image plan.
+struct LaunchRect {
+    int b0, nb, k0, nk;      // k0 counts from the start of the group
+    int a0, na;              // the chunk of kernels [a0, a0 + na) whose column spectra the launch reads (k0 - a0: its offset in A)
+    bool chunk_start;
+    int first(int image_stride) const { return b0 * image_stride + k0; }
+    int ny() const { return nb * nk; }
+};
+// The launches one after the other, without a list of them (the per-kernel loop of a convolve allocates nothing on the host
+// either): chunks outermost, then images, then kernel ranges of the chunk -- a chunk's column spectra serve every image.
+struct LaunchCutter {
+    int B, n, image_stride, nbA, nbY;
+    int a0 = 0, b = 0, y0 = 0;       // the next launch: chunk start, image, kernel offset within the chunk
+    bool start = true;               // ... is the first of its chunk
+    LaunchCutter(int B_, int n_, int image_stride_, int nbA_, int nbY_)
+        : B(B_), n(n_), image_stride(image_stride_), nbA(std::max(1, nbA_)), nbY(std::max(1, nbY_)) {}
+    bool next(LaunchRect& r) {
+        if (B < 1 || n < 1 || a0 >= n) return false;
+        const int na = std::min(nbA, n - a0);
+        if (na == n && image_stride == n && nbY >= n) {      // whole images x all kernels of the call
+            const int per = nbY / n;
+            r = {b, std::min(per, B - b), 0, n, a0, na, start};
+            b += per;
+        } else {                                             // one image x a kernel range of the chunk
+            const int step = std::min(nbY, na);
+            r = {b, 1, a0 + y0, std::min(step, na - y0), a0, na, start};
+            y0 += step;
+            if (y0 >= na) { y0 = 0; b++; }
+        }
+        start = false;
+        if (b >= B) { b = 0; y0 = 0; a0 += nbA; start = true; }
+        return true;
+    }
+};
+// the same as a list (the CPU tier checks it)
+inline std::vector<LaunchRect> cut_launches(int B, int n, int image_stride, int nbA, int nbY) {
+    std::vector<LaunchRect> r;
+    LaunchCutter cut(B, n, image_stride, nbA, nbY);
+    for (LaunchRect l; cut.next(l);) r.push_back(l);
+    return r;
+}
+
 inline int fast_rows_nz2(const Geometry& g, int kw) { return (kw + g.fast_rows.R3 - 1) / g.fast_rows.R3; }
 
 inline ColsC2RArgs cols_c2r_args(const Geometry& g, const Tables& t, const DeviceTables& d,

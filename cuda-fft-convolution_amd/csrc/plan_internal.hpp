@@ -227,8 +227,14 @@ struct fftconv_plan {
     DevBuf<int> fr_map, fc_rowoff, fc_pair_row_of, nat_row_of, nat_col_of;
     DevBuf<c32> S;     // image spectrum (own buffer)
     c32* Sx = nullptr; // caller-owned spectrum buffer, if any
+    size_t Sx_bytes = 0;   // ... and its size (fftconv_plan_use_spectrum_buffer)
+    // Images the plan holds (fftconv_plan_set_images; set_image: 1; 0 before any image and after the spectrum was invalidated):
+    // their spectra lie [b][f][row][s_pitch] in the spectrum buffer, g.spectrum_elems() apart
+    int n_images = 0;
+    int images_held() const { return n_images > 1 ? n_images : 1; }   // what the spectrum buffer is sized and reported for
     c32* spec() const { return Sx ? Sx : S.p; }   // S is allocated by the first use that needs it (ensure_spectrum)
-    int ensure_spectrum() { return Sx ? 0 : S.ensure(g.spectrum_elems()); }
+    // (the own buffer grows on demand: a larger batch reallocates it, and its contents are then gone -- the callers write all of it)
+    int ensure_spectrum(int images = 0) { return Sx ? 0 : S.ensure(g.spectrum_elems() * (size_t)(images > 0 ? images : images_held())); }
     DevBuf<c32> A;     // kernel column spectra of the current chunk
     DevBuf<c32> Y;     // intermediate of the current map batch
     DevBuf<float> K;   // packed kernels staged on the device
@@ -369,11 +375,15 @@ struct Sink {
     float* const* ptrs = nullptr;   // or one pointer per map
     int location = FFTCONV_DEVICE;  // of ptrs
     const OutWindow* window = nullptr;   // or (block plan of an overlap-save plan) the output kernel stores this window of the full maps
+    // a plan holding several images: maps between the first maps of two images in `packed` / `ptrs` -- the kernels of the whole
+    // call, of which the group may be a part (ragged cells); 0 = the kernels of the group
+    int image_stride = 0;
 };
 
 struct BatchSizes {
     size_t per_a;  // c32 of column spectrum per kernel
-    int nbY;       // maps per spectral/output launch
+    int nbY;       // maps per spectral/output launch (kernels of one image)
+    int nbM;       // maps per launch over the images the plan holds (>= nbY; equal on a one-image plan)
     int nbA;       // kernels per column-spectrum chunk (a multiple of nbY)
 };
 

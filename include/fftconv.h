@@ -247,8 +247,33 @@ int fftconv_plan_get_info(const fftconv_plan *plan, fftconv_plan_info *info);
  * up to 1 MiB -- in which case the call does not wait for the GPU at all); the spectrum is ordered on the plan's stream like
  * any other work of the plan.  A caller that reads fftconv_plan_spectrum() on ANOTHER stream orders that stream behind the
  * plan's (an event, or fftconv_plan_synchronize) whatever the location.  Device input: `data` must stay valid until the
- * stream has passed the transform. */
+ * stream has passed the transform.
+ * A call that fails with an argument error leaves the plan as it was.  One that fails later -- an allocation, a copy or a launch
+ * (FFTCONV_ERR_ALLOC / FFTCONV_ERR_HIP) -- leaves the plan WITHOUT an image once the transform has been started (option "images" reads 0,
+ * a convolve fails with FFTCONV_ERR_NO_IMAGE): the spectrum buffer may have been reallocated or half overwritten by then.  The same holds for
+ * fftconv_plan_set_images. */
 int fftconv_plan_set_image(fftconv_plan *plan, const float *data, int location);
+
+/* Image batches: the plan holds n_images images of its size and convolves ALL of them with the kernels of every following call --
+ * video frames, equal-sized pyramid levels, tiles.  `data`: n_images images back to back ([b][f][w][h], each as
+ * fftconv_plan_set_image takes it), host or device memory; ordering and consumption as for fftconv_plan_set_image (queued on the
+ * plan's stream; host data consumed on return; the pinned staging takes a whole batch of at most 1 MiB).  The batch is ONE forward
+ * pass over n_images * F planes -- the launches of one image -- and a convolve puts the (image, kernel) grid behind its launches:
+ * where n_images * n_kernel maps fit one launch ("batch_maps"), one spectral-row launch and one output launch in all.
+ *   fftconv_plan_convolve_packed  writes n_images * n_kernel consecutive maps, image-major: map b * n_kernel + k is image b (x) kernel k.
+ *   fftconv_plan_convolve         takes out[] with n_images * n_kernel pointers in the same order; kernels[] keeps n_kernel entries
+ *                                 (ragged cells as ever).
+ * Every output option ("map_format", fftconv_plan_set_output_rect, "output_region", "flip_kernels") and every delivery route acts
+ * per map; fftconv_plan_prepare_kernels_packed and "defer_prepare" work (the kernel half does not depend on the images).  After one
+ * warm-up call with the same arguments fftconv_plan_set_images(DEVICE) + fftconv_plan_convolve_packed allocate nothing and never
+ * synchronise.  The spectrum buffer grows on demand: fftconv_plan_spectrum returns n_images * plan_info.spectrum_bytes, image b at
+ * offset b * spectrum_bytes (spectrum_bytes stays the size of ONE image); a caller's buffer (fftconv_plan_use_spectrum_buffer) must
+ * hold that much.  fftconv_plan_set_image means one image and returns the plan to one image; read-only option "images" tells how
+ * many the plan holds (0 before any).  FFTCONV_ERR_INVALID_ARG, the plan's state untouched: n_images < 1; n_images > 1 on a
+ * block-wise plan ("blockwise" > 0: block spectra are kept per image); a caller's spectrum buffer that is too small.  While a plan
+ * holds more than one image fftconv_plan_export_spectrum / _import_spectrum fail with FFTCONV_ERR_INVALID_ARG, and "tune_placement"
+ * -1 (automatic) does not tune.  fftconv_multi_*, the one-shot and the two-step entries take one image. */
+int fftconv_plan_set_images(fftconv_plan *plan, const float *data, int n_images, int location);
 
 /* Device pointer + size of the image spectrum (library-owned, valid until destroy).  This is the
  * buffer the multi-GPU path broadcasts (the reference's cudaMemcpyPeerAsync of d_CFFT_DATA,
@@ -409,7 +434,8 @@ int fftconv_plan_set_output_rect(fftconv_plan *plan, int off_h, int off_w, int o
  * and "tuned_best" (index of the one kept), "blockwise" (blocks of a block-wise plan, 0 = one pass), "overlap_save" (1: the blocks are stored by the output kernel),
  * "rows_slots_per_cu" (workgroups of the multi-map row kernel a CU holds at once: what the walk length is chosen for),
  * "specialised_kernels" (bit 0: the spectral-row pass runs on a specialised kernel, bit 1: the column passes do; 3 = no
- * generic kernel runs for this plan). */
+ * generic kernel runs for this plan), "images" (images the plan holds: fftconv_plan_set_images' n_images, 1 after
+ * fftconv_plan_set_image, 0 before any image). */
 int fftconv_plan_get_option(fftconv_plan *plan, const char *name, long *value);
 
 typedef struct fftconv_profile {
