@@ -269,8 +269,8 @@ int tiled_convolve_save(fftconv_plan* p, int n, const float* const* kernels, con
                 win.base = big + (size_t)gr.first * big_map + ((ptrdiff_t)(x0 - ts->Sw) * ts->FH + (y0 - ts->Sh));
                 // one group that fits one chunk of column spectra: block 0 left the kernels' column spectra in the block plan
                 // (every block runs the same transform), the other blocks reuse them
-                if (b > 0 && groups.size() == 1 && gr.count <= batch_sizes(sub, gr.count, kw[k0 + gr.first]).nbA && !sub->deferred.on)
-                    sub->prepared = KernelSet{gr.dk, gr.count, kh[k0 + gr.first], kw[k0 + gr.first], sub->stream};
+                if (b > 0 && groups.size() == 1 && gr.count <= batch_sizes(sub, gr.count, kw[k0 + gr.first]).nbA)
+                    sub->a_holds.adopt(KernelSet{gr.dk, gr.count, kh[k0 + gr.first], kw[k0 + gr.first], sub->stream});
                 if (int rc = run_group(sub, gr.count, gr.dk, kh[k0 + gr.first], kw[k0 + gr.first], sink)) return rc;
             }
         }

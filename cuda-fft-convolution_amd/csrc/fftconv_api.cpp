@@ -130,14 +130,13 @@ int launch_kernel_cols(fftconv_plan* p, const float* dk, int a0, int na, int kh,
 
 // the deferred kernel-column pass of fftconv_plan_prepare_kernels_packed, on its own (no set_image came first)
 int flush_pending_prepare(fftconv_plan* p) {
-    if (!p->deferred.on) return 0;
-    const auto pd = p->deferred;
-    p->deferred.on = false;
+    ColumnCache::Request pd;
+    if (!p->a_holds.take_pending(pd)) return 0;
     const hipStream_t cur = p->stream;
-    p->stream = pd.stream;                      // where the caller ordered the kernels' readiness
+    p->stream = static_cast<hipStream_t>(pd.stream);   // where the caller ordered the kernels' readiness
     const int rc = launch_kernel_cols(p, pd.dk, 0, pd.na, pd.kh, pd.kw);
     p->stream = cur;
-    if (!rc) p->prepared = pd;
+    if (!rc) p->a_holds.ready(pd);
     return rc;
 }
 
@@ -305,7 +304,7 @@ int deliver_batch(fftconv_plan* p, const Delivery& d, const Sink& sink, int firs
 // for the staging buffer, output columns, crop or pad, then the batch's delivery.
 int run_group_impl(fftconv_plan* p, int n, const float* dk, int kh, int kw, const Sink& sink) {
     const Geometry& g = p->g;
-    if (!p->have_image) return api_fail(FFTCONV_ERR_NO_IMAGE, "no image spectrum: call fftconv_plan_set_image first");
+    if (!p->have_image()) return api_fail(FFTCONV_ERR_NO_IMAGE, "no image spectrum: call fftconv_plan_set_image first");
     if (int rc = check_kernel_size(p, kh, kw)) return rc;
     if (int rc = flush_pending_prepare(p)) return rc;
     const BatchSizes bs = batch_sizes(p, n, kw);
@@ -328,8 +327,7 @@ int run_group_impl(fftconv_plan* p, int n, const float* dk, int kh, int kw, cons
     LaunchCutter cutter(B, n, image_stride, nbA, nbY);
     for (LaunchRect l; cutter.next(l);) {
         if (l.chunk_start) {
-            const bool have_cols = l.a0 == 0 && p->prepared == KernelSet{dk, n, kh, kw, p->stream};
-            p->prepared.dk = nullptr;   // A is about to be consumed / overwritten
+            const bool have_cols = p->a_holds.consume(KernelSet{dk, n, kh, kw, p->stream}) && l.a0 == 0;   // A is about to be consumed / overwritten
             if (!have_cols)
                 if (int rc = launch_kernel_cols(p, dk, l.a0, l.na, kh, kw)) return rc;
         }
@@ -362,7 +360,7 @@ int run_group_impl(fftconv_plan* p, int n, const float* dk, int kh, int kw, cons
 enum : unsigned {
     OPT_BOOL = 1,       // stored as value != 0
     OPT_REJECT = 2,     // a value outside [lo, hi] is an error (otherwise it is clamped)
-    OPT_FORGETS = 4,    // the kernel column spectra in A depend on it: forget_prepared
+    OPT_FORGETS = 4,    // the kernel column spectra in A depend on it: ColumnCache::forget
     OPT_RING = 8,       // the host-output ring is sized by it: torn down, rebuilt by the next host-output call
     OPT_GET_ONLY = 16,  // get_option only: read-only, or set_option handles the name in code
     OPT_SET_ONLY = 32,
@@ -422,6 +420,25 @@ int run_group(fftconv_plan* p, int n, const float* dk, int kh, int kw, const Sin
     const int rc = run_group_impl(p, n, dk, kh, kw, sink);
     if (rc && p->ring) (void)keep_error([&] { return p->ring->wait_idle(); });
     return rc;
+}
+
+int prepare_kernels(fftconv_plan* p, int n, const float* dk, int kh, int kw, bool force_defer) {
+    if (int rc = use_device(p)) return rc;
+    if (int rc = check_kernel_size(p, kh, kw)) return rc;
+    const BatchSizes bs = batch_sizes(p, n, kw);
+    if (int rc = flush_pending_prepare(p)) return rc;      // an earlier request nobody consumed
+    if (int rc = p->A.ensure(bs.per_a * bs.nbA)) return rc;
+    p->a_holds.forget();      // (a launch that fails below leaves nothing behind)
+    const KernelSet ks{dk, n, kh, kw, p->stream};
+    const int na = std::min(bs.nbA, n);
+    const bool timed_apart = p->profile && (p->profile_mask & ((1u << PK_KERNEL_COLS) | (1u << PK_IMAGE_COLS)));   // per-kind figures wanted
+    if ((force_defer || p->opt_defer_prepare) && p->g.fast_fwd && !p->opt_flip_kernels && !timed_apart) {   // deferred: rides in the launch of the next image's column pass
+        p->a_holds.request(ks, na);
+        return 0;
+    }
+    if (int rc = launch_kernel_cols(p, dk, 0, na, kh, kw)) return rc;
+    p->a_holds.ready(ks);
+    return 0;
 }
 
 int check_thread_size(const double* thread_size, int n_thread_size) {
@@ -686,25 +703,23 @@ static int set_images_impl(fftconv_plan* plan, const float* data, int nimg, int 
     FC_VERBOSE(p, "FFT size: h=%d, w=%d (internal transform %d x %d, %s column pass, %s row pass, %s intermediate%s)", g.fft_h, g.fft_w, g.Lh, g.Lw,   // :114
                g.fast_fwd ? "specialised" : "generic", g.fast_rows.ok ? "specialised" : "generic", g.y_tiled() ? "tiled" : "row-major", chirp);
     // (with the fast row kernel the w-pass stores the spectrum directly in that kernel's register order)
-    p->have_image = false;      // (until the new spectra are queued: a larger batch reallocates the plan's own buffer)
-    p->n_images = 0;
+    p->n_images = 0;      // (until the new spectra are queued: a larger batch reallocates the plan's own buffer)
     if (int rc = p->ensure_spectrum(nimg)) return rc;
     c32* sgen = p->spec();
-    if (p->deferred.on && p->deferred.stream != p->stream)
+    if (p->a_holds.pending_off_stream(p->stream))
         if (int rc = flush_pending_prepare(p)) return rc;
     if (int rc = p->prof_begin(PK_IMAGE_COLS, planes)) return rc;
     if (g.fast_fwd) {
         FastColsFwdArgs fa = fast_cols_fwd_args(g, p->d, dimg, (size_t)g.H * g.W, g.H, g.H, g.W, planes, sgen,
                                                 (size_t)g.rows * g.s_pitch, g.s_pitch, false);
-        if (p->deferred.on) {
+        ColumnCache::Request pd;
+        if (p->a_holds.take_pending(pd)) {
             // the deferred kernel-column pass of fftconv_plan_prepare_kernels_packed and the image's column pass: ONE launch
-            const auto pd = p->deferred;
-            p->deferred.on = false;
             FastColsFwdArgs fk = fast_cols_fwd_args(g, p->d, pd.dk, (size_t)pd.kh * pd.kw, pd.kh, pd.kh, pd.kw, pd.na * g.F, p->A.p,
                                                     (size_t)g.rows * a_pitch_for(pd.kw), a_pitch_for(pd.kw), true);
             FC_VERBOSE(p, "image columns (%d tiles) and the columns of %d kernels (%d tiles) in one launch", fa.ntiles, pd.na, fk.ntiles);
             HIP_TRY(launch_fast_cols_fwd_pair(g.M, g.fast_cols.T, fa, fk, fast_cols_fwd_pruned_ok(g.fast_cols, pd.kh), p->num_cus, p->stream));
-            p->prepared = pd;      // (pd.stream is p->stream: a request on another stream was flushed above)
+            p->a_holds.ready(pd);     // (pd.stream is p->stream: a request on another stream was flushed above)
         } else
             HIP_TRY(launch_fast_cols_fwd(g.M, g.fast_cols.T, false, fa, p->num_cus, p->stream));
     } else {
@@ -723,7 +738,6 @@ static int set_images_impl(fftconv_plan* plan, const float* data, int nimg, int 
     }
     if (int rc = p->prof_end()) return rc;
     if (location == FFTCONV_HOST && !image_pinned) HIP_TRY(hipStreamSynchronize(p->stream));
-    p->have_image = true;
     p->n_images = nimg;
     return 0;
 }
@@ -757,10 +771,10 @@ static int spectrum_exchange(fftconv_plan* p, float* spectrum, int location, boo
         return api_fail(FFTCONV_ERR_UNSUPPORTED_SIZE,
                     "this plan transforms %dx%d, not the %dx%d window: create it with fftconv_plan_options.exact_window = 1 to exchange "
                     "spectra in the reference's order", g.Lh, g.Lw, g.fft_h, g.fft_w);
-    if (p->have_image && p->n_images > 1)
+    if (p->n_images > 1)
         return api_fail(FFTCONV_ERR_INVALID_ARG, "the plan holds %d images (fftconv_plan_set_images): the spectrum in the reference's order is "
                         "exchanged for one image -- call fftconv_plan_set_image first", p->n_images);
-    if (to_natural && !p->have_image) return api_fail(FFTCONV_ERR_NO_IMAGE, "no image spectrum: call fftconv_plan_set_image first");
+    if (to_natural && !p->have_image()) return api_fail(FFTCONV_ERR_NO_IMAGE, "no image spectrum: call fftconv_plan_set_image first");
     if (int rc = use_device(p)) return rc;
     if (int rc = p->ensure_spectrum()) return rc;
     if (!p->nat_col_of.p) {     // (the second of the two: both are there, or both are uploaded again)
@@ -782,7 +796,7 @@ static int spectrum_exchange(fftconv_plan* p, float* spectrum, int location, boo
         if (to_natural) HIP_TRY(hipMemcpyAsync(spectrum, nat, n * sizeof(c32), hipMemcpyDeviceToHost, p->stream));
         HIP_TRY(hipStreamSynchronize(p->stream));
     }
-    if (!to_natural) { p->have_image = true; p->n_images = 1; }
+    if (!to_natural) p->n_images = 1;
     return 0;
 }
 
@@ -806,7 +820,6 @@ int fftconv_plan_use_spectrum_buffer(fftconv_plan* plan, void* device_ptr, size_
     // (need: one image; fftconv_plan_set_images checks the size again for its batch)
     plan->Sx = reinterpret_cast<c32*>(device_ptr);
     plan->Sx_bytes = device_ptr ? bytes : 0;
-    plan->have_image = false;
     plan->n_images = 0;
     return 0;
 }
@@ -819,7 +832,6 @@ int fftconv_plan_mark_spectrum_valid(fftconv_plan* plan) {
         return 0;
     }
     if (!plan->spec()) return api_fail(FFTCONV_ERR_NO_IMAGE, "the plan has no spectrum buffer yet (fftconv_plan_spectrum / fftconv_plan_use_spectrum_buffer)");
-    plan->have_image = true;
     if (plan->n_images < 1) plan->n_images = 1;
     return 0;
 }
@@ -850,25 +862,8 @@ int fftconv_plan_prepare_kernels_packed(fftconv_plan* plan, int n_kernel, const 
     if (!plan || n_kernel < 0) return api_fail(FFTCONV_ERR_INVALID_ARG, "Wrong number of inputs");
     if (n_kernel == 0) return 0;
     if (!kernels_device) return api_fail(FFTCONV_ERR_INVALID_ARG, "NULL kernel pointer");
-    fftconv_plan* p = plan;
-    if (p->tiled) return 0;        // block-wise: the kernels are transformed per block inside convolve
-    if (int rc = use_device(p)) return rc;
-    if (int rc = check_kernel_size(p, kernel_h, kernel_w)) return rc;
-    const BatchSizes bs = batch_sizes(p, n_kernel, kernel_w);
-    if (int rc = flush_pending_prepare(p)) return rc;      // an earlier request nobody consumed
-    if (int rc = p->A.ensure(bs.per_a * bs.nbA)) return rc;
-    p->prepared.dk = nullptr;
-    const KernelSet ks{kernels_device, n_kernel, kernel_h, kernel_w, p->stream};
-    const bool timed_apart = p->profile && (p->profile_mask & ((1u << PK_KERNEL_COLS) | (1u << PK_IMAGE_COLS)));   // per-kind figures wanted
-    if (p->opt_defer_prepare && p->g.fast_fwd && !p->opt_flip_kernels && !timed_apart) {   // deferred: rides in the launch of the next image's column pass
-        static_cast<KernelSet&>(p->deferred) = ks;
-        p->deferred.on = true;
-        p->deferred.na = std::min(bs.nbA, n_kernel);
-        return 0;
-    }
-    if (int rc = launch_kernel_cols(p, kernels_device, 0, std::min(bs.nbA, n_kernel), kernel_h, kernel_w)) return rc;
-    p->prepared = ks;
-    return 0;
+    if (plan->tiled) return 0;     // block-wise: the kernels are transformed per block inside convolve
+    return prepare_kernels(plan, n_kernel, kernels_device, kernel_h, kernel_w, false);
 }
 
 int fftconv_plan_convolve(fftconv_plan* plan, int n_kernel, const float* const* kernels, const int* kernel_h,
@@ -884,7 +879,7 @@ int fftconv_plan_convolve(fftconv_plan* plan, int n_kernel, const float* const* 
         if (rc) (void)keep_error([&] { return hipStreamSynchronize(p->tiled->sub->stream); });   // nothing may still be writing into the caller's buffers
         return rc;
     }
-    if (!p->have_image) return api_fail(FFTCONV_ERR_NO_IMAGE, "no image spectrum: call fftconv_plan_set_image first");
+    if (!p->have_image()) return api_fail(FFTCONV_ERR_NO_IMAGE, "no image spectrum: call fftconv_plan_set_image first");
     // validate everything up front so nothing is launched on a bad cell (the reference fails
     // mid-loop and leaks: SURVEY D3)
     for (int k = 0; k < n_kernel; k++) {
@@ -908,8 +903,7 @@ int fftconv_plan_convolve(fftconv_plan* plan, int n_kernel, const float* const* 
             if (int rc = p->pin_k.wait()) return rc;
             for (int j = 0; j < n; j++) memcpy(p->pin_k.p + per * j * sizeof(float), kernels[k0 + j], per * sizeof(float));
             dk = reinterpret_cast<const float*>(p->pin_k.p);
-            if (p->prepared.dk == dk) p->prepared.dk = nullptr;      // column spectra of the buffer's previous contents
-            if (p->deferred.on && p->deferred.dk == dk) p->deferred.on = false;
+            p->a_holds.source_overwritten(dk);      // column spectra, or a request, of the buffer's previous contents
         } else {
             if (int rc = p->K.ensure(per * n)) return rc;
             for (int j = 0; j < n; j++)
@@ -938,7 +932,7 @@ int fftconv_plan_set_stream(fftconv_plan* plan, void* hip_stream) {
     // (prepared column spectra stay: they count again once the plan is back on the stream they were produced on --
     //  the image transform of the multi-GPU step borrows the plan for a side stream and hands it back; a DEFERRED
     //  preparation is launched now, on the stream it was asked for)
-    if (!plan->tiled && plan->deferred.on) {
+    if (!plan->tiled && plan->a_holds.pending()) {
         if (int rc = use_device(plan)) return rc;
         if (int rc = flush_pending_prepare(plan)) return rc;
     }
@@ -973,11 +967,11 @@ int fftconv_plan_set_option(fftconv_plan* plan, const char* name, long value) {
             if (o->member == &fftconv_plan::opt_host_stream && value > 2) return api_fail(FFTCONV_ERR_INVALID_ARG, "host_stream is 0, 1 or 2");
         }
         plan->*(o->member) = (o->flags & OPT_BOOL) ? (value != 0) : std::min(std::max(value, o->lo), o->hi);
-        if (o->flags & OPT_FORGETS) plan->forget_prepared();
+        if (o->flags & OPT_FORGETS) plan->a_holds.forget();
         return 0;
     }
     if (!strcmp(name, "profile")) {
-        if (value != 0 && plan->deferred.on && (plan->profile_mask & ((1u << PK_KERNEL_COLS) | (1u << PK_IMAGE_COLS)))) {   // per-kind figures: the kernels' column pass is timed as a launch of its own
+        if (value != 0 && plan->a_holds.pending() && (plan->profile_mask & ((1u << PK_KERNEL_COLS) | (1u << PK_IMAGE_COLS)))) {   // per-kind figures: the kernels' column pass is timed as a launch of its own
             if (int rc = use_device(plan)) return rc;
             if (int rc = flush_pending_prepare(plan)) return rc;
         }
@@ -1002,7 +996,7 @@ int fftconv_plan_set_option(fftconv_plan* plan, const char* name, long value) {
         return 0;
     }
     if (!strcmp(name, "defer_prepare")) {
-        if (!value && plan->deferred.on) {
+        if (!value && plan->a_holds.pending()) {
             if (int rc = use_device(plan)) return rc;
             if (int rc = flush_pending_prepare(plan)) return rc;
         }
@@ -1060,7 +1054,7 @@ int fftconv_plan_get_option(fftconv_plan* plan, const char* name, long* value) {
     if (!strcmp(name, "blockwise")) { *value = plan->tiled ? plan->tiled->nblk : 0; return 0; }   // read-only: number of blocks (0 = one pass)
     if (!strcmp(name, "overlap_save")) { *value = plan->tiled && plan->tiled->save ? 1 : 0; return 0; }   // read-only: blocks stored by the output kernel (1) or summed (0)
     // read-only: the images the plan holds -- fftconv_plan_set_images' count, 1 after fftconv_plan_set_image, 0 before any image
-    if (!strcmp(name, "images")) { *value = plan->tiled ? (plan->tiled->have_image ? 1 : 0) : (plan->have_image ? plan->images_held() : 0); return 0; }
+    if (!strcmp(name, "images")) { *value = plan->tiled ? (plan->tiled->have_image ? 1 : 0) : plan->n_images; return 0; }
     if (plan->tiled && strcmp(name, "output_region")) return fftconv_plan_get_option(plan->tiled->sub, name, value);
     if (const LongOption* o = find_option(name, OPT_SET_ONLY)) { *value = plan->*(o->member); return 0; }
     if (!strcmp(name, "rows_group")) { *value = plan->g.rows_group; return 0; }
@@ -1069,7 +1063,7 @@ int fftconv_plan_get_option(fftconv_plan* plan, const char* name, long* value) {
     if (!strcmp(name, "specialised_kernels")) { *value = (plan->g.fast_rows.ok ? 1 : 0) | (plan->g.fast_cols.ok ? 2 : 0); return 0; }
     if (!strcmp(name, "rows_slots_per_cu")) { *value = plan->g.rows_slots_per_cu; return 0; }   // read-only: resident row workgroups per CU
     if (!strcmp(name, "profile")) { *value = plan->profile ? 1 : 0; return 0; }
-    if (!strcmp(name, "prepare_pending")) { *value = plan->deferred.on ? 1 : 0; return 0; }   // read-only: a recorded, not yet launched preparation
+    if (!strcmp(name, "prepare_pending")) { *value = plan->a_holds.pending() ? 1 : 0; return 0; }   // read-only: a recorded, not yet launched preparation
     return api_fail(FFTCONV_ERR_INVALID_ARG, "unknown option '%s'", name);
 }
 

@@ -252,12 +252,9 @@ int fftconv_convolution_fft_ex(const float* data, int data_h, int data_w, int fe
         if (same && per > 0 && per * n_kernel * sizeof(float) <= FC_PIN_INPLACE_BYTES && kernel_h[0] <= p->g.max_kh && kernel_w[0] <= p->g.max_kw &&
             use_device(p) == 0 && p->pin_k.ensure(per * n_kernel * sizeof(float)) == 0 && p->pin_k.wait() == 0) {
             for (int j = 0; j < n_kernel; j++) memcpy(p->pin_k.p + per * j * sizeof(float), kernels[j], per * sizeof(float));
-            const long keep_defer = p->opt_defer_prepare;
-            p->opt_defer_prepare = 1;
-            const int rcp = fftconv_plan_prepare_kernels_packed(p, n_kernel, reinterpret_cast<const float*>(p->pin_k.p), kernel_h[0], kernel_w[0]);
-            p->opt_defer_prepare = keep_defer;
-            if (rcp == 0 && p->deferred.on) staged_dk = reinterpret_cast<const float*>(p->pin_k.p);
-            else p->deferred.on = false;
+            const int rcp = prepare_kernels(p, n_kernel, reinterpret_cast<const float*>(p->pin_k.p), kernel_h[0], kernel_w[0], true);
+            if (rcp == 0 && p->a_holds.pending()) staged_dk = reinterpret_cast<const float*>(p->pin_k.p);
+            else p->a_holds.forget();
         }
     }
     int rc = fftconv_plan_set_image(p, data, FFTCONV_HOST);
@@ -277,14 +274,15 @@ int fftconv_convolution_fft_ex(const float* data, int data_h, int data_w, int fe
     } else if (!rc) {
         rc = fftconv_plan_convolve(p, n_kernel, kernels, kernel_h, kernel_w, kernel_location, out, FFTCONV_HOST);
     }
-    if (rc) p->deferred.on = false;       // (a failed image leaves no request behind in a plan that goes back into the cache)
     tm.convolve_ms = ms_since(t2);
     const auto t3 = std::chrono::steady_clock::now();
     // argument-class failures were found before anything was queued and leave the plan as it was; after a HIP or
     // allocation failure the plan is not trusted again
     const bool reusable = rc == 0 || rc == FFTCONV_ERR_INVALID_ARG || rc == FFTCONV_ERR_KERNEL_SHAPE || rc == FFTCONV_ERR_KERNEL_EXCEEDS_MAX ||
                           rc == FFTCONV_ERR_THREAD_SIZE;
-    if (!p->tiled) p->forget_prepared();   // (both records may name pin_k, whose contents the next call replaces)
+    // (the record may name pin_k, whose contents the next call replaces; and a failed image leaves no request behind in a plan
+    //  that goes back into the cache)
+    if (!p->tiled) p->a_holds.forget();
     auto release = [&] { if (reusable) cache_put(key, p); else (void)fftconv_plan_destroy(p); return 0; };
     (void)(rc ? keep_error(release) : release());
     tm.release_ms = ms_since(t3);

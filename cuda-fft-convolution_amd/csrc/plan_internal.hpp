@@ -1,7 +1,9 @@
 // plan_internal.hpp -- what the host translation units of libfftconv.so share (not installed): the plan object behind
 // include/fftconv.h, its device / pinned buffers, and the internal entry points each unit offers the others.
+//   column_cache.hpp   what the column-spectrum buffer A holds between calls (KernelSet, ColumnCache): the one owner of that record
 //   fftconv_api.cpp    plan core: creation (plan_device_setup), image transform, the per-kernel loop (run_group: plan_delivery,
-//                      launch_spectral_rows_batch, launch_output_cols, deliver_batch), options (kLongOptions), two-step pair
+//                      launch_spectral_rows_batch, launch_output_cols, deliver_batch), kernel preparation (prepare_kernels),
+//                      options (kLongOptions), two-step pair
 //   plan_cache.cpp     plan cache of the one-shot entries + fftconv_convolution_fft[_ex] (the MEX body)
 //   host_ring.cpp      host-output streaming (copy threads, pinned ring, the two staging buffers of a streamed group)
 //   blockwise.cpp      block-wise plans (overlap-save / overlap-add) and their planner
@@ -20,6 +22,7 @@
 
 #include "../../include/fftconv.h"
 #include "api_internal.hpp"
+#include "column_cache.hpp"
 #include "kernels.hpp"
 #include "pipeline.hpp"
 
@@ -203,14 +206,6 @@ struct OutWindow {
     int pitch, h_lo, h_hi, w_first, ncols;
 };
 
-// n packed kernels of one size at dk whose column spectra are (or are to be) in A, and the stream that orders A's contents
-struct KernelSet {
-    const float* dk = nullptr;
-    int n = 0, kh = 0, kw = 0;
-    hipStream_t stream = nullptr;
-    bool operator==(const KernelSet& o) const { return dk == o.dk && n == o.n && kh == o.kh && kw == o.kw && stream == o.stream; }
-};
-
 using namespace fc;   // (host units only: this header is not installed)
 
 struct fftconv_plan {
@@ -220,7 +215,6 @@ struct fftconv_plan {
     DeviceTables d;
     int gpu_id = 0;
     hipStream_t stream = nullptr;
-    bool have_image = false;
     // device copies of the Tables (fftconv_api.cpp: plan_device_setup; the natural-order pair: on first use)
     DevBuf<c32> tw_m, tw_w, fr_tw1, fr_tw2, fc_tw1, fc_tw2;
     DevBuf<PairEntry> pairs, fc_pairs;
@@ -231,6 +225,7 @@ struct fftconv_plan {
     // Images the plan holds (fftconv_plan_set_images; set_image: 1; 0 before any image and after the spectrum was invalidated):
     // their spectra lie [b][f][row][s_pitch] in the spectrum buffer, g.spectrum_elems() apart
     int n_images = 0;
+    bool have_image() const { return n_images >= 1; }
     int images_held() const { return n_images > 1 ? n_images : 1; }   // what the spectrum buffer is sized and reported for
     c32* spec() const { return Sx ? Sx : S.p; }   // S is allocated by the first use that needs it (ensure_spectrum)
     // (the own buffer grows on demand: a larger batch reallocates it, and its contents are then gone -- the callers write all of it)
@@ -275,19 +270,13 @@ struct fftconv_plan {
     long opt_host_threads = 0;     // host copy threads of the output ring (0 = auto)
     long opt_host_chunk_kb = 0;    // ring chunk size (0 = auto)
     long opt_host_slots = 0;       // ring chunks (0 = auto)
-    long opt_defer_prepare = 0;    // 1: fftconv_plan_prepare_kernels_packed only records its request (see `deferred`)
+    long opt_defer_prepare = 0;    // 1: fftconv_plan_prepare_kernels_packed only records its request (column_cache.hpp: Pending)
     long opt_verbose = 0;          // 1: per-stage sizes and launch shapes to stderr (the reference's `debug`, src/cudaConvolutionFFT.cu:9)
     HostRing* ring = nullptr;      // created on the first host-output convolve
     bool profile = false;
     unsigned profile_mask = ~0u;   // which kinds (bit = PK_* index) are timed while `profile` is on
     bool prof_open = false;        // the last prof_begin recorded a start event
-    // kernel column spectra of the first chunk already in A (fftconv_plan_prepare_kernels_packed); dk == nullptr: none
-    KernelSet prepared;
-    // fftconv_plan_prepare_kernels_packed DEFERRED: the kernels' column pass is launched by whichever comes first, the
-    // next set_image on the same stream (then in ONE launch with the image's column pass: launch_fast_cols_fwd_pair) or
-    // the next convolve / any call that must see it done (flush_pending_prepare)
-    struct Deferred : KernelSet { bool on = false; int na = 0; } deferred;   // (na: kernels of the first chunk)
-    void forget_prepared() { prepared.dk = nullptr; deferred.on = false; }    // A's contents, or what they depend on, are about to change
+    ColumnCache a_holds;           // what A holds: nothing known, a recorded preparation, or the first chunk's column spectra
     std::vector<EventPair> pending;
     std::vector<EventPair> pool;
     double prof_ms[PK_COUNT] = {0, 0, 0, 0, 0};
@@ -397,6 +386,9 @@ int launch_region(const fftconv_plan* p, const float* src, float* dst, int nmaps
 // Core of the per-kernel loop for n kernels of one size, packed on the device at dk ([n][F][kw][kh]); on failure nothing of the
 // host-output ring is still writing into the caller's buffers when the error is returned
 int run_group(fftconv_plan* p, int n, const float* dk, int kh, int kw, const Sink& sink);
+// fftconv_plan_prepare_kernels_packed behind its argument checks (one-pass plans).  force_defer: as if option "defer_prepare" were
+// set -- the one-shot entry stages its kernels ahead of the image; whether the request was in fact recorded: p->a_holds.pending()
+int prepare_kernels(fftconv_plan* p, int n, const float* dk, int kh, int kw, bool force_defer);
 // cyclic: the block plan of an overlap-save block-wise plan (PlanTuning::cyclic) -- never block-wise itself
 int plan_create_internal(fftconv_plan** plan, int data_h, int data_w, int feature_dim, int max_kernel_h, int max_kernel_w, int gpu_id,
                          void* hip_stream, const fftconv_plan_options* options, bool cyclic);

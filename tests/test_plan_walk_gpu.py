@@ -12,32 +12,41 @@ ends it and nothing more starts.  A failing walk prints its ops as a literal; to
 Proof that the walk has teeth (the convention of test_stream_order_host.py): one-line mutations of the library, each built in a
 scratch copy, never committed, whose only effect is wrong values; this file run once against each on an MI355X.
 
-  1. "flip_kernels" loses OPT_FORGETS in kLongOptions (prepared column spectra survive a change of the flip):
-     test_plan_walk[specialised-4], [exact-3] and [bluestein-3] fail, each at a convolve_packed of a prepared set, maps off by 1.3 - 1.5
-     of the window's maximum.
-  2. `p->prepared.dk = nullptr;` dropped at the top of the chunk loop of run_group_impl (consumed column spectra count again):
-     test_plan_walk[generic-4], [save_blocks-1] and [save_blocks-4] fail (a packed set convolved again after other kernels went
-     through A; on the overlap-save plan two host sets of one size and count, told apart by nothing but their contents).
+  1. "flip_kernels" loses OPT_FORGETS in kLongOptions (no ColumnCache::forget: prepared column spectra survive a change of the
+     flip): test_plan_walk[specialised-4], [exact-3], [bluestein-3] and [exact-sentinel0] fail, each at a convolve_packed of a
+     prepared set, maps off by 1.3 - 1.5 of the window's maximum.
+  2. ColumnCache::consume (csrc/column_cache.hpp) no longer clears the record it found -- `state_ = Empty;` dropped (consumed
+     column spectra count again): test_plan_walk[generic-4], [save_blocks-1], [save_blocks-4] and [save_blocks-sentinel1] fail
+     (a packed set convolved again after other kernels went through A; on the overlap-save plan two host sets of one size and
+     count, told apart by nothing but their contents).
   3. evict_lru in plan_cache.cpp picks the MOST recently used plan (`<` turned into `>`): test_cache_walk[1], [2] and [3] fail, at
      calls 14, 5 and 11: last_call_timing's cache_hit disagrees with the model's view of which keys are resident.
   4. `c.hits++;` dropped in cache_take: test_cache_walk[1], [2] and [3] fail at the first call served from the cache (calls 1, 1
      and 5): hits + misses grew by 0 over a call with one look-up.
   5. "kernel_chunk_mb" loses OPT_FORGETS: the 32 random walks and the cache walks PASS -- the wrong map needs four calls in a row
      (a small "batch_maps", a prepare, a chunk budget that then holds more kernels, a packed convolve of the prepared set), which the
-     generator did not deal.  sentinel2 below was written by hand for it and fails under this mutation; the generator itself still
-     lacks the transition.
+     generator did not deal.  sentinel2 below was written by hand for it and test_plan_walk[generic-sentinel2] alone fails under
+     this mutation; the generator itself still lacks the transition.
 
-Four more lines were tried or read and CANNOT change what a caller sees; none of them counts above.  The
-`if (p->prepared.dk == dk) ...` / `deferred` pair behind the pin_k gather of fftconv_plan_convolve and `forget_prepared()` in
-plan_cache.cpp (35 passed under each): both guard a record that names the plan's own pinned kernel buffer pin_k, and only the
-one-shot entry ever prepares from that buffer.  Inside that entry the deferred request is consumed by the set_image that follows
-and the prepared record by run_group_impl's chunk loop (line 2 above) before the call returns; a call that fails in between is an
-allocation or HIP failure whose plan is destroyed, not cached.  `p->prepared.dk = nullptr;` in
-fftconv_plan_prepare_kernels_packed (37 passed): on the direct path the record is overwritten three lines on; on the deferred
-path A still holds the spectra the old record names until the request is launched, and every launch of it (flush_pending_prepare,
-the pair launch of set_image) overwrites the record as well.  The flush in fftconv_plan_set_stream (37 passed): without it the
-request is launched later, still on the stream it was asked for, and the header has the caller order the two streams around the
-switch, so the values cannot differ.  All four are second guards, dead while the lines behind them stand.
+(1, 2 and 5 were run again, with the failures named above, when the record of what A holds became one object, ColumnCache:
+fftconv_plan::a_holds.  tests/test_column_cache_host.py holds that object alone to a model of A over every short call sequence.)
+
+Four more invalidations were tried or read and CANNOT change what a caller sees; none of them counts above (the counts of passes
+are those of the lines the calls below replaced; these four runs were not repeated).  All four are still
+there, each as ONE call on the cache; what the cache has made impossible to write is half of one -- clearing the ready record
+and leaving the request, or the reverse -- because the two are states of one record.
+`a_holds.source_overwritten(dk)` behind the pin_k gather of fftconv_plan_convolve and `a_holds.forget()` before the one-shot
+entry in plan_cache.cpp hands its plan back (35 passed under each): both guard a record that names the plan's own pinned
+kernel buffer pin_k, and only the one-shot entry ever prepares from that buffer.  Inside that entry the request is taken by the
+set_image that follows and the ready record by run_group_impl's consume (mutation 2 above) before the call returns; a call that
+fails in between is an allocation or HIP failure whose plan is destroyed, not cached.  (The first was two lines, one per record,
+the second a call beside two direct writes of the request's flag: that a line of either is missing can no longer be written.)
+`a_holds.forget()` in prepare_kernels (37 passed): on the direct path ready() replaces the record three lines on, and
+only a launch that fails in between sees the difference; on the deferred path request() replaces it -- a stale ready record beside
+the new request, which the old pair of records could spell, is not a state of the cache.  The flush in fftconv_plan_set_stream,
+`if (a_holds.pending()) flush_pending_prepare()` (37 passed): without it the request is launched later, still on the
+stream it was asked for, and the header has the caller order the two streams around the switch, so the values cannot differ.
+All four are second guards, dead while the calls behind them stand.
 """
 import pytest
 
