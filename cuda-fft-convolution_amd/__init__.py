@@ -509,6 +509,9 @@ class Plan:
         _check(self._lib.fftconv_plan_set_stream(self._h, ctypes.c_void_p(int(stream) or None)))
 
     def set_option(self, name, value):
+        """plan options by name (include/fftconv.h: fftconv_plan_set_option), e.g. "batch_maps", "map_format", "rows_group", and for
+        image batches "image_walk" (1: spectral-row launches of several images walk over images; read-only "image_walk_active"
+        tells whether this plan has the kernel for it)"""
         _check(self._lib.fftconv_plan_set_option(self._h, name.encode(), int(value)))
         _check(self._lib.fftconv_plan_get_info(self._h, ctypes.byref(self.info)))
 

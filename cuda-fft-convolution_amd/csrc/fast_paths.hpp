@@ -12,6 +12,7 @@
 #include "fast_cols_fwd.hpp"
 #include "fast_rows.hpp"
 #include "fast_rows_fwd.hpp"
+#include "fast_rows_images.hpp"
 #include "fast_rows_multi.hpp"
 #include "planner.hpp"
 
@@ -215,6 +216,23 @@ template <int G, class Runner>
 inline bool fast_rows_fwd_dispatch_group(int L, Runner&& run) {
     return fast_rows_dispatch_group<G>(L, 0, DropNZ2<std::remove_reference_t<Runner>>{run});
 }
+
+// Image-walk spectral-row kernel (fast_rows_images.hpp; plan option "image_walk"): one instantiation per length -- its forward
+// part runs once per walk and reads every stage-2 input, so the NZ2 of the list does not enter (fast_rows_fwd_dispatch_group
+// finds the length's configuration).  A length whose kernel would spill registers, use scratch or hold fewer than the 3 waves
+// per SIMD of its launch bounds in the build's reports (csrc/*.rpt) is NOT built and listed here: a plan of that length keeps the
+// kernel walk (read-only option "image_walk_active" 0).  The built ones and the ones listed here add up to the 32 lengths.
+// At the 168 registers of three waves per SIMD, kf + the product + the butterfly's temporaries leave no room at these six:
+// 4160 = 8.20.26 spills 72 registers (radix 26), 7040 = 10.32.22 x2 20 (a 32-point stage 2 beside two rows' constants), and
+// 6144, 5120, 4608 and 1920 (stage 3 of 24 / 20 points) each park one stage-1 base twiddle in scratch and fetch it back in
+// every map's P5 -- little, but a scratch access shares the in-order memory counter with the stores and the row in flight.
+constexpr int FC_ROWS_IMAGES_NOT_BUILT[] = {7040, 6144, 5120, 4608, 4160, 1920};
+constexpr bool fast_rows_images_built(int L) {
+    for (int x : FC_ROWS_IMAGES_NOT_BUILT)
+        if (x == L) return false;
+    return true;
+}
+inline bool fast_rows_images_available(int L, int max_kw) { return fast_rows_lookup(L, max_kw < 1 ? 1 : max_kw).ok && fast_rows_images_built(L); }
 
 // Host tables of a fast row configuration.
 struct FastRowsTables {
@@ -464,6 +482,24 @@ FC_HD RowsWalk rows_walk_flat(int b, int groups, int walks, int images, int kern
     const int kernel0 = walk * per_wg;
     return {image, gl * 8 + xcd, kernel0, kernels_per_image - kernel0 < per_wg ? kernels_per_image - kernel0 : per_wg};
 }
+// Image walk (fast_rows_images.hpp): a workgroup of (row group, kernel) walks the images [image0, image0 + ni) of the launch,
+// iwalks walks of per_wg images each (the last one shorter: a walk never runs past the images of the launch).  Flat XCD-aware
+// 1-D grid of 8 * ceil(groups / 8) * iwalks * kernels_per_image blocks as rows_walk_flat: blocks b and b + 8 share an XCD, XCD x
+// takes the row groups x, x + 8, ...; within a row group the KERNEL is the fastest coordinate and the image walk the next, so
+// the kernels_per_image workgroups that read the same image-spectrum rows sit side by side on one L2 (a speed assumption
+// only).  group >= groups: the padding of the last round of XCDs, no work.
+struct RowsImageWalk { int group, kernel, image0, ni; };
+FC_HD int rows_image_walks(int images, int per_wg) { return (rows_images(images) + per_wg - 1) / per_wg; }
+FC_HD RowsImageWalk rows_walk_images(int b, int groups, int kernels_per_image, int iwalks, int images, int per_wg) {
+    const int xcd = b & 7, sq = b >> 3;
+    const int per_group = iwalks * kernels_per_image;
+    const int gl = sq / per_group;
+    const int r = sq - gl * per_group;
+    const int iw = r / kernels_per_image;
+    const int image0 = iw * per_wg, left = rows_images(images) - image0;
+    return {gl * 8 + xcd, r - iw * kernels_per_image, image0, left < per_wg ? left : per_wg};
+}
+inline int rows_images_grid(int groups, int kernels_per_image, int iwalks) { return 8 * ((groups + 7) / 8) * iwalks * kernels_per_image; }
 // generic kernel (kernels_body.hpp: spectral_rows_body), grid (row, kernel of the image, image): the map's slot in Y, which the
 // body splits again with SpectralRowsArgs::kernels_per_image
 FC_HD int rows_generic_slot(int by, int bz, int kernels_per_image) { return bz * kernels_per_image + by; }

@@ -196,14 +196,31 @@ int plan_delivery(fftconv_plan* p, const Sink& sink, int nbY, Delivery& d) {
 // spectral rows of nb x nk maps: the nk column spectra at `a` times the spectra of the images [b0, b0 + nb), transformed along w into
 // the slots (b - b0) * nk + k of Y -- one launch, the image is a grid coordinate of the kernels (pipeline.hpp: rows_args_set_images;
 // fast_paths.hpp: rows_walk_3d, rows_walk_flat, rows_shift_to_image, rows_generic_slot)
-int launch_spectral_rows_batch(fftconv_plan* p, const c32* a, int kw, int b0, int nb, int nk) {
+// Which walk a spectral-row launch of nb images x nk kernels runs and how long it is: decided ONCE per launch -- the launch and the
+// verbose line that names it both read this.  image_walk: the kernel row stays in registers and the workgroup walks over images
+// (fast_rows_images.hpp: "image_walk" on a plan that has the kernel, more than one image); else the walk over kernels.
+struct RowsRoute {
+    bool image_walk;
+    int per_wg;        // images (image walk) or maps (kernel walk) per workgroup
+};
+RowsRoute rows_route(const fftconv_plan* p, int nb, int nk) {
+    const Geometry& g = p->g;
+    if (nb > 1 && p->image_walk_active()) return {true, g.images_group_for(nb, nk, p->num_cus)};
+    return {false, g.rows_group_for(nk, p->num_cus)};      // (one map per workgroup where the multi-map walk is off; a walk never crosses an image)
+}
+
+int launch_spectral_rows_batch(fftconv_plan* p, const c32* a, int kw, int b0, int nb, int nk, const RowsRoute& route) {
     const Geometry& g = p->g;
     const c32* s = p->spec() + (size_t)b0 * g.spectrum_elems();
     if (int rc = p->prof_begin(PK_SPECTRAL, (long)nb * nk)) return rc;
-    if (g.fast_rows.ok) {   // (a walk of one map per workgroup where the multi-map walk is off: rows_group_for; a walk never crosses an image)
+    if (route.image_walk) {
         FastRowsArgs fa = fast_rows_args(g, p->d, a, kw, s, p->Y.p);
         rows_args_set_images(fa, g, nb, nk);
-        HIP_TRY(launch_fast_rows_multi(g.Lw, fast_rows_nz2(g, kw), fa, g.rows, nk, g.rows_group_for(nk, p->num_cus), p->stream));
+        HIP_TRY(launch_fast_rows_images(g.Lw, fa, g.rows, route.per_wg, p->stream));
+    } else if (g.fast_rows.ok) {
+        FastRowsArgs fa = fast_rows_args(g, p->d, a, kw, s, p->Y.p);
+        rows_args_set_images(fa, g, nb, nk);
+        HIP_TRY(launch_fast_rows_multi(g.Lw, fast_rows_nz2(g, kw), fa, g.rows, nk, route.per_wg, p->stream));
     } else {
         SpectralRowsArgs sa = spectral_rows_args(g, p->t, p->d, a, kw, s, p->Y.p);
         rows_args_set_images(sa, g, nb, nk);
@@ -334,10 +351,11 @@ int run_group_impl(fftconv_plan* p, int n, const float* dk, int kh, int kw, cons
         {
             const int ny = l.ny(), first = l.first(image_stride);
             if (B > 1) FC_VERBOSE(p, "images %d..%d x kernels %d..%d", l.b0, l.b0 + l.nb - 1, l.k0, l.k0 + l.nk - 1);
-            FC_VERBOSE(p, "maps %d..%d: spectral rows (%s, %d rows x %d points, %d maps per workgroup), output columns (%s, %d-point, %d columns per tile)",
-                       first, first + ny - 1, g.fast_rows.ok ? "specialised" : "generic", g.rows, g.Lw, g.rows_group_for(l.nk, p->num_cus),
-                       g.fast_cols.ok ? "specialised" : "generic", g.M, g.fast_cols.ok ? g.fast_cols.T : g.T_cols);
-            if (int rc = launch_spectral_rows_batch(p, p->A.p + (size_t)(l.k0 - l.a0) * bs.per_a, kw, l.b0, l.nb, l.nk)) return rc;
+            const RowsRoute route = rows_route(p, l.nb, l.nk);
+            FC_VERBOSE(p, "maps %d..%d: spectral rows (%s, %d rows x %d points, %s%d %s per workgroup), output columns (%s, %d-point, %d columns per tile)",
+                       first, first + ny - 1, g.fast_rows.ok ? "specialised" : "generic", g.rows, g.Lw, route.image_walk ? "image walk: " : "", route.per_wg,
+                       route.image_walk ? "images" : "maps", g.fast_cols.ok ? "specialised" : "generic", g.M, g.fast_cols.ok ? g.fast_cols.T : g.T_cols);
+            if (int rc = launch_spectral_rows_batch(p, p->A.p + (size_t)(l.k0 - l.a0) * bs.per_a, kw, l.b0, l.nb, l.nk, route)) return rc;
             int buf = 0;
             if (d.route == Route::Ring)
                 if (int rc = ring_claim_staging(p, &buf)) return rc;
@@ -390,6 +408,7 @@ const LongOption kLongOptions[] = {
     {"rect_store", &fftconv_plan::opt_rect_store, 0, 1, OPT_BOOL},
     {"dynamic_tiles", &fftconv_plan::opt_dynamic_tiles, 0, 0, OPT_GET_ONLY},
     {"defer_prepare", &fftconv_plan::opt_defer_prepare, 0, 0, OPT_GET_ONLY},
+    {"image_walk", &fftconv_plan::opt_image_walk, 0, 1, OPT_BOOL},      // (nothing cached depends on it: no OPT_FORGETS)
 };
 const LongOption* find_option(const char* name, unsigned not_flag) {
     for (const LongOption& o : kLongOptions)
@@ -1051,6 +1070,8 @@ int fftconv_plan_get_option(fftconv_plan* plan, const char* name, long* value) {
     if (!strcmp(name, "rect_off_w")) { *value = plan->opt_region == 5 ? plan->off_w : 0; return 0; }
     if (!strcmp(name, "rect_direct")) { *value = plan->rect_direct() ? 1 : 0; return 0; }
     if (!strcmp(name, "rect_store")) { *value = plan->opt_rect_store; return 0; }
+    // read-only: 1 if, with the plan's current settings, a spectral-row launch of more than one image walks over images
+    if (!strcmp(name, "image_walk_active")) { *value = plan->image_walk_active() ? 1 : 0; return 0; }
     if (!strcmp(name, "blockwise")) { *value = plan->tiled ? plan->tiled->nblk : 0; return 0; }   // read-only: number of blocks (0 = one pass)
     if (!strcmp(name, "overlap_save")) { *value = plan->tiled && plan->tiled->save ? 1 : 0; return 0; }   // read-only: blocks stored by the output kernel (1) or summed (0)
     // read-only: the images the plan holds -- fftconv_plan_set_images' count, 1 after fftconv_plan_set_image, 0 before any image

@@ -201,6 +201,12 @@ hipError_t launch_fast_rows_multi(int L, int nz2, const FastRowsArgs& a, int row
     return in_first_group<FC_ROW_GROUPS>([&](auto g) { return launch_fast_rows_multi_group<g.value>(L, nz2, a, rows, kernels, kernels_per_wg, s); });
 }
 
+hipError_t launch_fast_rows_images(int L, const FastRowsArgs& a, int rows, int images_per_wg, hipStream_t s) {
+    if (rows <= 0) return hipSuccess;
+    if (a.F != 1 || images_per_wg < 1 || a.images < 1 || a.kernels_per_image < 1) return hipErrorInvalidValue;
+    return in_first_group<FC_ROW_GROUPS>([&](auto g) { return launch_fast_rows_images_group<g.value>(L, a, rows, images_per_wg, s); });
+}
+
 hipError_t fast_rows_multi_wgs_per_cu(int L, int nz2, const FastRowsArgs& a, int* wgs_per_cu) {
     return in_first_group<FC_ROW_GROUPS>([&](auto g) { return fast_rows_multi_wgs_per_cu_group<g.value>(L, nz2, a, wgs_per_cu); });
 }

@@ -37,6 +37,10 @@ hipError_t launch_spectral_rows(const SpectralRowsArgs& a, int rows, int kernels
 hipError_t launch_fast_rows_multi(int L, int nz2, const FastRowsArgs& a, int rows, int kernels, int kernels_per_wg, hipStream_t s);
 // how many workgroups of that kernel a CU holds at once (hipOccupancyMaxActiveBlocksPerMultiprocessor)
 hipError_t fast_rows_multi_wgs_per_cu(int L, int nz2, const FastRowsArgs& a, int* wgs_per_cu);
+// image-walk spectral rows (fast_rows_images.hpp; F = 1): the a.images x a.kernels_per_image maps of the launch, a workgroup per
+// (row group, kernel) walking images_per_wg (>= 1) consecutive images; hipErrorInvalidValue if L has no such kernel
+// (fast_paths.hpp: fast_rows_images_built)
+hipError_t launch_fast_rows_images(int L, const FastRowsArgs& a, int rows, int images_per_wg, hipStream_t s);
 hipError_t launch_fast_cols(int M, int T, const FastColsArgs& a, int num_cus, hipStream_t s);
 // the rectangle store of the output kernel (fast_cols.hpp: RECT): `shape` from fast_cols_rect_launch_shape (fast_paths.hpp)
 hipError_t launch_fast_cols_rect(int M, int T, const FastColsShape& shape, hipStream_t s);
@@ -53,6 +57,8 @@ using GroupResult = std::optional<hipError_t>;
 template <int G> GroupResult launch_fast_rows_fwd_group(int L, const FastRowsFwdArgs& a, int rows, hipStream_t s);
 template <int G> GroupResult launch_fast_rows_multi_group(int L, int nz2, const FastRowsArgs& a, int rows, int kernels, int kernels_per_wg, hipStream_t s);
 template <int G> GroupResult fast_rows_multi_wgs_per_cu_group(int L, int nz2, const FastRowsArgs& a, int* wgs_per_cu);
+// (the image walk: kernels_rows_images_g<G>.hip)
+template <int G> GroupResult launch_fast_rows_images_group(int L, const FastRowsArgs& a, int rows, int images_per_wg, hipStream_t s);
 template <int G> GroupResult launch_fast_cols_group(int M, int T, const FastColsArgs& a, int num_cus, hipStream_t s);
 // (the 16-bit-map instantiations of the same configurations: kernels_cols16_g<G>.hip)
 template <int G> GroupResult launch_fast_cols16_group(int M, int T, const FastColsArgs& a, int num_cus, hipStream_t s);

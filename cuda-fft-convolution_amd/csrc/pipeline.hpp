@@ -89,14 +89,27 @@ struct Geometry {
     // shortest walk whose FULL walks are all resident at once (the remainder walk of every row group, launched last,
     // fills the slots they leave and the first ones to free up) -- cfg2, 289 row groups x 16 maps on 1536 slots: walks of
     // 1 / 2 / 3 / 4 / 5 maps take 84.6 / 81.4 / 79.2 / 82.6 / 83.6 us per step; 3 = 1445 full walks + 289 single maps.
-    int rows_group_auto(int nmaps, int num_cus) const {
-        const long groups = (rows + fast_rows.RPW - 1) / fast_rows.RPW;
-        const long slots = (long)num_cus * std::max(1, rows_slots_per_cu), total = groups * nmaps;
-        if (total >= 8 * slots) return (int)std::max<long>(1, std::min<long>(16, std::min<long>(total / (4 * slots), nmaps)));
+    int rows_group_auto(int nmaps, int num_cus) const { return walk_auto((rows + fast_rows.RPW - 1) / fast_rows.RPW, nmaps, num_cus); }
+    // the rule itself: `units` workgroups would run per walked item (row groups; row groups x kernels for the image walk), `count` items
+    // (maps of the launch; images of the launch) are dealt into walks
+    int walk_auto(long units, int count, int num_cus) const {
+        const long slots = (long)num_cus * std::max(1, rows_slots_per_cu), total = units * count;
+        if (total >= 8 * slots) return (int)std::max<long>(1, std::min<long>(16, std::min<long>(total / (4 * slots), count)));
         if (total <= slots) return 1;        // everything resident at once
-        for (int w = 2; w <= std::min(16, nmaps); w++)
-            if (groups * (nmaps / w) <= slots) return w;
-        return std::min(16, nmaps);
+        for (int w = 2; w <= std::min(16, count); w++)
+            if (units * (count / w) <= slots) return w;
+        return std::min(16, count);
+    }
+    // Image walk (fast_rows_images.hpp): images per workgroup for a launch of `images` images x nk kernels -- the same rule over
+    // the same slots with workgroups = groups * nk * walks: fill the chip first, at most 16; a fixed rows_group > 1 is the walk
+    // (capped by the images of the launch), rows_group 0 / 1 walks of one image.
+    int images_group_auto(int images, int nk, int num_cus) const {
+        return walk_auto((long)((rows + fast_rows.RPW - 1) / fast_rows.RPW) * nk, images, num_cus);
+    }
+    int images_group_for(int images, int nk, int num_cus) const {
+        if (!rows_multi_ok()) return 1;
+        if (rows_group > 1) return std::min(rows_group, images);
+        return images_group_auto(images, nk, num_cus);
     }
     size_t spectrum_elems() const { return (size_t)F * rows * s_pitch; }
     size_t y_elems_per_kernel() const {

@@ -244,6 +244,13 @@ struct fftconv_plan {
     // rect_direct(); 0, and every plan it cannot serve: the window goes through the fp32 staging O and is cropped like regions 1-3
     long opt_rect_store = 1;
     bool rect_direct() const { return opt_region == 5 && opt_rect_store && !tiled && fast_cols_rect_available(g.M, g.y_tiled()); }
+    // "image_walk" 1: a spectral-row launch of more than one image runs the kernel that keeps the transformed KERNEL row in
+    // registers and walks over images (fast_rows_images.hpp) where the plan has it -- image_walk_active(); 0 (default), and
+    // every plan it cannot serve: the walk over kernels.  Nothing cached depends on it.
+    long opt_image_walk = 0;
+    bool image_walk_active() const {
+        return opt_image_walk && !tiled && g.F == 1 && g.path_mode != 0 && g.fast_rows.ok && fast_rows_images_available(g.Lw, g.max_kw);
+    }
     DevBuf<float> OC;  // cropped maps staged for the copy-out
     size_t out_elems() const { return opt_region ? (size_t)out_h * out_w : g.map_elems(); }   // (block-wise plans: g holds the whole window)
     // "map_format": element format of every result map (fc_common.hpp: FC_MAP_*; one-pass plans only).  The staging buffers O / OC

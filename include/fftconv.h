@@ -400,6 +400,20 @@ int fftconv_plan_synchronize(fftconv_plan *plan);
  *             plan has the kernel for it; 0: the window goes through the fp32 staging and is cropped like regions 1-3.
  *             Read-only beside it: "rect_direct" (1 if, with the plan's current settings, the output kernel will store the
  *             rectangle itself), "rect_off_h" / "rect_off_w" (the rectangle's offsets; 0 without one)),
+ *          "image_walk" (image batches, fftconv_plan_set_images.  0 (default): a workgroup of the spectral-row kernel keeps an
+ *             image-spectrum row in registers and walks over kernels.  1: where the plan has the kernel for it, a launch of more
+ *             than one image keeps the transformed KERNEL row in registers and walks over the images of the launch ("rows_group"
+ *             then counts images: automatic, or the walk itself when > 1) -- the forward transform of a kernel row is paid once
+ *             per walk instead of once per map, the image-spectrum row is read once per map instead of once per walk: for
+ *             many images against few kernels.  A launch of one image runs the kernel it runs at 0.  A convolve puts several
+ *             images behind one launch only as whole images x all kernels of the call, "batch_maps" / n_kernel images at a time:
+ *             with 64 kernels and the default "batch_maps" (64) every launch holds one image and the option changes nothing -- a
+ *             caller raises "batch_maps".  The maps of an (image, kernel) pair are the same bits whatever the walk length and
+ *             the batch; they differ from the maps at 0 in the last bits (another summation order in the kernel row's
+ *             transform).  Nothing prepared is forgotten.  Read-only beside it: "image_walk_active" (1 if, with the plan's
+ *             current settings, a launch of more than one image will walk over images; 0 with "image_walk" 0, F > 1, the
+ *             generic or Bluestein row kernel (kernel_path 1), a block-wise plan, and the six row lengths whose kernel is not
+ *             built because it would spill registers: 1920, 4160, 4608, 5120, 6144, 7040)),
  *          "defer_prepare" (1: fftconv_plan_prepare_kernels_packed records its request instead of launching it, see
              there; 0 (default): launched at once.  Read-only "prepare_pending": 1 while such a request waits),
           "verbose" (1: the sizes and launch shapes of every stage go to stderr as the work is queued -- the

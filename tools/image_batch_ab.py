@@ -9,7 +9,14 @@ A device-resident step, timed with HIP events on the plan's stream, in fresh pro
     batch  set_images(DEVICE, B) + convolve_packed             -- this tree's library only
 Shapes: BASELINE cfg1 (256^2 (x) 31^2, N = 1) at B = 16 and 64, cfg2 (1024^2 (x) 63^2, N = 16) at B = 8, cfg5 (2048^2 (x) 63^2,
 N = 64) at B = 4.  Per shape and mode: the median over the rounds and the spread (min .. max), microseconds per step; the spread
-of the alternating runs is the yardstick for "no slower".  The B = 1 headline is bench.py's own line on either library."""
+of the alternating runs is the yardstick for "no slower".  The B = 1 headline is bench.py's own line on either library.
+
+    python tools/image_batch_ab.py --image-walk [--rounds 5] [--out profiles/image_walk_ab.txt]
+
+A/B of plan option "image_walk" on ONE library (this tree's): set_images(DEVICE, B) + convolve_packed with the option at 0 and at
+1, fresh processes alternating.  Per shape and setting: the step time (HIP events around the timed steps), and from a second,
+profiled pass (plan option "profile") the spectral-row kernel's time per map; "image_walk_active" and the walk the plan's rule
+picks are printed beside them."""
 import argparse
 import json
 import os
@@ -23,6 +30,16 @@ SHAPES = [  # name, H, W, kh, kw, N, B, steps
     ("cfg1 256^2 (x) 31^2 N=1 B=64", 256, 256, 31, 31, 1, 64, 30),
     ("cfg2 1024^2 (x) 63^2 N=16 B=8", 1024, 1024, 63, 63, 16, 8, 20),
     ("cfg5 2048^2 (x) 63^2 N=64 B=4", 2048, 2048, 63, 63, 64, 4, 8),
+]
+# --image-walk: name, H, W, kh, kw, N, B, batch_maps (0: default), rows_group (0: automatic), steps
+WALK_SHAPES = [
+    ("cfg1 256^2 (x) 31^2 N=1 B=16", 256, 256, 31, 31, 1, 16, 0, 0, 60),
+    ("cfg1 256^2 (x) 31^2 N=1 B=64", 256, 256, 31, 31, 1, 64, 0, 0, 30),
+    ("cfg1 256^2 (x) 31^2 N=1 B=64 rows_group 16", 256, 256, 31, 31, 1, 64, 0, 16, 30),     # (the automatic walk of so small a batch is one image)
+    ("cfg2 1024^2 (x) 63^2 N=16 B=8", 1024, 1024, 63, 63, 16, 8, 0, 0, 20),
+    ("cfg2 1024^2 (x) 63^2 N=16 B=8 batch_maps 256", 1024, 1024, 63, 63, 16, 8, 256, 0, 20),
+    ("cfg5 2048^2 (x) 63^2 N=64 B=4 batch_maps 256", 2048, 2048, 63, 63, 64, 4, 256, 0, 8),
+    ("4096^2 (x) 127^2 N=4 B=8", 4096, 4096, 127, 127, 4, 8, 0, 0, 6),
 ]
 
 
@@ -97,15 +114,97 @@ def child(modes):
     print("RESULT " + json.dumps(res))
 
 
+def walk_child(walk):
+    """every WALK_SHAPES entry with "image_walk" = walk: us per step, us of the spectral-row kernel per map"""
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import util
+    fc = util.load_package()
+    dev = torch.device("cuda", 0)
+    res = {}
+    for name, H, W, kh, kw, N, B, batch_maps, rows_group, steps in WALK_SHAPES:
+        s = torch.cuda.Stream(dev)
+        with fc.Plan(H, W, 1, kh, kw) as probe:       # (a block-wise plan holds one image: such a size is measured as one pass)
+            one_pass = {"blockwise": 1} if probe.get_option("blockwise") else None
+        with torch.cuda.stream(s), fc.Plan(H, W, 1, kh, kw, stream=s.cuda_stream, options=one_pass) as p:
+            g = torch.Generator(device="cpu").manual_seed(11)
+            imgs = torch.rand((B, 1, W, H), generator=g, dtype=torch.float32).to(dev)
+            ker = torch.rand((N, 1, kw, kh), generator=g, dtype=torch.float32).to(dev)
+            out = torch.empty((B * N, p.info.fft_w, p.info.fft_h), dtype=torch.float32, device=dev)
+            p.set_option("image_walk", walk)
+            if batch_maps:
+                p.set_option("batch_maps", batch_maps)
+            if rows_group:
+                p.set_option("rows_group", rows_group)
+
+            def step():
+                p.set_images_device(imgs.data_ptr(), B)
+                p.convolve_packed_device(N, ker.data_ptr(), kh, kw, out.data_ptr())
+
+            for _ in range(max(3, steps // 4)):
+                step()
+            p.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(s)
+            for _ in range(steps):
+                step()
+            e1.record(s)
+            e1.synchronize()
+            p.set_option("profile", 1)
+            p.profile(reset=True)
+            for _ in range(3):
+                step()
+            p.synchronize()
+            rows = p.profile(reset=True)["spectral_rows"]
+            res[name] = {"step_us": e0.elapsed_time(e1) * 1000.0 / steps, "rows_us_per_map": rows["ms"] * 1000.0 / max(1, rows["units"]),
+                         "active": p.get_option("image_walk_active"), "transform": "%dx%d" % (p.info.transform_h, p.info.transform_w),
+                         "launches": rows["launches"] // 3}
+    print("RESULT " + json.dumps(res))
+
+
+def walk_main(a):
+    runs = {}
+    for r in range(a.rounds):
+        for walk in (0, 1):
+            o = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "walk%d" % walk], stdout=subprocess.PIPE, text=True, timeout=900)
+            if o.returncode != 0:
+                sys.exit("child failed (image_walk %d, round %d): exit %d" % (walk, r, o.returncode))
+            line = [l for l in o.stdout.splitlines() if l.startswith("RESULT ")][-1]
+            for k, v in json.loads(line[7:]).items():
+                runs.setdefault((k, walk), []).append(v)
+    lines = ["image walk: set_images(DEVICE, B) + convolve_packed, plan option image_walk 0 against 1 on the same library",
+             "median of %d fresh processes per setting, alternating (min .. max); device-resident, HIP events; rows = the spectral-row" % a.rounds,
+             "kernel's time per map from the plan's profile (a second, profiled pass of three steps)", ""]
+    for name, *_ in WALK_SHAPES:
+        base = statistics.median(v["step_us"] for v in runs[(name, 0)])
+        for walk in (0, 1):
+            v = runs[(name, walk)]
+            st, rw = [x["step_us"] for x in v], [x["rows_us_per_map"] for x in v]
+            lines.append("%-46s image_walk %d (active %d, %s, %d row launches)  step %9.1f us (%.1f .. %.1f) x%.3f   rows %7.2f us/map (%.2f .. %.2f)" % (
+                name, walk, v[0]["active"], v[0]["transform"], v[0]["launches"], statistics.median(st), min(st), max(st), statistics.median(st) / base,
+                statistics.median(rw), min(rw), max(rw)))
+        lines.append("")
+    text = "\n".join(lines)
+    print(text)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--image-walk", action="store_true", help="A/B of plan option image_walk on this tree's library")
     ap.add_argument("--parent-lib")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out")
     ap.add_argument("--child", help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.child and a.child.startswith("walk"):
+        return walk_child(int(a.child[4:]))
     if a.child:
         return child(a.child.split(","))
+    if a.image_walk:
+        return walk_main(a)
     if not a.parent_lib or not os.path.exists(a.parent_lib):
         sys.exit("--parent-lib: the parent commit's libfftconv.so")
     runs = {}
