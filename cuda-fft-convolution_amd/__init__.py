@@ -120,7 +120,7 @@ EXPORTED_SYMBOLS = (
     "fftconv_plan_use_spectrum_buffer", "fftconv_plan_export_spectrum", "fftconv_plan_import_spectrum",
     "fftconv_plan_convolve", "fftconv_plan_convolve_packed", "fftconv_plan_prepare_kernels_packed",
     "fftconv_plan_synchronize", "fftconv_plan_set_stream",
-    "fftconv_plan_set_option", "fftconv_plan_set_output_rect", "fftconv_plan_get_option", "fftconv_plan_get_profile",
+    "fftconv_plan_set_option", "fftconv_plan_set_output_rect", "fftconv_plan_set_normalisation", "fftconv_plan_get_option", "fftconv_plan_get_profile",
     "fftconv_fft_data", "fftconv_conv_fft_data",
     "fftconv_multi_create", "fftconv_multi_destroy", "fftconv_multi_set_image", "fftconv_multi_import_spectrum",
     "fftconv_multi_convolve", "fftconv_multi_set_option", "fftconv_multi_get_option",
@@ -194,6 +194,7 @@ def load_library():
     lib.fftconv_plan_set_stream.argtypes = [vp, vp]
     lib.fftconv_plan_set_option.argtypes = [vp, ctypes.c_char_p, ctypes.c_long]
     lib.fftconv_plan_set_output_rect.argtypes = [vp, ci, ci, ci, ci]
+    lib.fftconv_plan_set_normalisation.argtypes = [vp, ci, ci, ci]
     lib.fftconv_plan_get_option.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_long)]
     lib.fftconv_plan_get_profile.argtypes = [vp, ctypes.POINTER(Profile), ci]
     lib.fftconv_fft_data.argtypes = [vp, ci, ci, ci, ci, ci, ci, ctypes.POINTER(vp)]
@@ -520,6 +521,14 @@ class Plan:
         (dense, column-major); info.out_h / out_w / out_map_bytes follow, option "output_region" then reads 5"""
         _check(self._lib.fftconv_plan_set_output_rect(self._h, int(off_h), int(off_w), int(out_h), int(out_w)))
         _check(self._lib.fftconv_plan_get_info(self._h, ctypes.byref(self.info)))
+
+    def set_normalisation(self, mode, box_h=0, box_w=0):
+        """mode 1: every map becomes the zero-mean normalised cross-correlation over the box box_h x box_w -- the size every
+        kernel then has (fftconv_plan_set_normalisation); mode 0: raw maps again.  A call that changes mode or box leaves the
+        plan without an image: set_image / set_images again before the next convolve.  Option "norm_store" (1 default: the
+        output kernel scales in its store where the plan can; 0: always the staged crop), read-only "norm_direct", "normalise",
+        "norm_box_h", "norm_box_w"."""
+        _check(self._lib.fftconv_plan_set_normalisation(self._h, int(mode), int(box_h), int(box_w)))
 
     def get_option(self, name):
         v = ctypes.c_long(0)

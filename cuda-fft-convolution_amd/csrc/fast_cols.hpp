@@ -191,6 +191,18 @@ struct FastColsArgs {
     int rect_w_lo, rect_w_n, rect_wide;
 };
 
+// NORM instantiations only (normalised maps, fftconv_plan_set_normalisation; ncc.hpp): the scale planes D of the plan's images,
+// [image][window column][pitch rows] fp32 with `plane` elements per image.  Map `kernel` of the launch belongs to image
+// (first + kernel) / per_image; the value pair of rows 2n, 2n + 1 of window column w is multiplied by the 8 bytes at
+// d + image * plane + w * pitch + 2n ahead of its store.  A kernel argument of its own, NOT appended to FastColsArgs: a longer
+// FastColsArgs moves the hidden kernel arguments (the grid size) of every kernel that takes it, and every existing output
+// kernel would then compile to other code than its parent's (tools/isa_same.py).
+struct FastColsNormArgs {
+    const float* d = nullptr;
+    size_t plane = 0;
+    int pitch = 0, first = 0, per_image = 0;
+};
+
 template <class C>
 struct ColState {
     c32x2 pre[C::UPT];   // gather of the next tile
@@ -270,8 +282,11 @@ FC_HD int pair_of_unit(int u) {
 // stored, and a store is never wider than its address is known to be aligned -- the pair store where g.rect_wide says every
 // pair is whole and aligned (uniform over the launch), element stores otherwise (a pair then straddles two destination
 // words, and the first / last stored row of a column may be half a pair).
-template <class C, bool TILED, bool SLICED = false, bool DYN = false, bool OUT16 = false, bool RECT = false, class Ctx>
-FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int nwg) {
+// NORM (RECT, fp32 maps): normalised maps -- a value pair is multiplied by the pair of D at its window coordinate ahead of its
+// store (FastColsNormArgs, the body's last argument); the multiply is the only arithmetic added, and the store stays ONE predicated block per pair.
+template <class C, bool TILED, bool SLICED = false, bool DYN = false, bool OUT16 = false, bool RECT = false, bool NORM = false, class Ctx>
+FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int nwg, [[maybe_unused]] const FastColsNormArgs* nrm = nullptr) {
+    static_assert(!NORM || (RECT && !OUT16), "the fused scale exists on the fp32 rectangle family");
     static_assert(!RECT || (TILED && !SLICED), "the rectangle store exists for unsliced launches on the tiled intermediate");
     static_assert(!SLICED || TILED, "column slices exist for the tiled intermediate only");
     static_assert(!(SLICED && DYN), "the sliced tail round is dealt statically");
@@ -546,6 +561,9 @@ FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int
         [[maybe_unused]] const int pair_lo = g.h_lo >> 1;                // complex pairs [pair_lo, pair_lo + nout) of a column are stored
         [[maybe_unused]] const unsigned nout = (unsigned)((g.fft_h - g.h_lo) >> 1);
         [[maybe_unused]] const unsigned nrows = (unsigned)(g.fft_h - g.h_lo);   // RECT: rows [h_lo, h_lo + nrows) of a column are stored
+        // NORM: the scale plane of this tile's image (uniform over the tile)
+        [[maybe_unused]] const float* dplane = nullptr;
+        if constexpr (NORM) dplane = nrm->d + (size_t)((nrm->first + kernel) / nrm->per_image) * nrm->plane;
         ctx.phase([&](int t, [[maybe_unused]] State& st) {
             // the next tile's gather (issued in C1) has had two stages to arrive: take it off the
             // memory counter now, so that landing it does not wait for the stores below
@@ -586,10 +604,17 @@ FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int
                             if constexpr (OUT16) return fc_map16(x, out_bf16);
                             else return x;
                         };
+                        [[maybe_unused]] const float* dcol = nullptr;
+                        if constexpr (NORM) dcol = dplane + (size_t)(w0 + col) * nrm->pitch;
                         static_for<0, R1>([&](auto a_) {
                             constexpr int a = decltype(a_)::value;
                             const int hr = 2 * (j + a * m1) - g.h_lo;
                             if ((unsigned)(hr + 1) <= nrows) {     // rows hr, hr + 1: at least one of them is in [0, nrows)
+                                if constexpr (NORM) {              // (rows 2n, 2n + 1 of a window column: both inside the plane, 8-byte aligned)
+                                    const c32 dv = *reinterpret_cast<const c32*>(dcol + 2 * (j + a * m1));
+                                    v[a].x *= dv.x;
+                                    v[a].y *= dv.y;
+                                }
                                 if (g.rect_wide) {
                                     if constexpr (OUT16) FC_STREAM_STORE4(o + hr, fc_pack_map16(v[a].x, v[a].y, out_bf16));
                                     else FC_STREAM_STORE(reinterpret_cast<c32*>(o + hr), v[a]);

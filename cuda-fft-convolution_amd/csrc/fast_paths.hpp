@@ -535,6 +535,7 @@ struct FastColsShape {
     FastColsVariant variant;
     FastColsArgs a;
     int grid;
+    FastColsNormArgs n{};      // the fused scale of normalised maps only (fast_cols_norm_launch_shape below)
 };
 inline FastColsShape fast_cols_launch_shape(int M, int T, const FastColsArgs& a, int want) {
     FastColsShape r{FastColsVariant::TILED_SLICED, a, 0};
@@ -588,6 +589,38 @@ inline FastColsShape fast_cols_rect_launch_shape(int T, const FastColsArgs& a, i
         r.a.queue_shift = 0;
         while ((16 << r.a.queue_shift) <= r.grid) r.a.queue_shift++;
     }
+    return r;
+}
+
+// Fused scale of normalised maps (fast_cols.hpp: NORM; plan entry fftconv_plan_set_normalisation): the fp32 rectangle kernel
+// multiplies every value pair by the scale plane D at its window coordinate ahead of the store.  A configuration whose kernel
+// spills registers, uses scratch or drops below the 3 waves per SIMD of its launch bounds in the build's reports (csrc/*.rpt) is
+// NOT built and listed here: its plans scale the staged window while it is cropped (kernels_ncc.hip), as every plan without
+// the specialised kernel does.  M = 544 and 2080 started here: their rectangle kernels are not built either.
+constexpr int FC_COLS_NORM_NOT_BUILT[] = {544, 2080};
+constexpr bool fast_cols_norm_built(int M) {
+    for (int x : FC_COLS_NORM_NOT_BUILT)
+        if (x == M) return false;
+    return true;
+}
+inline bool fast_cols_norm_available(int M, bool y_tiled) { return y_tiled && fast_cols_lookup(M).ok && fast_cols_norm_built(M); }
+// Whether the output kernel itself scales the normalised maps of a plan with these settings (fftconv_plan::norm_direct, read-only
+// option "norm_direct"): mode 1 with "norm_store" 1 on a one-pass plan that stores fp32 maps of the window (region 0) or of the
+// caller's rectangle (region 5) and has the kernel.  Everything else is staged.
+inline bool fast_cols_norm_direct(bool normalise, bool norm_store, bool blockwise, int map_format, long region, int M, bool y_tiled) {
+    return normalise && norm_store && !blockwise && map_format == FC_MAP_F32 && (region == 0 || region == 5) && fast_cols_norm_available(M, y_tiled);
+}
+// The launch of nk normalised maps: fast_cols_rect_launch_shape of the rectangle (a plan without one: the whole window, which
+// keeps the pair stores) plus the scale planes d ([image][win_w][win_h]); the maps of the launch are image-major from image
+// image0 on with per_image kernels each (ncc.hpp: ncc_image_of)
+inline FastColsShape fast_cols_norm_launch_shape(int T, const FastColsArgs& a, int off_h, int off_w, int out_h, int out_w, int want, const float* d,
+                                                 int win_h, int win_w, int image0, int per_image) {
+    FastColsShape r = fast_cols_rect_launch_shape(T, a, off_h, off_w, out_h, out_w, want);
+    r.n.d = d;
+    r.n.plane = (size_t)win_h * win_w;
+    r.n.pitch = win_h;
+    r.n.first = image0 * per_image;
+    r.n.per_image = per_image;
     return r;
 }
 

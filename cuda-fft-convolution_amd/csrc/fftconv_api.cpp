@@ -89,6 +89,10 @@ BatchSizes batch_sizes(const fftconv_plan* p, int n, int kw) {
 
 int check_kernel_size(const fftconv_plan* p, int kh, int kw) {
     const Geometry& g = p->g;
+    // normalised maps: the window statistics were taken over the plan's box, and a kernel of another size has another D
+    if (p->opt_normalise && (kh != p->norm_box_h || kw != p->norm_box_w))
+        return api_fail(FFTCONV_ERR_INVALID_ARG, "kernel %dx%d: while normalisation is on every kernel has the size of its box, %ldx%ld "
+                        "(fftconv_plan_set_normalisation)", kh, kw, p->norm_box_h, p->norm_box_w);
     if (kh < 1 || kw < 1 || kh > g.fft_h || kw > g.fft_w)  // src/cudaConvolutionFFT.cu:242
         return api_fail(FFTCONV_ERR_KERNEL_SHAPE,
                     "Kernel and Data must have the same number of features and kernel size should be smaller than data size");
@@ -106,9 +110,27 @@ int check_kernel_size(const fftconv_plan* p, int kh, int kw) {
 
 namespace {
 
-// h-transform of the kernels [a0, a0 + na) of a packed group into the column-spectrum buffer A
-int launch_kernel_cols(fftconv_plan* p, const float* dk, int a0, int na, int kh, int kw) {
+// normalised maps (ncc.hpp): the na kernels at dk, centred per plane and scaled to unit joint norm, into the plan's scratch KN --
+// one kernel for every kernel location, so every entry returns the same bits
+int normalise_kernels(fftconv_plan* p, const float* dk, int na, int kh, int kw) {
     const Geometry& g = p->g;
+    if (int rc = p->KN.ensure((size_t)na * g.F * kh * kw)) return rc;
+    if (int rc = p->NS64.ensure((size_t)2 * na * g.F)) return rc;
+    FC_VERBOSE(p, "kernel normalisation: %d kernels centred per plane and scaled to unit norm", na);
+    HIP_TRY(launch_ncc_unit_kernels(dk, p->KN.p, na, g.F, kh * kw, p->NS64.p, p->stream));
+    return 0;
+}
+
+// h-transform of the kernels [a0, a0 + na) of a packed group into the column-spectrum buffer A
+// (normalised maps: the column pass reads the normalised kernels in KN; in_kn: they are there already -- a deferred request)
+int launch_kernel_cols(fftconv_plan* p, const float* dk, int a0, int na, int kh, int kw, bool in_kn = false) {
+    const Geometry& g = p->g;
+    if (p->opt_normalise) {
+        if (!in_kn)
+            if (int rc = normalise_kernels(p, dk + (size_t)a0 * g.F * kh * kw, na, kh, kw)) return rc;
+        dk = p->KN.p;
+        a0 = 0;
+    }
     if (p->opt_flip_kernels) {   // template matching: correlate instead of convolve (demoCudaConvolutionFFT.m:63-69)
         const size_t chunk = (size_t)na * g.F * kh * kw;
         if (int rc = p->KF.ensure(chunk)) return rc;
@@ -134,7 +156,7 @@ int flush_pending_prepare(fftconv_plan* p) {
     if (!p->a_holds.take_pending(pd)) return 0;
     const hipStream_t cur = p->stream;
     p->stream = static_cast<hipStream_t>(pd.stream);   // where the caller ordered the kernels' readiness
-    const int rc = launch_kernel_cols(p, pd.dk, 0, pd.na, pd.kh, pd.kw);
+    const int rc = launch_kernel_cols(p, pd.dk, 0, pd.na, pd.kh, pd.kw, true);
     p->stream = cur;
     if (!rc) p->a_holds.ready(pd);
     return rc;
@@ -155,6 +177,10 @@ struct Delivery {
     bool cropped = false;
     // the caller's rectangle, stored by the output kernel itself (fftconv_plan::rect_direct): no full window, no crop, no O
     bool rect = false;
+    // normalised maps, decided once per group and read by the launch and its verbose line: fused -- the output kernel scales by D
+    // itself (fftconv_plan::norm_direct; delivered like `rect`: dense maps straight from the output kernel) -- or staged: scaled
+    // while the staged window is cropped (`cropped` is then set whatever the region)
+    bool norm = false, norm_fused = false;
     DevBuf<float>* stage = nullptr;    // staged routes: where the maps wait for their copy (OC for region maps, else O)
     size_t oe = 0;                     // elements per delivered map
     size_t eb = sizeof(float);         // bytes per element ("map_format")
@@ -166,9 +192,12 @@ struct Delivery {
 int plan_delivery(fftconv_plan* p, const Sink& sink, int nbY, Delivery& d) {
     const Geometry& g = p->g;
     if (sink.window && !g.fast_cols.ok) return api_fail(FFTCONV_ERR_INVALID_ARG, "an output window needs the specialised output kernel");
+    if (sink.window && p->opt_normalise) return api_fail(FFTCONV_ERR_INVALID_ARG, "an output window takes no normalisation");
     d.rect = !sink.window && p->rect_direct();
-    d.cropped = p->opt_region != 0 && !d.rect;
-    d.stage = (d.cropped || d.rect) ? &p->OC : &p->O;
+    d.norm = p->opt_normalise != 0;
+    d.norm_fused = d.norm && !sink.window && p->norm_direct();
+    d.cropped = ((p->opt_region != 0 && !d.rect) || d.norm) && !d.norm_fused;
+    d.stage = (d.cropped || d.rect || d.norm_fused) ? &p->OC : &p->O;
     d.oe = p->out_elems();
     d.eb = p->elem_bytes();
     d.kernel_format = d.cropped ? FC_MAP_F32 : (int)p->opt_map_format;
@@ -241,16 +270,29 @@ FastColsShape output_rect_shape(const fftconv_plan* p, const c32* y, float* out,
     return fast_cols_rect_launch_shape(g.fast_cols.T, fa, p->off_h, p->off_w, p->out_h, p->out_w,
                                        persistent_want(g.fast_cols.lds_bytes, g.fast_cols.NT, p->num_cus));
 }
+FastColsShape output_norm_shape(const fftconv_plan* p, const c32* y, float* out, int ny, int image0, int per_image) {
+    const Geometry& g = p->g;
+    const bool rect = p->opt_region == 5;      // (else the whole window as the rectangle)
+    const FastColsArgs fa = fast_cols_args(g, p->d, y, out, p->out_elems(), ny, FC_MAP_F32);
+    return fast_cols_norm_launch_shape(g.fast_cols.T, fa, rect ? p->off_h : 0, rect ? p->off_w : 0, rect ? p->out_h : g.fft_h, rect ? p->out_w : g.fft_w,
+                                       persistent_want(g.fast_cols.lds_bytes, g.fast_cols.NT, p->num_cus), p->ND.p, g.fft_h, g.fft_w, image0, per_image);
+}
 }  // namespace fc
 
 namespace {
 
 // output columns of ny maps: Y transformed along h into the maps at obase (or into the window of an overlap-save block)
 // (rect: the dense maps of the plan's rectangle, stored by the output kernel itself -- Delivery::rect)
-int launch_output_cols(fftconv_plan* p, const OutWindow* win, float* obase, int ny, int format, bool rect) {
+int launch_output_cols(fftconv_plan* p, const OutWindow* win, float* obase, int ny, int format, bool rect, bool norm_fused = false, int image0 = 0,
+                       int per_image = 1) {
     const Geometry& g = p->g;
     if (int rc = p->prof_begin(PK_OUT_COLS, ny)) return rc;
-    if (rect) {
+    if (norm_fused) {
+        const FastColsShape sh = output_norm_shape(p, p->Y.p, obase, ny, image0, per_image);
+        FC_VERBOSE(p, "output kernel: tiled rectangle scaled by D (normalisation: fused), %d workgroups, fp32 elements, rows [%d, %d) of columns [%d, %d), images %d..",
+                   sh.grid, sh.a.h_lo, sh.a.fft_h, sh.a.rect_w_lo, sh.a.rect_w_lo + sh.a.rect_w_n, image0);
+        HIP_TRY(launch_fast_cols_norm(g.M, g.fast_cols.T, sh, p->stream));
+    } else if (rect) {
         const FastColsShape sh = output_rect_shape(p, p->Y.p, obase, ny, format);
         FC_VERBOSE(p, "output kernel: tiled rectangle, %d workgroups, %s elements, rows [%d, %d) of columns [%d, %d)", sh.grid, kMapFormatNames[format],
                    p->off_h, p->off_h + p->out_h, p->off_w, p->off_w + p->out_w);
@@ -337,7 +379,10 @@ int run_group_impl(fftconv_plan* p, int n, const float* dk, int kh, int kw, cons
     if (int rc = plan_delivery(p, sink, nbY, d)) return rc;
     if (p->Y.fresh) {   // before anything is written into it: the tuner may keep another allocation
         // (several images: no automatic tuning -- the tuner's probe launches are shaped for the maps of one image)
-        if (B > 1 && p->opt_tune_placement < 0) p->Y.fresh = false;
+        // (normalised maps: no tuning -- the probe launches are the plain output kernel's, not the scaled launch the group runs; the
+        //  allocation stays marked fresh, so the first group after fftconv_plan_set_normalisation(0) tunes it as a fresh plan's)
+        if (p->opt_normalise) {}
+        else if (B > 1 && p->opt_tune_placement < 0) p->Y.fresh = false;
         else if (int rc = tune_intermediate_placement(p, sink, n * B, nbY, d.cropped ? p->O.p : d.staged() ? d.stage->p : sink.packed, !d.cropped && !d.staged(), d.kernel_format))
             return rc;
     }
@@ -361,9 +406,9 @@ int run_group_impl(fftconv_plan* p, int n, const float* dk, int kh, int kw, cons
                 if (int rc = ring_claim_staging(p, &buf)) return rc;
             float* dest = sink.window ? sink.window->base + (size_t)first * sink.window->map_stride            // where the maps of this batch go
                           : d.staged() ? map_at(d.stage->p, (size_t)buf * nbY * d.oe, d.eb) : map_at(sink.packed, (size_t)first * d.oe, d.eb);
-            if (int rc = launch_output_cols(p, sink.window, d.cropped ? p->O.p : dest, ny, d.kernel_format, d.rect)) return rc;
+            if (int rc = launch_output_cols(p, sink.window, d.cropped ? p->O.p : dest, ny, d.kernel_format, d.rect, d.norm_fused, l.b0, l.nk)) return rc;
             if (d.cropped)
-                if (int rc = launch_region(p, p->O.p, dest, ny, p->stream)) return rc;
+                if (int rc = launch_region(p, p->O.p, dest, ny, p->stream, d.norm ? p->ND.p : nullptr, l.b0, l.nk)) return rc;
             if (int rc = deliver_batch(p, d, sink, first, ny, buf, dest)) return rc;
         }
     }
@@ -409,6 +454,10 @@ const LongOption kLongOptions[] = {
     {"dynamic_tiles", &fftconv_plan::opt_dynamic_tiles, 0, 0, OPT_GET_ONLY},
     {"defer_prepare", &fftconv_plan::opt_defer_prepare, 0, 0, OPT_GET_ONLY},
     {"image_walk", &fftconv_plan::opt_image_walk, 0, 1, OPT_BOOL},      // (nothing cached depends on it: no OPT_FORGETS)
+    {"norm_store", &fftconv_plan::opt_norm_store, 0, 1, OPT_BOOL},       // (the kernel column spectra are the same either way: no OPT_FORGETS)
+    {"normalise", &fftconv_plan::opt_normalise, 0, 0, OPT_GET_ONLY},     // (fftconv_plan_set_normalisation sets the three)
+    {"norm_box_h", &fftconv_plan::norm_box_h, 0, 0, OPT_GET_ONLY},
+    {"norm_box_w", &fftconv_plan::norm_box_w, 0, 0, OPT_GET_ONLY},
 };
 const LongOption* find_option(const char* name, unsigned not_flag) {
     for (const LongOption& o : kLongOptions)
@@ -420,9 +469,20 @@ const LongOption* find_option(const char* name, unsigned not_flag) {
 
 namespace fc {
 
-int launch_region(const fftconv_plan* p, const float* src, float* dst, int nmaps, hipStream_t s) {
+int launch_region(const fftconv_plan* p, const float* src, float* dst, int nmaps, hipStream_t s, const float* scale, int image0, int per_image) {
     const Geometry& g = p->g;      // (block-wise plans: g holds the whole window)
     const int format = (int)p->opt_map_format;      // of dst; src is fp32
+    if (scale) {     // normalised maps: the same pass multiplies by D at the window coordinate; region 0 is the crop of the whole window
+        const int oh = p->opt_region ? p->out_h : g.fft_h, ow = p->opt_region ? p->out_w : g.fft_w;
+        const int fh = p->opt_region ? p->off_h : 0, fw = p->opt_region ? p->off_w : 0;
+        FC_VERBOSE(p, "normalisation: staged -- %d maps of images %d.. scaled by D while %s from the fp32 window into %d x %d %s maps", nmaps, image0,
+                   p->opt_region == 4 ? "padded" : "cropped", oh, ow, kMapFormatNames[format]);
+        if (p->opt_region == 4)
+            HIP_TRY(launch_pad_maps_norm(src, g.fft_h, g.fft_w, g.map_elems(), dst, oh, ow, p->out_elems(), nmaps, scale, image0, per_image, s, format));
+        else
+            HIP_TRY(launch_crop_maps_norm(src, g.fft_h, g.map_elems(), dst, oh, ow, p->out_elems(), fh, fw, nmaps, scale, image0, per_image, s, format));
+        return 0;
+    }
     if (p->opt_region == 5)
         FC_VERBOSE(p, "output rectangle: %d maps cropped from the fp32 window, rows [%d, %d) of columns [%d, %d), into %s maps", nmaps, p->off_h,
                    p->off_h + p->out_h, p->off_w, p->off_w + p->out_w, kMapFormatNames[format]);
@@ -452,6 +512,8 @@ int prepare_kernels(fftconv_plan* p, int n, const float* dk, int kh, int kw, boo
     const int na = std::min(bs.nbA, n);
     const bool timed_apart = p->profile && (p->profile_mask & ((1u << PK_KERNEL_COLS) | (1u << PK_IMAGE_COLS)));   // per-kind figures wanted
     if ((force_defer || p->opt_defer_prepare) && p->g.fast_fwd && !p->opt_flip_kernels && !timed_apart) {   // deferred: rides in the launch of the next image's column pass
+        if (p->opt_normalise)      // (now, while the caller's kernels are there: the deferred column pass reads KN)
+            if (int rc = normalise_kernels(p, dk, na, kh, kw)) return rc;
         p->a_holds.request(ks, na);
         return 0;
     }
@@ -658,7 +720,8 @@ int fftconv_plan_get_info(const fftconv_plan* plan, fftconv_plan_info* info) {
     info->out_h = plan->opt_region ? plan->out_h : g.fft_h;
     info->out_w = plan->opt_region ? plan->out_w : g.fft_w;
     info->out_map_bytes = plan->out_map_bytes();
-    info->workspace_bytes = plan->A.bytes() + plan->Y.bytes() + plan->K.bytes() + plan->O.bytes() + plan->I.bytes();
+    info->workspace_bytes = plan->A.bytes() + plan->Y.bytes() + plan->K.bytes() + plan->O.bytes() + plan->I.bytes() +
+                            plan->ND.bytes() + plan->KN.bytes() + plan->NS64.bytes();      // (normalised maps: all 0 until the mode is on)
     if (const TiledState* ts = plan->tiled) {     // block-wise: the window of the whole image; the spectrum is every block's
         info->spectrum_bytes = ts->spec_total() * sizeof(c32);
         info->map_bytes = ts->big_map() * sizeof(float);
@@ -724,6 +787,10 @@ static int set_images_impl(fftconv_plan* plan, const float* data, int nimg, int 
     // (with the fast row kernel the w-pass stores the spectrum directly in that kernel's register order)
     p->n_images = 0;      // (until the new spectra are queued: a larger batch reallocates the plan's own buffer)
     if (int rc = p->ensure_spectrum(nimg)) return rc;
+    if (p->opt_normalise) {
+        if (int rc = p->ND.ensure(g.map_elems() * (size_t)nimg)) return rc;
+        if (int rc = p->NS64.ensure((size_t)2 * g.F * ncc_strip_columns(g.fft_h, g.fft_w, g.F, (int)p->norm_box_w, FC_NCC_SCRATCH_BYTES) * g.fft_h)) return rc;
+    }
     c32* sgen = p->spec();
     if (p->a_holds.pending_off_stream(p->stream))
         if (int rc = flush_pending_prepare(p)) return rc;
@@ -734,7 +801,7 @@ static int set_images_impl(fftconv_plan* plan, const float* data, int nimg, int 
         ColumnCache::Request pd;
         if (p->a_holds.take_pending(pd)) {
             // the deferred kernel-column pass of fftconv_plan_prepare_kernels_packed and the image's column pass: ONE launch
-            FastColsFwdArgs fk = fast_cols_fwd_args(g, p->d, pd.dk, (size_t)pd.kh * pd.kw, pd.kh, pd.kh, pd.kw, pd.na * g.F, p->A.p,
+            FastColsFwdArgs fk = fast_cols_fwd_args(g, p->d, p->opt_normalise ? p->KN.p : pd.dk, (size_t)pd.kh * pd.kw, pd.kh, pd.kh, pd.kw, pd.na * g.F, p->A.p,
                                                     (size_t)g.rows * a_pitch_for(pd.kw), a_pitch_for(pd.kw), true);
             FC_VERBOSE(p, "image columns (%d tiles) and the columns of %d kernels (%d tiles) in one launch", fa.ntiles, pd.na, fk.ntiles);
             HIP_TRY(launch_fast_cols_fwd_pair(g.M, g.fast_cols.T, fa, fk, fast_cols_fwd_pruned_ok(g.fast_cols, pd.kh), p->num_cus, p->stream));
@@ -746,8 +813,16 @@ static int set_images_impl(fftconv_plan* plan, const float* data, int nimg, int 
         HIP_TRY(launch_cols_r2c(ia, tiles_for(g.W, g.T_cols), planes, cols_threads(g), p->cols_lds(), p->stream));
     }
     if (int rc = p->prof_end()) return rc;
+    if (p->opt_normalise) {      // window statistics (ncc.hpp), while the pixels are still there: D of every image, in strips of columns
+        const int strip = ncc_strip_columns(g.fft_h, g.fft_w, g.F, (int)p->norm_box_w, FC_NCC_SCRATCH_BYTES);
+        FC_VERBOSE(p, "window statistics: box %ld x %ld, %d images, strips of %d columns (%zu bytes of float64 scratch)", p->norm_box_h, p->norm_box_w,
+                   nimg, strip, (size_t)2 * g.F * strip * g.fft_h * sizeof(double));
+        for (int b = 0; b < nimg; b++)
+            HIP_TRY(launch_ncc_statistics(dimg + (size_t)b * g.F * g.H * g.W, g.H, g.W, g.F, g.fft_h, g.fft_w, (int)p->norm_box_h, (int)p->norm_box_w,
+                                          p->NS64.p, strip, p->ND.p + (size_t)b * g.map_elems(), p->stream));
+    }
     if (image_pinned)
-        if (int rc = p->pin_img.mark(p->stream)) return rc;      // the column pass (or the copy) is the last reader
+        if (int rc = p->pin_img.mark(p->stream)) return rc;      // the column pass, the copy or the statistics: the last reader
     if (int rc = p->prof_begin(PK_IMAGE_ROWS, planes)) return rc;
     if (g.fast_rows.ok) {
         HIP_TRY(launch_fast_rows_fwd(g.Lw, fast_rows_fwd_args(g, p->d, sgen), planes * g.rows, p->stream));
@@ -783,6 +858,8 @@ int fftconv_plan_spectrum(fftconv_plan* plan, void** device_ptr, size_t* bytes) 
 
 static int spectrum_exchange(fftconv_plan* p, float* spectrum, int location, bool to_natural) {
     if (!p || !spectrum) return api_fail(FFTCONV_ERR_INVALID_ARG, "NULL argument");
+    if (!to_natural && p->opt_normalise)
+        return api_fail(FFTCONV_ERR_INVALID_ARG, "normalisation is on (fftconv_plan_set_normalisation): an imported spectrum carries no window statistics");
     if (location != FFTCONV_HOST && location != FFTCONV_DEVICE) return api_fail(FFTCONV_ERR_INVALID_ARG, "bad location");
     if (p->tiled) return tiled_unsupported("the spectrum in the reference's order");
     const Geometry& g = p->g;
@@ -845,6 +922,8 @@ int fftconv_plan_use_spectrum_buffer(fftconv_plan* plan, void* device_ptr, size_
 
 int fftconv_plan_mark_spectrum_valid(fftconv_plan* plan) {
     if (!plan) return api_fail(FFTCONV_ERR_INVALID_ARG, "plan is NULL");
+    if (plan->opt_normalise)
+        return api_fail(FFTCONV_ERR_INVALID_ARG, "normalisation is on (fftconv_plan_set_normalisation): a spectrum written by the caller carries no window statistics");
     if (plan->tiled) {
         if (!plan->tiled->spec_base()) return api_fail(FFTCONV_ERR_NO_IMAGE, "the plan has no spectrum buffer yet (fftconv_plan_spectrum / fftconv_plan_use_spectrum_buffer)");
         plan->tiled->have_image = true;
@@ -1062,6 +1141,25 @@ int fftconv_plan_set_output_rect(fftconv_plan* plan, int off_h, int off_w, int o
     return 0;
 }
 
+int fftconv_plan_set_normalisation(fftconv_plan* plan, int mode, int box_h, int box_w) {
+    if (!plan) return api_fail(FFTCONV_ERR_INVALID_ARG, "plan is NULL");
+    const Geometry& g = plan->g;
+    if (const char* why = ncc_args_error(mode, box_h, box_w, g.max_kh, g.max_kw))
+        return api_fail(FFTCONV_ERR_INVALID_ARG, "%s (mode %d, box %d x %d asked of a plan with MAX_KERNEL %d x %d)", why, mode, box_h, box_w, g.max_kh, g.max_kw);
+    if (plan->tiled)
+        return api_fail(FFTCONV_ERR_INVALID_ARG, "normalisation is not available on a block-wise plan (%d blocks: the window statistics span blocks); "
+                        "create a one-pass plan (fftconv_plan_options.blockwise = 1)", plan->tiled->nblk);
+    if (mode == 0) box_h = box_w = 0;
+    if (plan->opt_normalise == mode && plan->norm_box_h == box_h && plan->norm_box_w == box_w) return 0;      // nothing changes: the image stays
+    if (int rc = use_device(plan)) return rc;
+    HIP_TRY(hipStreamSynchronize(plan->stream));
+    // the kernel column spectra are those of the normalised kernels, or not; D belongs to (image, box) and the pixels are gone
+    plan->a_holds.forget();
+    plan->n_images = 0;
+    plan->opt_normalise = mode; plan->norm_box_h = box_h; plan->norm_box_w = box_w;
+    return 0;
+}
+
 int fftconv_plan_get_option(fftconv_plan* plan, const char* name, long* value) {
     if (!plan || !name || !value) return api_fail(FFTCONV_ERR_INVALID_ARG, "null argument");
     // the caller's rectangle (fftconv_plan_set_output_rect), read-only: its offsets (0 without one), and whether the output
@@ -1070,6 +1168,8 @@ int fftconv_plan_get_option(fftconv_plan* plan, const char* name, long* value) {
     if (!strcmp(name, "rect_off_w")) { *value = plan->opt_region == 5 ? plan->off_w : 0; return 0; }
     if (!strcmp(name, "rect_direct")) { *value = plan->rect_direct() ? 1 : 0; return 0; }
     if (!strcmp(name, "rect_store")) { *value = plan->opt_rect_store; return 0; }
+    // read-only: 1 if, with the plan's current settings, the output kernel itself scales normalised maps (else the staged crop does)
+    if (!strcmp(name, "norm_direct")) { *value = plan->norm_direct() ? 1 : 0; return 0; }
     // read-only: 1 if, with the plan's current settings, a spectral-row launch of more than one image walks over images
     if (!strcmp(name, "image_walk_active")) { *value = plan->image_walk_active() ? 1 : 0; return 0; }
     if (!strcmp(name, "blockwise")) { *value = plan->tiled ? plan->tiled->nblk : 0; return 0; }   // read-only: number of blocks (0 = one pass)

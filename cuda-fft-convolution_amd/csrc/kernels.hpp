@@ -27,6 +27,19 @@ hipError_t launch_spectrum_reorder(bool to_natural, c32* S, size_t s_plane, int 
 // dst[map] (dst_h x dst_w >= src) = src[map] in the top-left corner, zero elsewhere
 hipError_t launch_pad_maps(const float* src, int src_h, int src_w, size_t src_map_stride, float* dst, int dst_h, int dst_w,
                            size_t dst_map_stride, int nmaps, hipStream_t s, int format = FC_MAP_F32);
+// ---- normalised cross-correlation maps (kernels_ncc.hip; ncc.hpp)
+// window statistics of ONE image ([f][W][H] at img): the fp32 plane D [fft_w][fft_h] at d, in strips of window columns --
+// scratch holds 2 * F * strip_cols * fft_h doubles (ncc_strip_columns)
+hipError_t launch_ncc_statistics(const float* img, int H, int W, int F, int fft_h, int fft_w, int box_h, int box_w, double* scratch,
+                                 int strip_cols, float* d, hipStream_t s);
+// dst = the n kernels at src ([n][F][plane_elems]) centred per plane and scaled to unit joint norm; stats: 2 * n * F doubles of scratch
+hipError_t launch_ncc_unit_kernels(const float* src, float* dst, int n, int F, int plane_elems, double* stats, hipStream_t s);
+// launch_crop_maps / launch_pad_maps with every element scaled by D ([image][src_w][src_h], images src_map_stride apart) at its
+// window coordinate; map m of the launch belongs to image image0 + m / per_image
+hipError_t launch_crop_maps_norm(const float* src, int src_h, size_t src_map_stride, float* dst, int dst_h, int dst_w, size_t dst_map_stride,
+                                 int off_h, int off_w, int nmaps, const float* D, int image0, int per_image, hipStream_t s, int format = FC_MAP_F32);
+hipError_t launch_pad_maps_norm(const float* src, int src_h, int src_w, size_t src_map_stride, float* dst, int dst_h, int dst_w,
+                                size_t dst_map_stride, int nmaps, const float* D, int image0, int per_image, hipStream_t s, int format = FC_MAP_F32);
 hipError_t launch_cols_r2c(const ColsR2CArgs& a, int tiles, int planes, int threads, size_t lds_bytes, hipStream_t s);
 hipError_t launch_rows_fwd(const RowsFwdArgs& a, int rows, int threads, size_t lds_bytes, hipStream_t s);
 // specialised forward image rows (fast_rows_fwd.hpp); hipErrorInvalidValue if L has no configuration
@@ -44,6 +57,8 @@ hipError_t launch_fast_rows_images(int L, const FastRowsArgs& a, int rows, int i
 hipError_t launch_fast_cols(int M, int T, const FastColsArgs& a, int num_cus, hipStream_t s);
 // the rectangle store of the output kernel (fast_cols.hpp: RECT): `shape` from fast_cols_rect_launch_shape (fast_paths.hpp)
 hipError_t launch_fast_cols_rect(int M, int T, const FastColsShape& shape, hipStream_t s);
+// the fused scale of normalised maps (fast_cols.hpp: NORM): `shape` from fast_cols_norm_launch_shape (fast_paths.hpp)
+hipError_t launch_fast_cols_norm(int M, int T, const FastColsShape& shape, hipStream_t s);
 hipError_t launch_fast_cols_fwd(int M, int T, bool pruned, const FastColsFwdArgs& a, int num_cus, hipStream_t s);
 // image columns (full variant) and kernel columns (pruned or full) of one plan in ONE launch (kernels_cols_fwd.hip)
 hipError_t launch_fast_cols_fwd_pair(int M, int T, const FastColsFwdArgs& image, const FastColsFwdArgs& kernels, bool kernels_pruned,
@@ -65,6 +80,8 @@ template <int G> GroupResult launch_fast_cols16_group(int M, int T, const FastCo
 // (the rectangle store, fp32 and 16-bit maps: kernels_cols_rect_g<G>.hip, kernels_cols_rect16_g<G>.hip)
 template <int G> GroupResult launch_fast_cols_rect_group(int M, int T, const FastColsShape& shape, hipStream_t s);
 template <int G> GroupResult launch_fast_cols_rect16_group(int M, int T, const FastColsShape& shape, hipStream_t s);
+// (the fused scale of normalised maps, fp32: kernels_cols_norm_g<G>.hip)
+template <int G> GroupResult launch_fast_cols_norm_group(int M, int T, const FastColsShape& shape, hipStream_t s);
 template <int G> GroupResult launch_fast_cols_fwd_group(int M, int T, bool pruned, const FastColsFwdArgs& a, int num_cus, hipStream_t s);
 template <int G> GroupResult launch_fast_cols_fwd_pair_group(int M, int T, const FastColsFwdArgs& image, const FastColsFwdArgs& kernels,
                                                              bool kernels_pruned, int num_cus, hipStream_t s);

@@ -24,8 +24,12 @@
 #include "api_internal.hpp"
 #include "column_cache.hpp"
 #include "kernels.hpp"
+#include "ncc.hpp"
 #include "pipeline.hpp"
 
+// default of plan option "norm_store": fused -- it beat the staged route beyond the spread of alternating runs at both geometries
+// measured (cfg3's with 64 maps: 3.90 against 4.98 ms per convolve; cfg2's with 16: 107 against 125 us; profiles/ncc_ab.txt)
+constexpr long FC_NORM_STORE_DEFAULT = 1;
 constexpr long FC_HOST_MIN_KB = 1024;   // default of plan option "host_min_kb" (0 reproduces the threaded path for small maps: tests)
 
 #define HIP_TRY(call)                                                                              \
@@ -243,7 +247,8 @@ struct fftconv_plan {
     // "rect_store" 1: the specialised output kernel stores the rectangle of region 5 itself (fast_cols.hpp: RECT) where it can --
     // rect_direct(); 0, and every plan it cannot serve: the window goes through the fp32 staging O and is cropped like regions 1-3
     long opt_rect_store = 1;
-    bool rect_direct() const { return opt_region == 5 && opt_rect_store && !tiled && fast_cols_rect_available(g.M, g.y_tiled()); }
+    // (normalised maps are scaled while the staged window is cropped: never direct)
+    bool rect_direct() const { return opt_region == 5 && opt_rect_store && !opt_normalise && !tiled && fast_cols_rect_available(g.M, g.y_tiled()); }
     // "image_walk" 1: a spectral-row launch of more than one image runs the kernel that keeps the transformed KERNEL row in
     // registers and walks over images (fast_rows_images.hpp) where the plan has it -- image_walk_active(); 0 (default), and
     // every plan it cannot serve: the walk over kernels.  Nothing cached depends on it.
@@ -251,6 +256,22 @@ struct fftconv_plan {
     bool image_walk_active() const {
         return opt_image_walk && !tiled && g.F == 1 && g.path_mode != 0 && g.fast_rows.ok && fast_rows_images_available(g.Lw, g.max_kw);
     }
+    // fftconv_plan_set_normalisation (ncc.hpp): 1 = the maps are zero-mean normalised cross-correlations over the box norm_box_h x
+    // norm_box_w, the size of every kernel while it is on.  ND holds the scale plane D of every image the plan holds
+    // ([b][fft_w][fft_h], written by set_image / set_images beside the forward transform), KN the normalised kernels T'' of the
+    // chunk whose column spectra are in A -- the column pass reads them instead of the caller's -- NS64 the float64 scratch of both.
+    // "norm_store" 1: the specialised output kernel multiplies by D itself ahead of its store (fast_cols.hpp: NORM) where it
+    // can -- norm_direct(): fp32 maps of the window or of a rectangle on a plan that has the kernel.  0, and everything else
+    // (16-bit maps, "output_region" 1-4, generic / Bluestein / kernel_path 1 or 2 output kernels, configurations that are not
+    // built): STAGED -- the output kernel stores the fp32 window into O as for a cropped region, and the crop / pad kernel
+    // multiplies by D at the window coordinate on the way into the maps (kernels_ncc.hip).
+    long opt_normalise = 0, norm_box_h = 0, norm_box_w = 0;
+    long opt_norm_store = FC_NORM_STORE_DEFAULT;
+    bool norm_direct() const {
+        return fast_cols_norm_direct(opt_normalise != 0, opt_norm_store != 0, tiled != nullptr, (int)opt_map_format, opt_region, g.M, g.y_tiled());
+    }
+    DevBuf<float> ND, KN;
+    DevBuf<double> NS64;
     DevBuf<float> OC;  // cropped maps staged for the copy-out
     size_t out_elems() const { return opt_region ? (size_t)out_h * out_w : g.map_elems(); }   // (block-wise plans: g holds the whole window)
     // "map_format": element format of every result map (fc_common.hpp: FC_MAP_*; one-pass plans only).  The staging buffers O / OC
@@ -347,6 +368,7 @@ struct fftconv_plan {
         fr_tw1.release(); fr_tw2.release(); fr_map.release();
         fc_tw1.release(); fc_tw2.release(); fc_pairs.release(); fc_rowoff.release(); fc_pair_row_of.release();
         nat_row_of.release(); nat_col_of.release(); NS.release(); queue.release();
+        ND.release(); KN.release(); NS64.release();
         pin_img.release(); pin_k.release(); pin_out.release();
         for (int h = 0; h < 2; h++) { if (pin_out_done[h]) (void)hipEventDestroy(pin_out_done[h]); pin_out_done[h] = nullptr; }
     }
@@ -389,7 +411,9 @@ BatchSizes batch_sizes(const fftconv_plan* p, int n, int kw);
 int check_kernel_size(const fftconv_plan* p, int kh, int kw);
 int check_thread_size(const double* thread_size, int n_thread_size);
 // the plan's "output_region" of nmaps full-window maps at src, compacted into dst: 4 pads to the pow2 window, the others crop
-int launch_region(const fftconv_plan* p, const float* src, float* dst, int nmaps, hipStream_t s);
+// scale: normalised maps -- the scale planes D of the plan's images; map m of the launch belongs to image image0 + m / per_image
+int launch_region(const fftconv_plan* p, const float* src, float* dst, int nmaps, hipStream_t s, const float* scale = nullptr, int image0 = 0,
+                  int per_image = 1);
 // Core of the per-kernel loop for n kernels of one size, packed on the device at dk ([n][F][kw][kh]); on failure nothing of the
 // host-output ring is still writing into the caller's buffers when the error is returned
 int run_group(fftconv_plan* p, int n, const float* dk, int kh, int kw, const Sink& sink);
@@ -402,6 +426,9 @@ int plan_create_internal(fftconv_plan** plan, int data_h, int data_w, int featur
 
 // the launch that stores ny maps of the plan's rectangle (fftconv_plan::rect_direct) from the intermediate y, dense from `out` on
 FastColsShape output_rect_shape(const fftconv_plan* p, const c32* y, float* out, int ny, int format);
+// the launch that stores ny normalised maps (fftconv_plan::norm_direct) of the window or of the plan's rectangle: image-major from
+// image image0 on, per_image kernels each
+FastColsShape output_norm_shape(const fftconv_plan* p, const c32* y, float* out, int ny, int image0, int per_image);
 
 // ---- host-output streaming (host_ring.cpp) ----
 // A streamed group (run_group, host maps of at least host_min_kb) has two staging buffers on the device: batch b is computed into

@@ -444,6 +444,42 @@ int fftconv_plan_set_option(fftconv_plan *plan, const char *name, long value);
  * kernel is not built because it would spill registers (1088 and 4160 points along h: exact_window plans of the 1088- / 4160-row
  * windows) -- computes the window and crops it; read-only option "rect_direct" tells which. */
 int fftconv_plan_set_output_rect(fftconv_plan *plan, int off_h, int off_w, int out_h, int out_w);
+/* Normalised cross-correlation maps.  mode 0 (default): the maps are the raw sums of products, bit for bit what they are
+ * without this entry.  mode 1: every map is the zero-mean normalised cross-correlation (MATLAB's normxcorr2, OpenCV's
+ * TM_CCOEFF_NORMED) over the box box_h x box_w, n = box_h * box_w: in [-1, 1], 1 at a perfect match, invariant to gain and
+ * offset of the kernel everywhere and of the image wherever the box lies wholly inside the data (rows >= box_h - 1 and columns
+ * >= box_w - 1 of the window, up to the data's last: the "valid" part).  The padding is zero whatever the image's offset, so a
+ * box that reaches into it sees the offset as an edge; gain alone is invariant everywhere.  With the zero-padded image I (zero outside the data) and, per feature plane f, the sums s1_f(u) /
+ * s2_f(u) of I / I^2 over the box_h x box_w pixels that element u of the FFT_H x FFT_W window sums over:
+ *     den2(u) = sum_f (s2_f - s1_f^2 / n),   e(u) = sum_f s2_f,
+ *     D(u)    = 0 where den2(u) <= 2^-30 e(u) (a window flat to within 2^-15 of its RMS; every window wholly in the padding),
+ *               else den2(u)^(-1/2), rounded once to fp32,
+ *     T''     = the kernel minus its per-plane mean, divided by the joint norm of what is left (all zeros for a constant kernel),
+ *     map_k(u) = D(u) * (I (*) T''_k)(u)          ("flip_kernels" decides convolution or correlation as ever; D is the same).
+ * D is computed once per image by fftconv_plan_set_image / _set_images beside the forward transform (float64 direct sums, in
+ * strips of columns: 32 MiB of transient scratch, or the 16 * F * FFT_H * box_w bytes of a strip of ONE window column where that is
+ * more -- F * FFT_H * box_w > 2^21, e.g. F = 4 with 4224 rows and a 127-wide box: 34.3 MB), T'' once per kernel ahead of its transform (float64), on the device
+ * for every kernel location.  The multiply by D is FUSED into the store of the specialised output kernel where the plan runs it
+ * on the tiled intermediate (kernel_path 0) and stores fp32 maps of the window or of a rectangle: 8C + 4P + 4P bytes per map,
+ * the read of D included.  Everything else is STAGED -- 16-bit maps, "output_region" 1-4, generic / Bluestein /
+ * kernel_path 1 or 2 output kernels, the two transforms whose fused kernel is not built (1088 and 4160 points along h), option
+ * "norm_store" 0: the output kernel stores the fp32 window into the plan's staging and the crop / pad kernel multiplies by D at
+ * the window coordinate while it crops and converts, one extra pass.  Both routes return the same bits; every "map_format",
+ * "output_region", rectangle, delivery route and image batch composes (read-only option "rect_direct" reads 0 meanwhile).
+ * Options: "norm_store" (1 (default): fused where possible; 0: always staged), read-only "norm_direct" (1 if, with the plan's
+ * current settings, the output kernel itself will scale).  Placement tuning does not run while mode 1 is on; an intermediate
+ * allocated meanwhile is tuned by the first convolve after mode 0, as a fresh plan's is.  plan_info.workspace_bytes counts D, T''
+ * and the float64 scratch.
+ * While mode 1 is on EVERY kernel must be exactly box_h x box_w (1 <= box <= MAX_KERNEL per dimension).
+ * Acts like fftconv_plan_set_output_rect: the plan's stream is synchronised and prepared kernels are forgotten.  A call that
+ * changes mode or box leaves the plan WITHOUT an image (option "images" reads 0, a convolve fails with FFTCONV_ERR_NO_IMAGE): D
+ * belongs to (image, box), and the pixels are gone once set_image has returned.  A call that changes nothing keeps the image.
+ * Read-only options beside it: "normalise", "norm_box_h", "norm_box_w".
+ * FFTCONV_ERR_INVALID_ARG, the plan's state untouched: a bad mode or box; a block-wise plan ("blockwise" > 0); while mode 1 is
+ * on, a convolve or prepare whose kernels are not exactly box_h x box_w (ragged cells included), and
+ * fftconv_plan_import_spectrum / fftconv_plan_mark_spectrum_valid (a spectrum carries no window statistics).
+ * The one-shot and two-step entries, fftconv_multi_*, the plan cache and the MEX gateways do not take the option. */
+int fftconv_plan_set_normalisation(fftconv_plan *plan, int mode, int box_h, int box_w);
 /* Current value of an option, plus read-only ones: "tuned_candidates" (allocations tried by the last placement tuning)
  * and "tuned_best" (index of the one kept), "blockwise" (blocks of a block-wise plan, 0 = one pass), "overlap_save" (1: the blocks are stored by the output kernel),
  * "rows_slots_per_cu" (workgroups of the multi-map row kernel a CU holds at once: what the walk length is chosen for),
