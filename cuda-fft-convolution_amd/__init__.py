@@ -71,6 +71,15 @@ MAP_F32, MAP_F16, MAP_BF16 = 0, 1, 2
 MAP_DTYPES = {MAP_F32: np.dtype(np.float32), MAP_F16: np.dtype(np.float16), MAP_BF16: np.dtype(np.uint16)}
 
 
+# Element format of typed image pixels (Plan.set_images_typed / fftconv_plan_set_images_typed): the value of a pixel is its exact
+# float32 conversion, no implied gain.  The format follows from the NumPy dtype; bfloat16 has none -- a uint16 array of bit
+# patterns with pixel_format=PIXEL_BF16 given explicitly.
+PIXEL_F32, PIXEL_U8, PIXEL_U16, PIXEL_F16, PIXEL_BF16 = 0, 1, 2, 3, 4
+PIXEL_DTYPES = {PIXEL_F32: np.dtype(np.float32), PIXEL_U8: np.dtype(np.uint8), PIXEL_U16: np.dtype(np.uint16), PIXEL_F16: np.dtype(np.float16),
+                PIXEL_BF16: np.dtype(np.uint16)}
+_PIXEL_OF_DTYPE = {np.dtype(np.uint8): PIXEL_U8, np.dtype(np.uint16): PIXEL_U16, np.dtype(np.float16): PIXEL_F16}
+
+
 def _options_map_dtype(options):
     """dtype of the maps a one-shot call with these options returns"""
     if options is None:
@@ -116,7 +125,7 @@ EXPORTED_SYMBOLS = (
     "fftconv_cache_configure", "fftconv_cache_clear", "fftconv_cache_stats", "fftconv_last_call_timing",
     "fftconv_plan_create", "fftconv_plan_create_ex",
     "fftconv_plan_is_live", "fftconv_plan_destroy", "fftconv_plan_get_info",
-    "fftconv_plan_set_image", "fftconv_plan_set_images", "fftconv_plan_spectrum", "fftconv_plan_mark_spectrum_valid",
+    "fftconv_plan_set_image", "fftconv_plan_set_images", "fftconv_plan_set_images_typed", "fftconv_plan_spectrum", "fftconv_plan_mark_spectrum_valid",
     "fftconv_plan_use_spectrum_buffer", "fftconv_plan_export_spectrum", "fftconv_plan_import_spectrum",
     "fftconv_plan_convolve", "fftconv_plan_convolve_packed", "fftconv_plan_prepare_kernels_packed",
     "fftconv_plan_synchronize", "fftconv_plan_set_stream",
@@ -182,6 +191,7 @@ def load_library():
     lib.fftconv_plan_get_info.argtypes = [vp, ctypes.POINTER(PlanInfo)]
     lib.fftconv_plan_set_image.argtypes = [vp, vp, ci]
     lib.fftconv_plan_set_images.argtypes = [vp, vp, ci, ci]
+    lib.fftconv_plan_set_images_typed.argtypes = [vp, vp, ci, ci, ci]
     lib.fftconv_plan_spectrum.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(cs)]
     lib.fftconv_plan_mark_spectrum_valid.argtypes = [vp]
     lib.fftconv_plan_use_spectrum_buffer.argtypes = [vp, vp, cs]
@@ -392,6 +402,48 @@ class Plan:
     def set_images_device(self, ptr, n):
         """n images back to back in device memory ([b][f][w][h] floats)"""
         _check(self._lib.fftconv_plan_set_images(self._h, ctypes.c_void_p(int(ptr)), int(n), DEVICE))
+        self._images = int(n)
+
+    # -- typed images: uint8 / uint16 / float16 / bfloat16 pixels, converted in the load (fftconv_plan_set_images_typed)
+    def _typed_format(self, a, pixel_format):
+        if pixel_format is None:
+            if a.dtype not in _PIXEL_OF_DTYPE:
+                raise FFTConvError(-1, "typed pixels are uint8, uint16 or float16 arrays (bfloat16: uint16 bit patterns with "
+                                   "pixel_format=PIXEL_BF16), got %s" % a.dtype)
+            return _PIXEL_OF_DTYPE[a.dtype]
+        fmt = int(pixel_format)
+        if fmt not in PIXEL_DTYPES or fmt == PIXEL_F32 or a.dtype != PIXEL_DTYPES[fmt]:
+            raise FFTConvError(-1, "pixel_format %s does not describe a %s array (float32 images: set_image / set_images)" % (pixel_format, a.dtype))
+        return fmt
+
+    def set_images_typed(self, data, pixel_format=None):
+        """a batch of typed images: host numpy H x W x F x B (H x W x B where the plan's F is 1) of uint8, uint16 or float16 --
+        the format follows from the dtype; bfloat16 is a uint16 array of bit patterns with pixel_format=PIXEL_BF16.  A pixel's
+        value is its exact float32 conversion (no 1/255): the maps are bit-equal to set_images of data.astype(float32)."""
+        a = np.asarray(data)
+        fmt = self._typed_format(a, pixel_format)
+        i = self.info
+        if a.ndim == 3 and i.feature_dim == 1:
+            a = a[:, :, None, :]
+        if a.ndim != 4 or a.shape[:3] != (i.data_h, i.data_w, i.feature_dim) or a.shape[3] < 1:
+            raise FFTConvError(-1, "Invalid data input: shape %s is not H x W x F x B of the plan" % (a.shape,))
+        a = np.asfortranarray(a)
+        _check(self._lib.fftconv_plan_set_images_typed(self._h, ctypes.c_void_p(a.ctypes.data), fmt, int(a.shape[3]), HOST))
+        self._images = int(a.shape[3])
+
+    def set_image_typed(self, data, pixel_format=None):
+        """one typed image: host numpy H x W x F (or H x W), as set_images_typed takes a batch"""
+        a = np.asarray(data)
+        i = self.info
+        if a.ndim == 2:
+            a = a[:, :, None]
+        if a.shape != (i.data_h, i.data_w, i.feature_dim):
+            raise FFTConvError(-1, "Invalid data input: shape %s does not match the plan" % (a.shape,))
+        self.set_images_typed(a[:, :, :, None], pixel_format)
+
+    def set_images_typed_device(self, ptr, pixel_format, n):
+        """n typed images back to back in device memory ([b][f][w][h] elements of pixel_format)"""
+        _check(self._lib.fftconv_plan_set_images_typed(self._h, ctypes.c_void_p(int(ptr)), int(pixel_format), int(n), DEVICE))
         self._images = int(n)
 
     def spectrum(self):

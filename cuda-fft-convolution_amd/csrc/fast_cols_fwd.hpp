@@ -15,11 +15,13 @@
 #include "butterflies.hpp"
 #include "fast_cols.hpp"
 #include "fc_common.hpp"
+#include "pixel_format.hpp"
 
 namespace fc {
 
 struct FastColsFwdArgs {
     const float* in;         // plane q at in + q*in_plane_stride; column c at + c*in_col_pitch, h contiguous
+                             // (typed pixels, pixel_format.hpp: the elements of the body's pixel type behind this pointer; strides in elements)
     size_t in_plane_stride;
     int in_col_pitch;
     int h_in;                // valid samples per column
@@ -41,8 +43,11 @@ struct ColFwdState {
 };
 
 // NZ2 < R2: pruned variant (see header); NZ2 == R2: any h_in <= 2M
-template <class C, int NZ2, class Ctx>
-FC_HD void fast_cols_fwd_body(Ctx& ctx, c32* lds, const FastColsFwdArgs& g, int wg, int nwg) {
+// Px: the pixel type of the input (pixel_format.hpp) -- float, or Pixel8 / Pixel16 with `px` saying which format the elements are
+// and whether a pair of rows comes in one load; only `sample` and the address arithmetic under it depend on it
+template <class C, int NZ2, class Px = float, class Ctx>
+FC_HD void fast_cols_fwd_body(Ctx& ctx, c32* lds, const FastColsFwdArgs& g, int wg, int nwg, [[maybe_unused]] const PixelLoad px = {}) {
+    using Elem = pixel_elem_t<Px>;
     constexpr int M = C::M, R1 = C::R1, R2 = C::R2, R3 = C::R3, T = C::T, NT = C::NT, LP = C::LP, m1 = C::m1;
     constexpr bool PRUNED = NZ2 < R2;
     using State = ColFwdState;
@@ -81,16 +86,29 @@ FC_HD void fast_cols_fwd_body(Ctx& ctx, c32* lds, const FastColsFwdArgs& g, int 
     for (int tile = first_tile; tile < g.ntiles;) {
         const int plane = tile / g.tiles_per_plane;
         const int c0 = (tile - plane * g.tiles_per_plane) * T;
-        const float* in = g.in + (size_t)plane * g.in_plane_stride;
+        const Elem* in = reinterpret_cast<const Elem*>(g.in) + (size_t)plane * g.in_plane_stride;
         c32* out = g.out + (size_t)plane * g.out_plane_stride;
 
         // F1: packed load z[n] = x[2n] + i x[2n+1] fused with stage 1 (radix R1, sub-length m1)
         ctx.phase([&](int t, [[maybe_unused]] State& st) {
             if (dyn && t == 0 && dyn_next < g.ntiles) st.tk = FC_QUEUE_TAKE(g.queue);
-            auto sample = [&](const float* col, int n) -> c32 {
-                float x0 = (2 * n < g.h_in) ? col[2 * n] : 0.f;
-                float x1 = (2 * n + 1 < g.h_in) ? col[2 * n + 1] : 0.f;
-                return mk(x0, x1);
+            auto sample = [&](const Elem* col, int n) -> c32 {
+                if constexpr (std::is_same_v<Px, float>) {
+                    float x0 = (2 * n < g.h_in) ? col[2 * n] : 0.f;
+                    float x1 = (2 * n + 1 < g.h_in) ? col[2 * n + 1] : 0.f;
+                    return mk(x0, x1);
+                } else {
+                    // rows 2n, 2n + 1 in one load where the launch knows every pair aligned (the last sample of an odd h_in has
+                    // no partner to read: element loads), else each element by itself; the conversions are exact
+                    float x0 = 0.f, x1 = 0.f;
+                    if (px.wide && 2 * n + 1 < g.h_in) {
+                        pixel_pair(col + 2 * n, px, x0, x1);
+                    } else {
+                        if (2 * n < g.h_in) x0 = pixel_value(col[2 * n], px);
+                        if (2 * n + 1 < g.h_in) x1 = pixel_value(col[2 * n + 1], px);
+                    }
+                    return mk(x0, x1);
+                }
             };
             if constexpr (PRUNED) {   // one non-zero input per butterfly: outputs z[j] * w_M^(j c)
                 for (int idx = t; idx < T * nz; idx += NT) {
@@ -111,7 +129,7 @@ FC_HD void fast_cols_fwd_body(Ctx& ctx, c32* lds, const FastColsFwdArgs& g, int 
                         c32* q = lds + col * LP + j;
                         c32 v[R1];
                         if (c0 + col < g.ncols) {
-                            const float* colp = in + (size_t)(c0 + col) * g.in_col_pitch;
+                            const Elem* colp = in + (size_t)(c0 + col) * g.in_col_pitch;
                             static_for<0, R1>([&](auto a_) {
                                 constexpr int a = decltype(a_)::value;
                                 v[a] = (j + a * m1 < nz) ? sample(colp, j + a * m1) : mk(0.f, 0.f);

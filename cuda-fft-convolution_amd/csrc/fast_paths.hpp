@@ -5,6 +5,7 @@
 // configs), chosen so that every stage keeps most lanes busy and the LDS budget allows
 // 3 waves per SIMD.  The planner prefers these lengths (planner.hpp: choose_length).
 #pragma once
+#include <array>
 #include <type_traits>
 #include <vector>
 
@@ -411,6 +412,35 @@ inline bool fast_cols_fwd_dispatch_group(int M, int T, bool pruned, Runner&& run
 inline bool fast_cols_fwd_pruned_ok(const FastColsInfo& fi, int h_in) {
     const int nz = (h_in + 1) / 2, m1 = fi.M / fi.R1;
     return fi.R2 > 3 && nz <= m1 && nz <= 3 * fi.R3;
+}
+
+// Typed image pixels (pixel_format.hpp; plan entry fftconv_plan_set_images_typed): the image's forward column kernel converts
+// uint8 / uint16 / fp16 / bf16 elements in its load -- the full variant (NZ2 = R2) of every configuration, one instantiation per
+// element size, the 16-bit format a uniform of the launch.  A configuration whose typed kernel spills registers, uses scratch
+// or drops below the 3 waves per SIMD of its launch bounds in the build's reports (csrc/*.rpt) is NOT built and listed here:
+// its plans convert the image into the fp32 staging first (kernels_pixels.hip), as every plan without the specialised forward
+// column kernel does.  The list is EMPTY: all 32 configurations are within the bound for both element sizes (40 ... 125 VGPRs,
+// 4 ... 8 waves per SIMD; tests/test_pixel_format_host.py holds the reports against it).
+constexpr std::array<int, 0> FC_COLS_FWD_PX_NOT_BUILT{};
+constexpr bool fast_cols_fwd_px_built(int M) {
+    for (int x : FC_COLS_FWD_PX_NOT_BUILT)
+        if (x == M) return false;
+    return true;
+}
+inline bool fast_cols_fwd_px_available(int M) { return fast_cols_lookup(M).ok && fast_cols_fwd_px_built(M); }
+// Whether a typed call on a plan with these settings converts in the column kernel's load (fftconv_plan::pixel_direct, read-only
+// option "pixel_direct"): "pixel_store" 1 on a one-pass plan whose image column pass is the specialised kernel and has the
+// typed instantiation.  Everything else is staged.
+inline bool fast_cols_fwd_px_direct(bool pixel_store, bool blockwise, bool fast_fwd, int M) {
+    return pixel_store && !blockwise && fast_fwd && fast_cols_fwd_px_available(M);
+}
+// The pixel uniforms of a typed forward column launch: the format, and the load form -- a pair of rows in one load only where
+// pixel_pair_load_ok (pixel_format.hpp) says every pair of the launch is aligned for it
+inline PixelLoad fast_cols_fwd_pixel_load(const FastColsFwdArgs& a, int format) {
+    PixelLoad px;
+    px.format = format;
+    px.wide = pixel_pair_load_ok(reinterpret_cast<uintptr_t>(a.in), a.in_col_pitch, a.in_plane_stride, fc_pixel_elem_bytes(format)) ? 1 : 0;
+    return px;
 }
 
 // Sliced tail round of the output kernel (fast_cols.hpp, SLICED): for the small transforms (M <= 1056: the launches of

@@ -455,6 +455,7 @@ const LongOption kLongOptions[] = {
     {"defer_prepare", &fftconv_plan::opt_defer_prepare, 0, 0, OPT_GET_ONLY},
     {"image_walk", &fftconv_plan::opt_image_walk, 0, 1, OPT_BOOL},      // (nothing cached depends on it: no OPT_FORGETS)
     {"norm_store", &fftconv_plan::opt_norm_store, 0, 1, OPT_BOOL},       // (the kernel column spectra are the same either way: no OPT_FORGETS)
+    {"pixel_store", &fftconv_plan::opt_pixel_store, 0, 1, OPT_BOOL},     // (it only chooses the route of the next typed call: no OPT_FORGETS)
     {"normalise", &fftconv_plan::opt_normalise, 0, 0, OPT_GET_ONLY},     // (fftconv_plan_set_normalisation sets the three)
     {"norm_box_h", &fftconv_plan::norm_box_h, 0, 0, OPT_GET_ONLY},
     {"norm_box_w", &fftconv_plan::norm_box_w, 0, 0, OPT_GET_ONLY},
@@ -720,7 +721,7 @@ int fftconv_plan_get_info(const fftconv_plan* plan, fftconv_plan_info* info) {
     info->out_h = plan->opt_region ? plan->out_h : g.fft_h;
     info->out_w = plan->opt_region ? plan->out_w : g.fft_w;
     info->out_map_bytes = plan->out_map_bytes();
-    info->workspace_bytes = plan->A.bytes() + plan->Y.bytes() + plan->K.bytes() + plan->O.bytes() + plan->I.bytes() +
+    info->workspace_bytes = plan->A.bytes() + plan->Y.bytes() + plan->K.bytes() + plan->O.bytes() + plan->I.bytes() + plan->IT.bytes() +
                             plan->ND.bytes() + plan->KN.bytes() + plan->NS64.bytes();      // (normalised maps: all 0 until the mode is on)
     if (const TiledState* ts = plan->tiled) {     // block-wise: the window of the whole image; the spectrum is every block's
         info->spectrum_bytes = ts->spec_total() * sizeof(c32);
@@ -735,9 +736,16 @@ int fftconv_plan_get_info(const fftconv_plan* plan, fftconv_plan_info* info) {
 // Zero-pad + forward transform of nimg images back to back at `data` ([b][f][w][h]): ONE forward pass over nimg * F planes -- the
 // spectra land [b][f][row][s_pitch] in the spectrum buffer, so the column and row kernels run as for one image with more planes
 // and rows, and the launch count is that of one image.
-static int set_images_impl(fftconv_plan* plan, const float* data, int nimg, int location) {
+// fmt: FFTCONV_PIXEL_* of the elements at `vdata` (fftconv_plan_set_images_typed; pixel_format.hpp).  F32 is the call as it always was.
+// A typed image takes one of two routes, decided here once (fftconv_plan::pixel_direct): DIRECT -- the specialised column kernel
+// converts in its load, and the window statistics read the typed elements too: no fp32 image exists; STAGED -- a small kernel
+// writes the fp32 image into I (after the H2D copy of a typed host image: the bytes that cross are the typed ones) and the call
+// goes on as an fp32 one from the device.
+static int set_images_impl(fftconv_plan* plan, const void* vdata, int fmt, int nimg, int location) {
     if (nimg < 1) return api_fail(FFTCONV_ERR_INVALID_ARG, "n_images must be at least 1 (got %d)", nimg);
-    if (!plan || !data) return api_fail(FFTCONV_ERR_INVALID_ARG, "Invalid data input");
+    if (!plan || !vdata) return api_fail(FFTCONV_ERR_INVALID_ARG, "Invalid data input");
+    if (!fc_pixel_format_ok(fmt))
+        return api_fail(FFTCONV_ERR_INVALID_ARG, "pixel_format is 0 (fp32), 1 (uint8), 2 (uint16), 3 (fp16) or 4 (bfloat16), got %d", fmt);
     if (location != FFTCONV_HOST && location != FFTCONV_DEVICE) return api_fail(FFTCONV_ERR_INVALID_ARG, "bad location");
     fftconv_plan* p = plan;
     const Geometry& g = p->g;
@@ -748,30 +756,62 @@ static int set_images_impl(fftconv_plan* plan, const float* data, int nimg, int 
         return api_fail(FFTCONV_ERR_INVALID_ARG, "the caller's spectrum buffer (fftconv_plan_use_spectrum_buffer) holds %zu bytes, %d images need %zu",
                         p->Sx_bytes, nimg, (size_t)nimg * g.spectrum_elems() * sizeof(c32));
     if (int rc = use_device(p)) return rc;
-    if (p->tiled) return tiled_set_image(p, data, location);
+    const bool typed = fmt != FC_PIXEL_F32;
+    const size_t eb = fc_pixel_elem_bytes(fmt);
+    if (p->tiled) {
+        if (!typed) {
+            const int rc = tiled_set_image(p, static_cast<const float*>(vdata), location);
+            if (!rc) p->pixel_format = FC_PIXEL_F32;
+            return rc;
+        }
+        // block-wise: the fp32 image on the device first (typed host pixels after their H2D copy), then the blocks as from a device image
+        const TiledState* ts = p->tiled;
+        const hipStream_t st = ts->sub->stream;
+        const size_t n = (size_t)ts->H * ts->W * ts->F;
+        const void* dtyped = vdata;
+        if (int rc = p->I.ensure(n)) return rc;
+        if (location == FFTCONV_HOST) {
+            if (int rc = p->IT.ensure(floats_for(n, eb))) return rc;
+            HIP_TRY(hipMemcpyAsync(p->IT.p, vdata, n * eb, hipMemcpyHostToDevice, st));
+            dtyped = p->IT.p;
+        }
+        FC_VERBOSE(p, "typed pixels (format %d): staged -- %zu elements converted into the fp32 image staging (block-wise plan)", fmt, n);
+        p->tiled->have_image = false;
+        HIP_TRY(launch_pixels_to_f32(dtyped, fmt, p->I.p, n, st));
+        if (location == FFTCONV_HOST) HIP_TRY(hipStreamSynchronize(st));      // the caller's array has been consumed
+        const int rc = tiled_set_image(p, p->I.p, FFTCONV_DEVICE);
+        if (!rc) p->pixel_format = fmt;
+        return rc;
+    }
     const int planes = nimg * g.F;
-    const float* dimg = data;
+    const bool direct = typed && p->pixel_direct();
+    const void* dimg_any = vdata;   // what the column pass reads: elements of `fmt` on the direct route and for fp32, else (staged) see below
     bool image_pinned = false;      // the caller's array has been consumed by the CPU: no wait for the GPU at the end
+    const size_t n = (size_t)g.H * g.W * planes;      // (the pinned staging takes a whole batch of at most 1 MiB)
     if (location == FFTCONV_HOST) {
-        const size_t n = (size_t)g.H * g.W * planes;      // (the pinned staging takes a whole batch of at most 1 MiB)
-        if (p->opt_host_pinned && n * sizeof(float) <= FC_PIN_IMAGE_BYTES) {
-            if (int rc = p->pin_img.ensure(n * sizeof(float))) return rc;
+        // (typed pixels: the limits are compared against the typed bytes -- four times the uint8 pixels fit; the staged route
+        //  converts on the device, so its copy always lands in IT)
+        DevBuf<float>& dev = typed ? p->IT : p->I;
+        if (p->opt_host_pinned && n * eb <= FC_PIN_IMAGE_BYTES) {
+            if (int rc = p->pin_img.ensure(n * eb)) return rc;
             if (int rc = p->pin_img.wait()) return rc;
-            memcpy(p->pin_img.p, data, n * sizeof(float));
+            memcpy(p->pin_img.p, vdata, n * eb);
             image_pinned = true;
-            if (n * sizeof(float) <= FC_PIN_INPLACE_BYTES) {
-                dimg = reinterpret_cast<const float*>(p->pin_img.p);      // the column pass reads it in place
+            if (n * eb <= FC_PIN_INPLACE_BYTES && (!typed || direct)) {
+                dimg_any = p->pin_img.p;      // the column pass reads it in place
             } else {
-                if (int rc = p->I.ensure(n)) return rc;
-                HIP_TRY(hipMemcpyAsync(p->I.p, p->pin_img.p, n * sizeof(float), hipMemcpyHostToDevice, p->stream));
-                dimg = p->I.p;
+                if (int rc = dev.ensure(floats_for(n, eb))) return rc;
+                HIP_TRY(hipMemcpyAsync(dev.p, p->pin_img.p, n * eb, hipMemcpyHostToDevice, p->stream));
+                dimg_any = dev.p;
             }
         } else {
-            if (int rc = p->I.ensure(n)) return rc;
-            HIP_TRY(hipMemcpyAsync(p->I.p, data, n * sizeof(float), hipMemcpyHostToDevice, p->stream));
-            dimg = p->I.p;
+            if (int rc = dev.ensure(floats_for(n, eb))) return rc;
+            HIP_TRY(hipMemcpyAsync(dev.p, vdata, n * eb, hipMemcpyHostToDevice, p->stream));
+            dimg_any = dev.p;
         }
     }
+    if (typed && !direct)
+        if (int rc = p->I.ensure(n)) return rc;
     FC_VERBOSE(p, "Using GPU : %d", p->gpu_id);                                                    // src/cudaConvolutionFFT.cu:87
     FC_VERBOSE(p, "Data size: h=%d, w=%d, f=%d", g.H, g.W, g.F);                                   // :100
     if (nimg > 1) FC_VERBOSE(p, "Images: %d (one forward pass over %d planes)", nimg, planes);
@@ -786,16 +826,32 @@ static int set_images_impl(fftconv_plan* plan, const float* data, int nimg, int 
                g.fast_fwd ? "specialised" : "generic", g.fast_rows.ok ? "specialised" : "generic", g.y_tiled() ? "tiled" : "row-major", chirp);
     // (with the fast row kernel the w-pass stores the spectrum directly in that kernel's register order)
     p->n_images = 0;      // (until the new spectra are queued: a larger batch reallocates the plan's own buffer)
+    p->pixel_format = FC_PIXEL_F32;
     if (int rc = p->ensure_spectrum(nimg)) return rc;
     if (p->opt_normalise) {
         if (int rc = p->ND.ensure(g.map_elems() * (size_t)nimg)) return rc;
         if (int rc = p->NS64.ensure((size_t)2 * g.F * ncc_strip_columns(g.fft_h, g.fft_w, g.F, (int)p->norm_box_w, FC_NCC_SCRATCH_BYTES) * g.fft_h)) return rc;
     }
     c32* sgen = p->spec();
-    if (p->a_holds.pending_off_stream(p->stream))
+    // (the merged image + kernels launch is fp32-only: a typed image on the direct route launches a pending kernels' column pass by itself)
+    if (direct ? p->a_holds.pending() : p->a_holds.pending_off_stream(p->stream))
         if (int rc = flush_pending_prepare(p)) return rc;
-    if (int rc = p->prof_begin(PK_IMAGE_COLS, planes)) return rc;
-    if (g.fast_fwd) {
+    int sfmt = fmt;                 // the format of what the column pass and the statistics read at dimg_any
+    if (int rc = p->prof_begin(PK_IMAGE_COLS, planes)) return rc;      // (the staged conversion counts as part of the image's column pass)
+    if (typed && !direct) {
+        FC_VERBOSE(p, "typed pixels (format %d): staged -- %zu elements converted into the fp32 image staging", fmt, n);
+        HIP_TRY(launch_pixels_to_f32(dimg_any, fmt, p->I.p, n, p->stream));
+        dimg_any = p->I.p;
+        sfmt = FC_PIXEL_F32;
+    }
+    const float* dimg = static_cast<const float*>(dimg_any);      // (direct route: opaque -- elements of sfmt)
+    if (direct) {
+        FastColsFwdArgs fa = fast_cols_fwd_args(g, p->d, dimg, (size_t)g.H * g.W, g.H, g.H, g.W, planes, sgen,
+                                                (size_t)g.rows * g.s_pitch, g.s_pitch, false);
+        const PixelLoad px = fast_cols_fwd_pixel_load(fa, fmt);
+        FC_VERBOSE(p, "typed pixels (format %d): direct -- converted in the column kernel's load, %s loads", fmt, px.wide ? "pair" : "element");
+        HIP_TRY(launch_fast_cols_fwd_px(g.M, g.fast_cols.T, fa, px, p->num_cus, p->stream));
+    } else if (g.fast_fwd) {
         FastColsFwdArgs fa = fast_cols_fwd_args(g, p->d, dimg, (size_t)g.H * g.W, g.H, g.H, g.W, planes, sgen,
                                                 (size_t)g.rows * g.s_pitch, g.s_pitch, false);
         ColumnCache::Request pd;
@@ -817,9 +873,10 @@ static int set_images_impl(fftconv_plan* plan, const float* data, int nimg, int 
         const int strip = ncc_strip_columns(g.fft_h, g.fft_w, g.F, (int)p->norm_box_w, FC_NCC_SCRATCH_BYTES);
         FC_VERBOSE(p, "window statistics: box %ld x %ld, %d images, strips of %d columns (%zu bytes of float64 scratch)", p->norm_box_h, p->norm_box_w,
                    nimg, strip, (size_t)2 * g.F * strip * g.fft_h * sizeof(double));
+        const size_t seb = fc_pixel_elem_bytes(sfmt);
         for (int b = 0; b < nimg; b++)
-            HIP_TRY(launch_ncc_statistics(dimg + (size_t)b * g.F * g.H * g.W, g.H, g.W, g.F, g.fft_h, g.fft_w, (int)p->norm_box_h, (int)p->norm_box_w,
-                                          p->NS64.p, strip, p->ND.p + (size_t)b * g.map_elems(), p->stream));
+            HIP_TRY(launch_ncc_statistics_typed(static_cast<const char*>(dimg_any) + (size_t)b * g.F * g.H * g.W * seb, sfmt, g.H, g.W, g.F, g.fft_h, g.fft_w,
+                                                (int)p->norm_box_h, (int)p->norm_box_w, p->NS64.p, strip, p->ND.p + (size_t)b * g.map_elems(), p->stream));
     }
     if (image_pinned)
         if (int rc = p->pin_img.mark(p->stream)) return rc;      // the column pass, the copy or the statistics: the last reader
@@ -833,11 +890,17 @@ static int set_images_impl(fftconv_plan* plan, const float* data, int nimg, int 
     if (int rc = p->prof_end()) return rc;
     if (location == FFTCONV_HOST && !image_pinned) HIP_TRY(hipStreamSynchronize(p->stream));
     p->n_images = nimg;
+    p->pixel_format = fmt;
     return 0;
 }
 
-int fftconv_plan_set_image(fftconv_plan* plan, const float* data, int location) { return set_images_impl(plan, data, 1, location); }
-int fftconv_plan_set_images(fftconv_plan* plan, const float* data, int n_images, int location) { return set_images_impl(plan, data, n_images, location); }
+int fftconv_plan_set_image(fftconv_plan* plan, const float* data, int location) { return set_images_impl(plan, data, FC_PIXEL_F32, 1, location); }
+int fftconv_plan_set_images(fftconv_plan* plan, const float* data, int n_images, int location) {
+    return set_images_impl(plan, data, FC_PIXEL_F32, n_images, location);
+}
+int fftconv_plan_set_images_typed(fftconv_plan* plan, const void* data, int pixel_format, int n_images, int location) {
+    return set_images_impl(plan, data, pixel_format, n_images, location);
+}
 
 int fftconv_plan_spectrum(fftconv_plan* plan, void** device_ptr, size_t* bytes) {
     if (!plan) return api_fail(FFTCONV_ERR_INVALID_ARG, "plan is NULL");
@@ -892,7 +955,7 @@ static int spectrum_exchange(fftconv_plan* p, float* spectrum, int location, boo
         if (to_natural) HIP_TRY(hipMemcpyAsync(spectrum, nat, n * sizeof(c32), hipMemcpyDeviceToHost, p->stream));
         HIP_TRY(hipStreamSynchronize(p->stream));
     }
-    if (!to_natural) p->n_images = 1;
+    if (!to_natural) { p->n_images = 1; p->pixel_format = FC_PIXEL_F32; }
     return 0;
 }
 
@@ -926,11 +989,12 @@ int fftconv_plan_mark_spectrum_valid(fftconv_plan* plan) {
         return api_fail(FFTCONV_ERR_INVALID_ARG, "normalisation is on (fftconv_plan_set_normalisation): a spectrum written by the caller carries no window statistics");
     if (plan->tiled) {
         if (!plan->tiled->spec_base()) return api_fail(FFTCONV_ERR_NO_IMAGE, "the plan has no spectrum buffer yet (fftconv_plan_spectrum / fftconv_plan_use_spectrum_buffer)");
+        if (!plan->tiled->have_image) plan->pixel_format = FC_PIXEL_F32;
         plan->tiled->have_image = true;
         return 0;
     }
     if (!plan->spec()) return api_fail(FFTCONV_ERR_NO_IMAGE, "the plan has no spectrum buffer yet (fftconv_plan_spectrum / fftconv_plan_use_spectrum_buffer)");
-    if (plan->n_images < 1) plan->n_images = 1;
+    if (plan->n_images < 1) { plan->n_images = 1; plan->pixel_format = FC_PIXEL_F32; }
     return 0;
 }
 
@@ -1172,6 +1236,14 @@ int fftconv_plan_get_option(fftconv_plan* plan, const char* name, long* value) {
     if (!strcmp(name, "norm_direct")) { *value = plan->norm_direct() ? 1 : 0; return 0; }
     // read-only: 1 if, with the plan's current settings, a spectral-row launch of more than one image walks over images
     if (!strcmp(name, "image_walk_active")) { *value = plan->image_walk_active() ? 1 : 0; return 0; }
+    // typed image pixels (fftconv_plan_set_images_typed), read-only: 1 if a typed call on this plan, with the options as they are,
+    // converts in the column kernel's load; the format of the images the plan holds (0: fp32, an imported spectrum, or none)
+    if (!strcmp(name, "pixel_direct")) { *value = plan->pixel_direct() ? 1 : 0; return 0; }
+    if (!strcmp(name, "pixel_format")) {
+        const bool have = plan->tiled ? plan->tiled->have_image : plan->have_image();
+        *value = have ? plan->pixel_format : 0;
+        return 0;
+    }
     if (!strcmp(name, "blockwise")) { *value = plan->tiled ? plan->tiled->nblk : 0; return 0; }   // read-only: number of blocks (0 = one pass)
     if (!strcmp(name, "overlap_save")) { *value = plan->tiled && plan->tiled->save ? 1 : 0; return 0; }   // read-only: blocks stored by the output kernel (1) or summed (0)
     // read-only: the images the plan holds -- fftconv_plan_set_images' count, 1 after fftconv_plan_set_image, 0 before any image

@@ -238,6 +238,12 @@ hipError_t launch_fast_cols_fwd(int M, int T, bool pruned, const FastColsFwdArgs
     return in_first_group<FC_COL_GROUPS>([&](auto g) { return launch_fast_cols_fwd_group<g.value>(M, T, pruned, a, num_cus, s); });
 }
 
+hipError_t launch_fast_cols_fwd_px(int M, int T, const FastColsFwdArgs& a, const PixelLoad& px, int num_cus, hipStream_t s) {
+    if (a.ntiles <= 0) return hipSuccess;
+    if (!fc_pixel_format_ok(px.format) || px.format == FC_PIXEL_F32) return hipErrorInvalidValue;
+    return in_first_group<FC_COL_GROUPS>([&](auto g) { return launch_fast_cols_fwd_px_group<g.value>(M, T, a, px, num_cus, s); });
+}
+
 hipError_t launch_fast_cols_fwd_pair(int M, int T, const FastColsFwdArgs& image, const FastColsFwdArgs& kernels, bool kernels_pruned,
                                      int num_cus, hipStream_t s) {
     if (image.ntiles <= 0 || kernels.ntiles <= 0) return hipErrorInvalidValue;

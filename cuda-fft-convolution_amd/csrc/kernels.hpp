@@ -32,6 +32,12 @@ hipError_t launch_pad_maps(const float* src, int src_h, int src_w, size_t src_ma
 // scratch holds 2 * F * strip_cols * fft_h doubles (ncc_strip_columns)
 hipError_t launch_ncc_statistics(const float* img, int H, int W, int F, int fft_h, int fft_w, int box_h, int box_w, double* scratch,
                                  int strip_cols, float* d, hipStream_t s);
+// ... of an image of typed pixels (pixel_format: FC_PIXEL_* of pixel_format.hpp; F32: the call above)
+hipError_t launch_ncc_statistics_typed(const void* img, int pixel_format, int H, int W, int F, int fft_h, int fft_w, int box_h, int box_w,
+                                       double* scratch, int strip_cols, float* d, hipStream_t s);
+// (its pass 1 over one strip of typed pixels, kernels_pixels.hip; the error is collected by the caller's hipGetLastError)
+void launch_ncc_column_sums_px(const void* img, const PixelLoad& px, int H, int W, int F, int fft_h, int box_h, int w_start, int ncols, double* c1,
+                               double* c2, hipStream_t s);
 // dst = the n kernels at src ([n][F][plane_elems]) centred per plane and scaled to unit joint norm; stats: 2 * n * F doubles of scratch
 hipError_t launch_ncc_unit_kernels(const float* src, float* dst, int n, int F, int plane_elems, double* stats, hipStream_t s);
 // launch_crop_maps / launch_pad_maps with every element scaled by D ([image][src_w][src_h], images src_map_stride apart) at its
@@ -60,6 +66,11 @@ hipError_t launch_fast_cols_rect(int M, int T, const FastColsShape& shape, hipSt
 // the fused scale of normalised maps (fast_cols.hpp: NORM): `shape` from fast_cols_norm_launch_shape (fast_paths.hpp)
 hipError_t launch_fast_cols_norm(int M, int T, const FastColsShape& shape, hipStream_t s);
 hipError_t launch_fast_cols_fwd(int M, int T, bool pruned, const FastColsFwdArgs& a, int num_cus, hipStream_t s);
+// image columns of typed pixels (kernels_cols_fwd_px_g<G>.hip; pixel_format.hpp): a.in holds elements of px.format, px from
+// fast_cols_fwd_pixel_load; hipErrorInvalidValue for fp32 pixels and for a configuration that is not built (fast_cols_fwd_px_built)
+hipError_t launch_fast_cols_fwd_px(int M, int T, const FastColsFwdArgs& a, const PixelLoad& px, int num_cus, hipStream_t s);
+// the staged route of typed pixels (kernels_pixels.hip): dst[i] = the exact fp32 value of element i of src, n elements
+hipError_t launch_pixels_to_f32(const void* src, int pixel_format, float* dst, size_t n, hipStream_t s);
 // image columns (full variant) and kernel columns (pruned or full) of one plan in ONE launch (kernels_cols_fwd.hip)
 hipError_t launch_fast_cols_fwd_pair(int M, int T, const FastColsFwdArgs& image, const FastColsFwdArgs& kernels, bool kernels_pruned,
                                      int num_cus, hipStream_t s);
@@ -83,6 +94,8 @@ template <int G> GroupResult launch_fast_cols_rect16_group(int M, int T, const F
 // (the fused scale of normalised maps, fp32: kernels_cols_norm_g<G>.hip)
 template <int G> GroupResult launch_fast_cols_norm_group(int M, int T, const FastColsShape& shape, hipStream_t s);
 template <int G> GroupResult launch_fast_cols_fwd_group(int M, int T, bool pruned, const FastColsFwdArgs& a, int num_cus, hipStream_t s);
+// (typed image pixels: kernels_cols_fwd_px_g<G>.hip)
+template <int G> GroupResult launch_fast_cols_fwd_px_group(int M, int T, const FastColsFwdArgs& a, const PixelLoad& px, int num_cus, hipStream_t s);
 template <int G> GroupResult launch_fast_cols_fwd_pair_group(int M, int T, const FastColsFwdArgs& image, const FastColsFwdArgs& kernels,
                                                              bool kernels_pruned, int num_cus, hipStream_t s);
 

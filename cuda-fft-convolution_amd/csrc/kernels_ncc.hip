@@ -107,15 +107,27 @@ __global__ void __launch_bounds__(256) k_pad_maps_norm(const float* __restrict__
 
 hipError_t launch_ncc_statistics(const float* img, int H, int W, int F, int fft_h, int fft_w, int box_h, int box_w, double* scratch,
                                  int strip_cols, float* d, hipStream_t s) {
+    return launch_ncc_statistics_typed(img, FC_PIXEL_F32, H, W, F, fft_h, fft_w, box_h, box_w, scratch, strip_cols, d, s);
+}
+
+hipError_t launch_ncc_statistics_typed(const void* vimg, int pixel_format, int H, int W, int F, int fft_h, int fft_w, int box_h, int box_w,
+                                       double* scratch, int strip_cols, float* d, hipStream_t s) {
     if (fft_h <= 0 || fft_w <= 0 || F <= 0) return hipSuccess;
-    if (box_h < 1 || box_w < 1 || strip_cols < box_w) return hipErrorInvalidValue;
+    if (box_h < 1 || box_w < 1 || strip_cols < box_w || !fc_pixel_format_ok(pixel_format)) return hipErrorInvalidValue;
+    const float* img = static_cast<const float*>(vimg);
+    PixelLoad px;
+    px.format = pixel_format;
     const int per_strip = strip_cols - (box_w - 1);      // window columns a strip yields
     for (int j0 = 0; j0 < fft_w; j0 += per_strip) {
         const int nout = fft_w - j0 < per_strip ? fft_w - j0 : per_strip, ncols = nout + box_w - 1;
         double* c1 = scratch;
         double* c2 = scratch + (size_t)F * ncols * fft_h;
         const unsigned zr = (unsigned)((fft_h + 255) / 256);
-        hipLaunchKernelGGL(k_ncc_column_sums, dim3((unsigned)ncols, (unsigned)F, zr), dim3(256), 0, s, img, H, W, fft_h, box_h, j0 - (box_w - 1), ncols, c1, c2);
+        const dim3 grid((unsigned)ncols, (unsigned)F, zr);
+        if (pixel_format == FC_PIXEL_F32)
+            hipLaunchKernelGGL(k_ncc_column_sums, grid, dim3(256), 0, s, img, H, W, fft_h, box_h, j0 - (box_w - 1), ncols, c1, c2);
+        else      // (typed pixels: the kernel lives in kernels_pixels.hip, so that this unit's device code stays what it was)
+            launch_ncc_column_sums_px(vimg, px, H, W, F, fft_h, box_h, j0 - (box_w - 1), ncols, c1, c2, s);
         hipLaunchKernelGGL(k_ncc_scale, dim3((unsigned)nout, zr), dim3(256), 0, s, c1, c2, ncols, fft_h, F, box_w, box_h * box_w, d + (size_t)j0 * fft_h);
     }
     return hipGetLastError();

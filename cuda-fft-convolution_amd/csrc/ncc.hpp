@@ -15,6 +15,7 @@
 #include <cmath>
 
 #include "fc_common.hpp"
+#include "pixel_format.hpp"
 
 namespace fc {
 
@@ -22,13 +23,16 @@ constexpr double FC_NCC_FLOOR = 1.0 / 1073741824.0;      // 2^-30
 
 // pass 1, one element: sum and sum of squares of rows i - a, a < box_h, of one image column (`col`: its H floats; rows
 // outside [0, H) are the padding)
-FC_HD void ncc_column_sums(const float* col, int H, int i, int box_h, double& s1, double& s2) {
+// Px: the pixel type of the image (pixel_format.hpp; float: the text as it was) -- a typed element goes to float64 through its
+// exact fp32 value, so the sums, and D, are those of the fp32 image to the bit
+template <class Px = float>
+FC_HD void ncc_column_sums(const pixel_elem_t<Px>* col, int H, int i, int box_h, double& s1, double& s2, [[maybe_unused]] const PixelLoad px = {}) {
     s1 = 0.0;
     s2 = 0.0;
     for (int a = 0; a < box_h; a++) {
         const int r = i - a;
         if (r >= 0 && r < H) {
-            const double v = (double)col[r];
+            const double v = (double)pixel_value(col[r], px);
             s1 += v;
             s2 += v * v;      // (exact in float64: a product of two 24-bit significands)
         }

@@ -30,6 +30,9 @@
 // default of plan option "norm_store": fused -- it beat the staged route beyond the spread of alternating runs at both geometries
 // measured (cfg3's with 64 maps: 3.90 against 4.98 ms per convolve; cfg2's with 16: 107 against 125 us; profiles/ncc_ab.txt)
 constexpr long FC_NORM_STORE_DEFAULT = 1;
+// default of plan option "pixel_store" (typed image pixels, fftconv_plan_set_images_typed): direct -- the conversion in the column
+// kernel's load (profiles/pixel_format_ab.txt)
+constexpr long FC_PIXEL_STORE_DEFAULT = 1;
 constexpr long FC_HOST_MIN_KB = 1024;   // default of plan option "host_min_kb" (0 reproduces the threaded path for small maps: tests)
 
 #define HIP_TRY(call)                                                                              \
@@ -281,6 +284,16 @@ struct fftconv_plan {
     size_t out_map_bytes() const { return out_elems() * elem_bytes(); }
     DevBuf<float> O;   // output staging (pointer-array / host output)
     DevBuf<float> I;   // image staging (host input)
+    // Typed image pixels (fftconv_plan_set_images_typed; pixel_format.hpp).  "pixel_store" 1: the image's forward column kernel
+    // converts the elements in its load where it can -- pixel_direct(): a one-pass plan whose image column pass is the specialised
+    // kernel and has the typed instantiation; 0, and every plan it cannot serve (generic / Bluestein column pass, configurations
+    // that are not built, block-wise plans): STAGED -- a small kernel writes the fp32 image into I and the call goes on as an fp32
+    // one.  It only chooses a route: nothing cached depends on it, and it takes effect at the next typed call.
+    // pixel_format: FC_PIXEL_* of the images the plan holds (0 after every other way an image gets in; read with have_image()).
+    long opt_pixel_store = FC_PIXEL_STORE_DEFAULT;
+    long pixel_format = 0;
+    bool pixel_direct() const { return fast_cols_fwd_px_direct(opt_pixel_store != 0, tiled != nullptr, g.fast_fwd, g.M); }
+    DevBuf<float> IT;  // typed pixels on the device: the H2D copy of a typed host image (sized in bytes: floats_for)
     PinBuf pin_img, pin_k, pin_out;   // pinned host staging of small host arrays (PinBuf above)
     hipEvent_t pin_out_done[2] = {nullptr, nullptr};   // copy into each half of pin_out complete
     long opt_host_pinned = 1;         // 0: small host arrays take the plain copies (A/B, tests)
@@ -364,7 +377,7 @@ struct fftconv_plan {
         pending.clear();
         pool.clear();
         tw_m.release(); tw_w.release(); pairs.release();
-        S.release(); A.release(); Y.release(); K.release(); KF.release(); O.release(); OC.release(); I.release();
+        S.release(); A.release(); Y.release(); K.release(); KF.release(); O.release(); OC.release(); I.release(); IT.release();
         fr_tw1.release(); fr_tw2.release(); fr_map.release();
         fc_tw1.release(); fc_tw2.release(); fc_pairs.release(); fc_rowoff.release(); fc_pair_row_of.release();
         nat_row_of.release(); nat_col_of.release(); NS.release(); queue.release();

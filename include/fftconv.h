@@ -275,6 +275,36 @@ int fftconv_plan_set_image(fftconv_plan *plan, const float *data, int location);
  * -1 (automatic) does not tune.  fftconv_multi_*, the one-shot and the two-step entries take one image. */
 int fftconv_plan_set_images(fftconv_plan *plan, const float *data, int n_images, int location);
 
+/* Typed images: camera pixels and half-precision tensors as they are, converted in the load -- the caller writes no fp32 copy,
+ * and a host image crosses the bus in its own bytes (a quarter of fp32's for uint8; the pinned staging of at most 1 MiB and the
+ * 512 KiB read in place are counted in those bytes, so four times the uint8 pixels fit).
+ * `data`: n_images images in the layout of fftconv_plan_set_images ([b][f][w][h], h contiguous, no gaps) in ELEMENTS of
+ * pixel_format, host or device memory, aligned for its element.  The VALUE of a pixel is its exact fp32 conversion -- all four
+ * conversions are exact, so every map is bit-equal to the map fftconv_plan_set_images gives on those fp32 values.  There is no
+ * implied 1/255: gain belongs in the kernels or in the maps; normalised maps (fftconv_plan_set_normalisation) do not depend on
+ * gain anyway; raw uint8 / uint16 sums can overflow fp16 maps ("map_format" 1: 65504).  FFTCONV_PIXEL_BF16 / _F16 elements are
+ * bit patterns (subnormals kept); Inf and NaN pass through as fp32 would carry them.
+ * FFTCONV_PIXEL_F32 is fftconv_plan_set_images itself: the same code path, the same bits.
+ * Failure contract: fftconv_plan_set_images'.  FFTCONV_ERR_INVALID_ARG, the plan's state untouched: NULL, a pixel_format outside
+ * 0..4, n_images < 1, a bad location, n_images > 1 on a block-wise plan, a caller's spectrum buffer that is too small.  A failure
+ * after the transform has started leaves the plan without an image.
+ * Routes.  Direct: on a one-pass plan whose image column pass is the specialised kernel ("specialised_kernels" bit 1) that kernel
+ * loads the typed elements -- rows 2n, 2n + 1 in one 16- / 32-bit load where every such pair is aligned (data pointer, H and H * W
+ * all even in elements), else element by element -- and converts them in registers; the window statistics of normalised maps read
+ * the typed elements too.  Staged: everywhere else (generic and Bluestein / exact_window column passes, block-wise plans) and with
+ * option "pixel_store" 0 one small kernel writes the fp32 image into the plan's staging first (typed host data after its copy to
+ * the device) and the call goes on as fftconv_plan_set_images from device memory.
+ * Options: "pixel_store" (1 (default): direct where possible; 0: always staged -- takes effect at the next typed call),
+ * read-only "pixel_direct" (1 if a typed call on this plan, with the options as they are, converts in the column kernel's load)
+ * and "pixel_format" (the format of the images the plan holds: 0 after fftconv_plan_set_image / _set_images, an imported or
+ * caller-written spectrum, or while it holds none).
+ * "defer_prepare" merges a recorded kernel preparation with the column pass of fp32 images only: a typed image on the direct
+ * route launches the pending kernels' column pass by itself, then its own.  A warm device-resident call allocates nothing, never
+ * synchronises and can be captured into a graph.
+ * Every other entry keeps fp32 images: fftconv_multi_*, the one-shot and two-step entries, the plan cache, the MEX gateways. */
+enum { FFTCONV_PIXEL_F32 = 0, FFTCONV_PIXEL_U8 = 1, FFTCONV_PIXEL_U16 = 2, FFTCONV_PIXEL_F16 = 3, FFTCONV_PIXEL_BF16 = 4 };
+int fftconv_plan_set_images_typed(fftconv_plan *plan, const void *data, int pixel_format, int n_images, int location);
+
 /* Device pointer + size of the image spectrum (library-owned, valid until destroy).  This is the
  * buffer the multi-GPU path broadcasts (the reference's cudaMemcpyPeerAsync of d_CFFT_DATA,
  * src/cudaConvFFTDataStreams.cu:279-289): rank 0 fills it with set_image, the others receive it
