@@ -80,6 +80,11 @@ PIXEL_DTYPES = {PIXEL_F32: np.dtype(np.float32), PIXEL_U8: np.dtype(np.uint8), P
 _PIXEL_OF_DTYPE = {np.dtype(np.uint8): PIXEL_U8, np.dtype(np.uint16): PIXEL_U16, np.dtype(np.float16): PIXEL_F16}
 
 
+# Border modes (Plan.set_border / fftconv_plan_set_border): what the image is beyond its data.  NumPy's np.pad modes of the same
+# extension: constant, edge, symmetric, reflect, wrap.
+BORDER_ZERO, BORDER_CONSTANT, BORDER_REPLICATE, BORDER_SYMMETRIC, BORDER_REFLECT101, BORDER_CIRCULAR = 0, 1, 2, 3, 4, 5
+
+
 def _options_map_dtype(options):
     """dtype of the maps a one-shot call with these options returns"""
     if options is None:
@@ -129,7 +134,7 @@ EXPORTED_SYMBOLS = (
     "fftconv_plan_use_spectrum_buffer", "fftconv_plan_export_spectrum", "fftconv_plan_import_spectrum",
     "fftconv_plan_convolve", "fftconv_plan_convolve_packed", "fftconv_plan_prepare_kernels_packed",
     "fftconv_plan_synchronize", "fftconv_plan_set_stream",
-    "fftconv_plan_set_option", "fftconv_plan_set_output_rect", "fftconv_plan_set_normalisation", "fftconv_plan_get_option", "fftconv_plan_get_profile",
+    "fftconv_plan_set_option", "fftconv_plan_set_output_rect", "fftconv_plan_set_normalisation", "fftconv_plan_set_border", "fftconv_plan_get_option", "fftconv_plan_get_profile",
     "fftconv_fft_data", "fftconv_conv_fft_data",
     "fftconv_multi_create", "fftconv_multi_destroy", "fftconv_multi_set_image", "fftconv_multi_import_spectrum",
     "fftconv_multi_convolve", "fftconv_multi_set_option", "fftconv_multi_get_option",
@@ -205,6 +210,7 @@ def load_library():
     lib.fftconv_plan_set_option.argtypes = [vp, ctypes.c_char_p, ctypes.c_long]
     lib.fftconv_plan_set_output_rect.argtypes = [vp, ci, ci, ci, ci]
     lib.fftconv_plan_set_normalisation.argtypes = [vp, ci, ci, ci]
+    lib.fftconv_plan_set_border.argtypes = [vp, ci, ctypes.c_float]
     lib.fftconv_plan_get_option.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_long)]
     lib.fftconv_plan_get_profile.argtypes = [vp, ctypes.POINTER(Profile), ci]
     lib.fftconv_fft_data.argtypes = [vp, ci, ci, ci, ci, ci, ci, ctypes.POINTER(vp)]
@@ -581,6 +587,17 @@ class Plan:
         output kernel scales in its store where the plan can; 0: always the staged crop), read-only "norm_direct", "normalise",
         "norm_box_h", "norm_box_w"."""
         _check(self._lib.fftconv_plan_set_normalisation(self._h, int(mode), int(box_h), int(box_w)))
+
+    def set_border(self, mode, value=0.0):
+        """what the image is beyond its data (fftconv_plan_set_border): BORDER_ZERO (the default), BORDER_CONSTANT (`value`),
+        BORDER_REPLICATE, BORDER_SYMMETRIC, BORDER_REFLECT101, BORDER_CIRCULAR.  A mode other than BORDER_ZERO makes every map the
+        H x W "same" map anchored on the plan's MAX_KERNEL box (info.out_h / out_w follow; a rectangle inside it may be set
+        afterwards with set_output_rect, in window coordinates); BORDER_ZERO restores the window.  A call that changes mode or
+        value leaves the plan without an image: set_image / set_images again before the next convolve.  Option "border_store"
+        (1, the default: the column kernel maps the indices in its load where the plan can; 0: always the staged extension), read-only
+        "border_direct", "border_mode", "border_lead_h", "border_lead_w"."""
+        _check(self._lib.fftconv_plan_set_border(self._h, int(mode), float(value)))
+        _check(self._lib.fftconv_plan_get_info(self._h, ctypes.byref(self.info)))
 
     def get_option(self, name):
         v = ctypes.c_long(0)

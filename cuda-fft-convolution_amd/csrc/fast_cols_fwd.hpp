@@ -12,6 +12,7 @@
 //     butterfly (a twiddle scaling) and stage 2 reads only its first NZ2 inputs;
 //   * persistent workgroups (tables loaded once), no run-time integer division.
 #pragma once
+#include "border.hpp"
 #include "butterflies.hpp"
 #include "fast_cols.hpp"
 #include "fc_common.hpp"
@@ -45,9 +46,16 @@ struct ColFwdState {
 // NZ2 < R2: pruned variant (see header); NZ2 == R2: any h_in <= 2M
 // Px: the pixel type of the input (pixel_format.hpp) -- float, or Pixel8 / Pixel16 with `px` saying which format the elements are
 // and whether a pair of rows comes in one load; only `sample` and the address arithmetic under it depend on it
-template <class C, int NZ2, class Px = float, class Ctx>
-FC_HD void fast_cols_fwd_body(Ctx& ctx, c32* lds, const FastColsFwdArgs& g, int wg, int nwg, [[maybe_unused]] const PixelLoad px = {}) {
+// Bd: the border of the image (border.hpp; fftconv_plan_set_border) -- NoBorder, or Bordered (fp32 pixels, full variant) with `bd`
+// the uniforms of the launch: g.h_in and g.ncols then count the EXTENDED image (DATA + MAXK - 1) and g.in is the data itself, H
+// samples a column at in_col_pitch -- `sample` maps rows 2n, 2n + 1 and `column` maps the column through border_index; nothing
+// else depends on it
+template <class C, int NZ2, class Px = float, class Bd = NoBorder, class Ctx>
+FC_HD void fast_cols_fwd_body(Ctx& ctx, c32* lds, const FastColsFwdArgs& g, int wg, int nwg, [[maybe_unused]] const PixelLoad px = {},
+                              [[maybe_unused]] const BorderLoad bd = {}) {
     using Elem = pixel_elem_t<Px>;
+    constexpr bool BORDER = std::is_same_v<Bd, Bordered>;
+    static_assert(!BORDER || (std::is_same_v<Px, float> && NZ2 == C::R2), "a border: fp32 pixels, the full variant");
     constexpr int M = C::M, R1 = C::R1, R2 = C::R2, R3 = C::R3, T = C::T, NT = C::NT, LP = C::LP, m1 = C::m1;
     constexpr bool PRUNED = NZ2 < R2;
     using State = ColFwdState;
@@ -93,7 +101,15 @@ FC_HD void fast_cols_fwd_body(Ctx& ctx, c32* lds, const FastColsFwdArgs& g, int 
         ctx.phase([&](int t, [[maybe_unused]] State& st) {
             if (dyn && t == 0 && dyn_next < g.ntiles) st.tk = FC_QUEUE_TAKE(g.queue);
             auto sample = [&](const Elem* col, int n) -> c32 {
-                if constexpr (std::is_same_v<Px, float>) {
+                if constexpr (BORDER) {
+                    // col: the data column the window column maps to; nullptr: a CONSTANT column outside the data, nothing is loaded
+                    const bool fill0 = bd.fill && (col == nullptr || border_outside(bd.h, 2 * n));
+                    const bool fill1 = bd.fill && (col == nullptr || border_outside(bd.h, 2 * n + 1));
+                    float x0 = 0.f, x1 = 0.f;
+                    if (2 * n < g.h_in) x0 = fill0 ? bd.value : col[border_index(bd.h, 2 * n)];
+                    if (2 * n + 1 < g.h_in) x1 = fill1 ? bd.value : col[border_index(bd.h, 2 * n + 1)];
+                    return mk(x0, x1);
+                } else if constexpr (std::is_same_v<Px, float>) {
                     float x0 = (2 * n < g.h_in) ? col[2 * n] : 0.f;
                     float x1 = (2 * n + 1 < g.h_in) ? col[2 * n + 1] : 0.f;
                     return mk(x0, x1);
@@ -129,7 +145,11 @@ FC_HD void fast_cols_fwd_body(Ctx& ctx, c32* lds, const FastColsFwdArgs& g, int 
                         c32* q = lds + col * LP + j;
                         c32 v[R1];
                         if (c0 + col < g.ncols) {
-                            const Elem* colp = in + (size_t)(c0 + col) * g.in_col_pitch;
+                            const Elem* colp;
+                            if constexpr (BORDER)      // once per (tile, column)
+                                colp = (bd.fill && border_outside(bd.w, c0 + col)) ? nullptr : in + (size_t)border_index(bd.w, c0 + col) * g.in_col_pitch;
+                            else
+                                colp = in + (size_t)(c0 + col) * g.in_col_pitch;
                             static_for<0, R1>([&](auto a_) {
                                 constexpr int a = decltype(a_)::value;
                                 v[a] = (j + a * m1 < nz) ? sample(colp, j + a * m1) : mk(0.f, 0.f);

@@ -443,6 +443,28 @@ inline PixelLoad fast_cols_fwd_pixel_load(const FastColsFwdArgs& a, int format) 
     return px;
 }
 
+// Border modes (border.hpp; plan entry fftconv_plan_set_border): the image's forward column kernel maps the indices of the
+// extended image in its load -- fp32 pixels, the full variant (NZ2 = R2) of every configuration, ONE instantiation per
+// configuration, the mode a uniform of the launch.  A configuration whose bordered kernel spills registers, uses scratch or loses a
+// wave per SIMD against its plain sibling in the build's reports (csrc/*.rpt) is NOT built and listed here: its plans take the
+// staged route (kernels_pixels.hip: k_extend_image writes the extended image into the plan's staging), as every plan without the
+// specialised forward column kernel does (tests/test_border_host.py holds the reports against the list).  Listed: 544 (the
+// bordered kernel spills 28 registers into 116 bytes of scratch at 3 waves, its plain sibling holds 110 VGPRs at 4) and 1280, 1536,
+// 1680, 2304 (7 waves per SIMD where the plain kernel has 8).  The other 27 keep their sibling's waves without spills.
+constexpr std::array<int, 5> FC_COLS_FWD_BORDER_NOT_BUILT{544, 1280, 1536, 1680, 2304};
+constexpr bool fast_cols_fwd_border_built(int M) {
+    for (int x : FC_COLS_FWD_BORDER_NOT_BUILT)
+        if (x == M) return false;
+    return true;
+}
+inline bool fast_cols_fwd_border_available(int M) { return fast_cols_lookup(M).ok && fast_cols_fwd_border_built(M); }
+// Whether an image on a plan with a border on and these settings is mapped in the column kernel's load (fftconv_plan::border_direct,
+// read-only option "border_direct"): "border_store" 1 on a one-pass plan whose image column pass is the specialised kernel and has
+// the bordered instantiation.  Everything else is staged.
+inline bool fast_cols_fwd_border_direct(bool border_store, bool blockwise, bool fast_fwd, int M) {
+    return border_store && !blockwise && fast_fwd && fast_cols_fwd_border_available(M);
+}
+
 // Sliced tail round of the output kernel (fast_cols.hpp, SLICED): for the small transforms (M <= 1056: the launches of
 // small problems are a handful of rounds of tiles) a last, partial round of `rem` tiles on `want` persistent workgroups is
 // cut into S = 2^k column slices per tile, S <= want / rem and at least 2 columns per slice.  Fills in the tail fields

@@ -456,6 +456,7 @@ const LongOption kLongOptions[] = {
     {"image_walk", &fftconv_plan::opt_image_walk, 0, 1, OPT_BOOL},      // (nothing cached depends on it: no OPT_FORGETS)
     {"norm_store", &fftconv_plan::opt_norm_store, 0, 1, OPT_BOOL},       // (the kernel column spectra are the same either way: no OPT_FORGETS)
     {"pixel_store", &fftconv_plan::opt_pixel_store, 0, 1, OPT_BOOL},     // (it only chooses the route of the next typed call: no OPT_FORGETS)
+    {"border_store", &fftconv_plan::opt_border_store, 0, 1, OPT_BOOL},   // (it only chooses the route of the next image: no OPT_FORGETS)
     {"normalise", &fftconv_plan::opt_normalise, 0, 0, OPT_GET_ONLY},     // (fftconv_plan_set_normalisation sets the three)
     {"norm_box_h", &fftconv_plan::norm_box_h, 0, 0, OPT_GET_ONLY},
     {"norm_box_w", &fftconv_plan::norm_box_w, 0, 0, OPT_GET_ONLY},
@@ -721,7 +722,7 @@ int fftconv_plan_get_info(const fftconv_plan* plan, fftconv_plan_info* info) {
     info->out_h = plan->opt_region ? plan->out_h : g.fft_h;
     info->out_w = plan->opt_region ? plan->out_w : g.fft_w;
     info->out_map_bytes = plan->out_map_bytes();
-    info->workspace_bytes = plan->A.bytes() + plan->Y.bytes() + plan->K.bytes() + plan->O.bytes() + plan->I.bytes() + plan->IT.bytes() +
+    info->workspace_bytes = plan->A.bytes() + plan->Y.bytes() + plan->K.bytes() + plan->O.bytes() + plan->I.bytes() + plan->IT.bytes() + plan->IE.bytes() +
                             plan->ND.bytes() + plan->KN.bytes() + plan->NS64.bytes();      // (normalised maps: all 0 until the mode is on)
     if (const TiledState* ts = plan->tiled) {     // block-wise: the window of the whole image; the spectrum is every block's
         info->spectrum_bytes = ts->spec_total() * sizeof(c32);
@@ -785,6 +786,12 @@ static int set_images_impl(fftconv_plan* plan, const void* vdata, int fmt, int n
     }
     const int planes = nimg * g.F;
     const bool direct = typed && p->pixel_direct();
+    // A border (fftconv_plan_set_border; border.hpp): the forward pass transforms the image extended to eh x ew samples a plane, one
+    // of two routes, decided here once (fftconv_plan::border_direct): DIRECT -- the specialised column kernel maps the indices in
+    // its load; STAGED -- a small kernel writes the extended image into IE and the column pass runs on that.  A typed image is
+    // converted into I first (pixel_direct() reads 0 meanwhile) and goes on as an fp32 one from the device.
+    const bool border = p->border_mode != 0, bdirect = border && p->border_direct();
+    const int eh = g.H + g.max_kh - 1, ew = g.W + g.max_kw - 1;
     const void* dimg_any = vdata;   // what the column pass reads: elements of `fmt` on the direct route and for fp32, else (staged) see below
     bool image_pinned = false;      // the caller's array has been consumed by the CPU: no wait for the GPU at the end
     const size_t n = (size_t)g.H * g.W * planes;      // (the pinned staging takes a whole batch of at most 1 MiB)
@@ -812,6 +819,8 @@ static int set_images_impl(fftconv_plan* plan, const void* vdata, int fmt, int n
     }
     if (typed && !direct)
         if (int rc = p->I.ensure(n)) return rc;
+    if (border && !bdirect)
+        if (int rc = p->IE.ensure((size_t)eh * ew * planes)) return rc;
     FC_VERBOSE(p, "Using GPU : %d", p->gpu_id);                                                    // src/cudaConvolutionFFT.cu:87
     FC_VERBOSE(p, "Data size: h=%d, w=%d, f=%d", g.H, g.W, g.F);                                   // :100
     if (nimg > 1) FC_VERBOSE(p, "Images: %d (one forward pass over %d planes)", nimg, planes);
@@ -833,8 +842,9 @@ static int set_images_impl(fftconv_plan* plan, const void* vdata, int fmt, int n
         if (int rc = p->NS64.ensure((size_t)2 * g.F * ncc_strip_columns(g.fft_h, g.fft_w, g.F, (int)p->norm_box_w, FC_NCC_SCRATCH_BYTES) * g.fft_h)) return rc;
     }
     c32* sgen = p->spec();
-    // (the merged image + kernels launch is fp32-only: a typed image on the direct route launches a pending kernels' column pass by itself)
-    if (direct ? p->a_holds.pending() : p->a_holds.pending_off_stream(p->stream))
+    // (the merged image + kernels launch is fp32-only and zero-border only: a typed image on the direct route and an image with a
+    //  border launch a pending kernels' column pass by itself)
+    if ((direct || border) ? p->a_holds.pending() : p->a_holds.pending_off_stream(p->stream))
         if (int rc = flush_pending_prepare(p)) return rc;
     int sfmt = fmt;                 // the format of what the column pass and the statistics read at dimg_any
     if (int rc = p->prof_begin(PK_IMAGE_COLS, planes)) return rc;      // (the staged conversion counts as part of the image's column pass)
@@ -845,7 +855,25 @@ static int set_images_impl(fftconv_plan* plan, const void* vdata, int fmt, int n
         sfmt = FC_PIXEL_F32;
     }
     const float* dimg = static_cast<const float*>(dimg_any);      // (direct route: opaque -- elements of sfmt)
-    if (direct) {
+    if (border) {
+        const BorderLoad bd = border_load((int)p->border_mode, p->border_value, g.H, g.W, g.max_kh, g.max_kw);
+        if (bdirect) {      // the data as it lies; the counts are the extension's
+            FastColsFwdArgs fa = fast_cols_fwd_args(g, p->d, dimg, (size_t)g.H * g.W, g.H, eh, ew, planes, sgen, (size_t)g.rows * g.s_pitch, g.s_pitch, false);
+            FC_VERBOSE(p, "border (mode %ld): direct -- mapped in the column kernel's load", p->border_mode);
+            HIP_TRY(launch_fast_cols_fwd_border(g.M, g.fast_cols.T, fa, bd, p->num_cus, p->stream));
+        } else {
+            FC_VERBOSE(p, "border (mode %ld): staged -- %zu elements extended into the fp32 image staging", p->border_mode, (size_t)eh * ew * planes);
+            HIP_TRY(launch_extend_image(dimg, p->IE.p, g.H, g.W, eh, ew, (size_t)planes, bd, p->stream));
+            if (g.fast_fwd) {
+                FastColsFwdArgs fa = fast_cols_fwd_args(g, p->d, p->IE.p, (size_t)eh * ew, eh, eh, ew, planes, sgen, (size_t)g.rows * g.s_pitch, g.s_pitch, false);
+                HIP_TRY(launch_fast_cols_fwd(g.M, g.fast_cols.T, false, fa, p->num_cus, p->stream));
+            } else {
+                ColsR2CArgs ia = image_cols_args(g, p->t, p->d, p->IE.p, sgen);
+                ia.in_plane_stride = (size_t)eh * ew; ia.in_col_pitch = eh; ia.h_in = eh; ia.ncols = ew;
+                HIP_TRY(launch_cols_r2c(ia, tiles_for(ew, g.T_cols), planes, cols_threads(g), p->cols_lds(), p->stream));
+            }
+        }
+    } else if (direct) {
         FastColsFwdArgs fa = fast_cols_fwd_args(g, p->d, dimg, (size_t)g.H * g.W, g.H, g.H, g.W, planes, sgen,
                                                 (size_t)g.rows * g.s_pitch, g.s_pitch, false);
         const PixelLoad px = fast_cols_fwd_pixel_load(fa, fmt);
@@ -882,9 +910,9 @@ static int set_images_impl(fftconv_plan* plan, const void* vdata, int fmt, int n
         if (int rc = p->pin_img.mark(p->stream)) return rc;      // the column pass, the copy or the statistics: the last reader
     if (int rc = p->prof_begin(PK_IMAGE_ROWS, planes)) return rc;
     if (g.fast_rows.ok) {
-        HIP_TRY(launch_fast_rows_fwd(g.Lw, fast_rows_fwd_args(g, p->d, sgen), planes * g.rows, p->stream));
+        HIP_TRY(launch_fast_rows_fwd(g.Lw, fast_rows_fwd_args(g, p->d, sgen, p->border_cols()), planes * g.rows, p->stream));
     } else {
-        RowsFwdArgs ra = image_rows_args(g, p->t, p->d, sgen);
+        RowsFwdArgs ra = image_rows_args(g, p->t, p->d, sgen, p->border_cols());
         HIP_TRY(launch_rows_fwd(ra, planes * g.rows, rows_threads(g), g.rows_fwd_lds_bytes(), p->stream));
     }
     if (int rc = p->prof_end()) return rc;
@@ -923,6 +951,8 @@ static int spectrum_exchange(fftconv_plan* p, float* spectrum, int location, boo
     if (!p || !spectrum) return api_fail(FFTCONV_ERR_INVALID_ARG, "NULL argument");
     if (!to_natural && p->opt_normalise)
         return api_fail(FFTCONV_ERR_INVALID_ARG, "normalisation is on (fftconv_plan_set_normalisation): an imported spectrum carries no window statistics");
+    if (!to_natural && p->border_mode)
+        return api_fail(FFTCONV_ERR_INVALID_ARG, "a border is on (fftconv_plan_set_border, mode %ld): an imported spectrum carries no border", p->border_mode);
     if (location != FFTCONV_HOST && location != FFTCONV_DEVICE) return api_fail(FFTCONV_ERR_INVALID_ARG, "bad location");
     if (p->tiled) return tiled_unsupported("the spectrum in the reference's order");
     const Geometry& g = p->g;
@@ -987,6 +1017,8 @@ int fftconv_plan_mark_spectrum_valid(fftconv_plan* plan) {
     if (!plan) return api_fail(FFTCONV_ERR_INVALID_ARG, "plan is NULL");
     if (plan->opt_normalise)
         return api_fail(FFTCONV_ERR_INVALID_ARG, "normalisation is on (fftconv_plan_set_normalisation): a spectrum written by the caller carries no window statistics");
+    if (plan->border_mode)
+        return api_fail(FFTCONV_ERR_INVALID_ARG, "a border is on (fftconv_plan_set_border, mode %ld): a spectrum written by the caller carries no border", plan->border_mode);
     if (plan->tiled) {
         if (!plan->tiled->spec_base()) return api_fail(FFTCONV_ERR_NO_IMAGE, "the plan has no spectrum buffer yet (fftconv_plan_spectrum / fftconv_plan_use_spectrum_buffer)");
         if (!plan->tiled->have_image) plan->pixel_format = FC_PIXEL_F32;
@@ -1213,6 +1245,9 @@ int fftconv_plan_set_normalisation(fftconv_plan* plan, int mode, int box_h, int 
     if (plan->tiled)
         return api_fail(FFTCONV_ERR_INVALID_ARG, "normalisation is not available on a block-wise plan (%d blocks: the window statistics span blocks); "
                         "create a one-pass plan (fftconv_plan_options.blockwise = 1)", plan->tiled->nblk);
+    if (mode != 0 && plan->border_mode)
+        return api_fail(FFTCONV_ERR_INVALID_ARG, "a border is on (fftconv_plan_set_border, mode %ld): the window statistics of normalised maps assume zero padding",
+                        plan->border_mode);
     if (mode == 0) box_h = box_w = 0;
     if (plan->opt_normalise == mode && plan->norm_box_h == box_h && plan->norm_box_w == box_w) return 0;      // nothing changes: the image stays
     if (int rc = use_device(plan)) return rc;
@@ -1224,8 +1259,42 @@ int fftconv_plan_set_normalisation(fftconv_plan* plan, int mode, int box_h, int 
     return 0;
 }
 
+int fftconv_plan_set_border(fftconv_plan* plan, int mode, float value) {
+    if (!plan) return api_fail(FFTCONV_ERR_INVALID_ARG, "plan is NULL");
+    const Geometry& g = plan->g;
+    if (const char* why = border_args_error(mode, value, g.H, g.W, g.max_kh, g.max_kw))
+        return api_fail(FFTCONV_ERR_INVALID_ARG, "%s (mode %d, value %g asked of a plan with DATA %d x %d and MAX_KERNEL %d x %d)", why, mode, (double)value, g.H,
+                        g.W, g.max_kh, g.max_kw);
+    if (plan->tiled)
+        return api_fail(FFTCONV_ERR_INVALID_ARG, "a border is not available on a block-wise plan (%d blocks: the blocks' own rims lie inside the image); "
+                        "create a one-pass plan (fftconv_plan_options.blockwise = 1)", plan->tiled->nblk);
+    if (mode != 0 && plan->opt_normalise)
+        return api_fail(FFTCONV_ERR_INVALID_ARG, "normalisation is on (fftconv_plan_set_normalisation): the window statistics of normalised maps assume zero padding");
+    if (mode != FC_BORDER_CONSTANT) value = 0.f;
+    if (plan->border_mode == mode && plan->border_value == value) return 0;      // nothing changes: the image and the rectangle stay
+    if (int rc = use_device(plan)) return rc;
+    HIP_TRY(hipStreamSynchronize(plan->stream));
+    plan->release_ring();          // sized for the map bytes
+    // as fftconv_plan_set_output_rect: prepared kernels are forgotten; and the spectrum belongs to (image, border)
+    plan->a_holds.forget();
+    plan->n_images = 0;
+    plan->border_mode = mode; plan->border_value = value;
+    if (mode) {      // the H x W "same" map anchored on the MAX_KERNEL box: the part of the window the cyclic wrap does not reach
+        plan->opt_region = 5; plan->out_h = g.H; plan->out_w = g.W; plan->off_h = g.max_kh - 1; plan->off_w = g.max_kw - 1;
+    } else {
+        plan->opt_region = 0; plan->out_h = g.fft_h; plan->out_w = g.fft_w; plan->off_h = 0; plan->off_w = 0;
+    }
+    return 0;
+}
+
 int fftconv_plan_get_option(fftconv_plan* plan, const char* name, long* value) {
     if (!plan || !name || !value) return api_fail(FFTCONV_ERR_INVALID_ARG, "null argument");
+    // border modes (fftconv_plan_set_border), read-only: the mode, where data sample 0 lies in the window, and whether the next
+    // image on this plan, with the options as they are, is mapped in the column kernel's load (0 without a border)
+    if (!strcmp(name, "border_mode")) { *value = plan->border_mode; return 0; }
+    if (!strcmp(name, "border_lead_h")) { *value = plan->border_mode ? border_lead(plan->g.max_kh) : 0; return 0; }
+    if (!strcmp(name, "border_lead_w")) { *value = plan->border_mode ? border_lead(plan->g.max_kw) : 0; return 0; }
+    if (!strcmp(name, "border_direct")) { *value = plan->border_direct() ? 1 : 0; return 0; }
     // the caller's rectangle (fftconv_plan_set_output_rect), read-only: its offsets (0 without one), and whether the output
     // kernel stores it itself with the plan's current settings
     if (!strcmp(name, "rect_off_h")) { *value = plan->opt_region == 5 ? plan->off_h : 0; return 0; }

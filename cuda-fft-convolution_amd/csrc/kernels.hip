@@ -244,6 +244,12 @@ hipError_t launch_fast_cols_fwd_px(int M, int T, const FastColsFwdArgs& a, const
     return in_first_group<FC_COL_GROUPS>([&](auto g) { return launch_fast_cols_fwd_px_group<g.value>(M, T, a, px, num_cus, s); });
 }
 
+hipError_t launch_fast_cols_fwd_border(int M, int T, const FastColsFwdArgs& a, const BorderLoad& bd, int num_cus, hipStream_t s) {
+    if (a.ntiles <= 0) return hipSuccess;
+    if (!fc_border_mode_ok(bd.mode) || bd.mode == FC_BORDER_ZERO) return hipErrorInvalidValue;
+    return in_first_group<FC_COL_GROUPS>([&](auto g) { return launch_fast_cols_fwd_border_group<g.value>(M, T, a, bd, num_cus, s); });
+}
+
 hipError_t launch_fast_cols_fwd_pair(int M, int T, const FastColsFwdArgs& image, const FastColsFwdArgs& kernels, bool kernels_pruned,
                                      int num_cus, hipStream_t s) {
     if (image.ntiles <= 0 || kernels.ntiles <= 0) return hipErrorInvalidValue;

@@ -71,6 +71,12 @@ hipError_t launch_fast_cols_fwd(int M, int T, bool pruned, const FastColsFwdArgs
 hipError_t launch_fast_cols_fwd_px(int M, int T, const FastColsFwdArgs& a, const PixelLoad& px, int num_cus, hipStream_t s);
 // the staged route of typed pixels (kernels_pixels.hip): dst[i] = the exact fp32 value of element i of src, n elements
 hipError_t launch_pixels_to_f32(const void* src, int pixel_format, float* dst, size_t n, hipStream_t s);
+// image columns with a border (kernels_cols_fwd_border_g<G>.hip; border.hpp): a.in is the data, a.h_in / a.ncols count the extended
+// image, bd from border_load; hipErrorInvalidValue for mode 0 and for a configuration that is not built (fast_cols_fwd_border_built)
+hipError_t launch_fast_cols_fwd_border(int M, int T, const FastColsFwdArgs& a, const BorderLoad& bd, int num_cus, hipStream_t s);
+// the staged route of a border (kernels_pixels.hip): dst = the extended image E of `planes` planes of H x W fp32 pixels at src,
+// (H + MAXK_H - 1) x (W + MAXK_W - 1) per plane, dense
+hipError_t launch_extend_image(const float* src, float* dst, int H, int W, int ext_h, int ext_w, size_t planes, const BorderLoad& bd, hipStream_t s);
 // image columns (full variant) and kernel columns (pruned or full) of one plan in ONE launch (kernels_cols_fwd.hip)
 hipError_t launch_fast_cols_fwd_pair(int M, int T, const FastColsFwdArgs& image, const FastColsFwdArgs& kernels, bool kernels_pruned,
                                      int num_cus, hipStream_t s);
@@ -96,6 +102,8 @@ template <int G> GroupResult launch_fast_cols_norm_group(int M, int T, const Fas
 template <int G> GroupResult launch_fast_cols_fwd_group(int M, int T, bool pruned, const FastColsFwdArgs& a, int num_cus, hipStream_t s);
 // (typed image pixels: kernels_cols_fwd_px_g<G>.hip)
 template <int G> GroupResult launch_fast_cols_fwd_px_group(int M, int T, const FastColsFwdArgs& a, const PixelLoad& px, int num_cus, hipStream_t s);
+// (an image with a border: kernels_cols_fwd_border_g<G>.hip)
+template <int G> GroupResult launch_fast_cols_fwd_border_group(int M, int T, const FastColsFwdArgs& a, const BorderLoad& bd, int num_cus, hipStream_t s);
 template <int G> GroupResult launch_fast_cols_fwd_pair_group(int M, int T, const FastColsFwdArgs& image, const FastColsFwdArgs& kernels,
                                                              bool kernels_pruned, int num_cus, hipStream_t s);
 

@@ -5,6 +5,7 @@
 // of a plan that has the typed column kernel.  Also here, so that kernels_ncc.hip compiles what it compiled before: pass 1 of
 // the window statistics of normalised maps over typed pixels, which the DIRECT route needs.
 #include "kernels.hpp"
+#include "border.hpp"
 #include "ncc.hpp"
 #include "pixel_format.hpp"
 
@@ -36,7 +37,32 @@ __global__ void __launch_bounds__(256) k_ncc_column_sums_px(const pixel_elem_t<P
     c2[at + i] = s2;
 }
 
+// Border modes (border.hpp; fftconv_plan_set_border), the STAGED route: the extended image E -- (H + MAXK_H - 1) x (W + MAXK_W - 1)
+// samples per plane, through the index function the bordered column kernel maps its loads with -- written into the plan's
+// staging; the column pass then runs on it as on an image of that size.  Not on the hot path of a plan that has the bordered
+// column kernel.  (One element per iteration of a grid-stride loop; the divisions are by uniforms.)
+__global__ void __launch_bounds__(256) k_extend_image(const float* __restrict__ src, float* __restrict__ dst, int H, int W, int ext_h, int ext_w,
+                                                      size_t n, BorderLoad bd) {
+    const size_t step = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {
+        const size_t cq = i / (size_t)ext_h;
+        const int r = (int)(i - cq * (size_t)ext_h);
+        const size_t q = cq / (size_t)ext_w;
+        const int c = (int)(cq - q * (size_t)ext_w);
+        dst[i] = border_sample(src + q * ((size_t)H * W), H, bd, r, c);
+    }
+}
+
 }  // namespace
+
+hipError_t launch_extend_image(const float* src, float* dst, int H, int W, int ext_h, int ext_w, size_t planes, const BorderLoad& bd, hipStream_t s) {
+    const size_t n = planes * (size_t)ext_h * ext_w;
+    if (n == 0) return hipSuccess;
+    if (!fc_border_mode_ok(bd.mode) || bd.mode == FC_BORDER_ZERO || ext_h < H || ext_w < W) return hipErrorInvalidValue;
+    const size_t blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(k_extend_image, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, s, src, dst, H, W, ext_h, ext_w, n, bd);
+    return hipGetLastError();
+}
 
 void launch_ncc_column_sums_px(const void* img, const PixelLoad& px, int H, int W, int F, int fft_h, int box_h, int w_start, int ncols, double* c1,
                                double* c2, hipStream_t s) {

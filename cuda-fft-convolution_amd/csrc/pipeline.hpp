@@ -233,9 +233,11 @@ inline ColsR2CArgs image_cols_args(const Geometry& g, const Tables& t, const Dev
     return a;
 }
 
-inline RowsFwdArgs image_rows_args(const Geometry& g, const Tables& t, const DeviceTables& d, c32* S) {
+// (border_cols: the columns a border adds to the image -- MAX_KERNEL_W - 1 while fftconv_plan_set_border is on, else 0: the column
+//  pass has written the spectra of W + border_cols columns)
+inline RowsFwdArgs image_rows_args(const Geometry& g, const Tables& t, const DeviceTables& d, c32* S, int border_cols = 0) {
     RowsFwdArgs a{};
-    a.S = S; a.pitch = g.s_pitch; a.nvalid = g.W;
+    a.S = S; a.pitch = g.s_pitch; a.nvalid = g.W + border_cols;
     a.scale = (float)(1.0 / ((double)g.Lh * (double)g.Lw));
     a.fd = t.pw.desc; a.tw = d.tw_w;
     a.out_map = g.fast_rows.ok ? d.fr_relayout : nullptr;   // store straight in the fast row kernel's order
@@ -243,9 +245,9 @@ inline RowsFwdArgs image_rows_args(const Geometry& g, const Tables& t, const Dev
 }
 
 // the same pass by the specialised kernel (fast_rows_fwd.hpp), when the row length has one
-inline FastRowsFwdArgs fast_rows_fwd_args(const Geometry& g, const DeviceTables& d, c32* S) {
+inline FastRowsFwdArgs fast_rows_fwd_args(const Geometry& g, const DeviceTables& d, c32* S, int border_cols = 0) {
     FastRowsFwdArgs a{};
-    a.S = S; a.pitch = g.s_pitch; a.nvalid = g.W;
+    a.S = S; a.pitch = g.s_pitch; a.nvalid = g.W + border_cols;
     a.scale = (float)(1.0 / ((double)g.Lh * (double)g.Lw));
     a.tw1 = d.fr_tw1; a.tw2 = d.fr_tw2;
     return a;

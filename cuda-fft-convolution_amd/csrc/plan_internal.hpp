@@ -33,6 +33,10 @@ constexpr long FC_NORM_STORE_DEFAULT = 1;
 // default of plan option "pixel_store" (typed image pixels, fftconv_plan_set_images_typed): direct -- the conversion in the column
 // kernel's load (profiles/pixel_format_ab.txt)
 constexpr long FC_PIXEL_STORE_DEFAULT = 1;
+// default of plan option "border_store" (border modes, fftconv_plan_set_border): direct -- the index map in the column kernel's
+// load beat the staged extension beyond the spread of alternating runs at every shape measured (the device-resident set_images
+// step: cfg5's 35.3 against 44.8 us, cfg3's 91.3 against 124.7, cfg1's x 64 32.4 against 44.2; profiles/border_ab.txt)
+constexpr long FC_BORDER_STORE_DEFAULT = 1;
 constexpr long FC_HOST_MIN_KB = 1024;   // default of plan option "host_min_kb" (0 reproduces the threaded path for small maps: tests)
 
 #define HIP_TRY(call)                                                                              \
@@ -292,8 +296,22 @@ struct fftconv_plan {
     // pixel_format: FC_PIXEL_* of the images the plan holds (0 after every other way an image gets in; read with have_image()).
     long opt_pixel_store = FC_PIXEL_STORE_DEFAULT;
     long pixel_format = 0;
-    bool pixel_direct() const { return fast_cols_fwd_px_direct(opt_pixel_store != 0, tiled != nullptr, g.fast_fwd, g.M); }
+    // (a typed image while a border is on is converted into I first and takes the fp32 border route from there: never direct)
+    bool pixel_direct() const { return !border_mode && fast_cols_fwd_px_direct(opt_pixel_store != 0, tiled != nullptr, g.fast_fwd, g.M); }
     DevBuf<float> IT;  // typed pixels on the device: the H2D copy of a typed host image (sized in bytes: floats_for)
+    // Border modes (fftconv_plan_set_border; border.hpp): FC_BORDER_* of what the image is beyond its data (0: zeros, the library
+    // as it always was) and the CONSTANT mode's value.  While a mode is on, the forward pass transforms the image extended to
+    // (H + MAX_KERNEL_H - 1) x (W + MAX_KERNEL_W - 1) and the plan's rectangle is the H x W "same" map (set by the call).
+    // "border_store" 1: the image's forward column kernel maps the indices in its load where it can -- border_direct(): a one-pass
+    // plan whose image column pass is the specialised kernel and has the bordered instantiation; 0, and every plan it cannot serve
+    // (generic / Bluestein column pass, configurations that are not built): STAGED -- a small kernel writes the extended image
+    // into IE and the column pass runs on that.  It only chooses a route: nothing cached depends on it.
+    long border_mode = 0;
+    float border_value = 0.f;
+    long opt_border_store = FC_BORDER_STORE_DEFAULT;
+    bool border_direct() const { return border_mode && fast_cols_fwd_border_direct(opt_border_store != 0, tiled != nullptr, g.fast_fwd, g.M); }
+    int border_cols() const { return border_mode ? g.max_kw - 1 : 0; }
+    DevBuf<float> IE;  // the extended image of the staged border route (its own buffer: I may hold the image the extension reads)
     PinBuf pin_img, pin_k, pin_out;   // pinned host staging of small host arrays (PinBuf above)
     hipEvent_t pin_out_done[2] = {nullptr, nullptr};   // copy into each half of pin_out complete
     long opt_host_pinned = 1;         // 0: small host arrays take the plain copies (A/B, tests)
@@ -377,7 +395,7 @@ struct fftconv_plan {
         pending.clear();
         pool.clear();
         tw_m.release(); tw_w.release(); pairs.release();
-        S.release(); A.release(); Y.release(); K.release(); KF.release(); O.release(); OC.release(); I.release(); IT.release();
+        S.release(); A.release(); Y.release(); K.release(); KF.release(); O.release(); OC.release(); I.release(); IT.release(); IE.release();
         fr_tw1.release(); fr_tw2.release(); fr_map.release();
         fc_tw1.release(); fc_tw2.release(); fc_pairs.release(); fc_rowoff.release(); fc_pair_row_of.release();
         nat_row_of.release(); nat_col_of.release(); NS.release(); queue.release();

@@ -510,6 +510,55 @@ int fftconv_plan_set_output_rect(fftconv_plan *plan, int off_h, int off_w, int o
  * fftconv_plan_import_spectrum / fftconv_plan_mark_spectrum_valid (a spectrum carries no window statistics).
  * The one-shot and two-step entries, fftconv_multi_*, the plan cache and the MEX gateways do not take the option. */
 int fftconv_plan_set_normalisation(fftconv_plan *plan, int mode, int box_h, int box_w);
+
+/* Border modes: what the image is beyond its data.  The library's own border is zero; a caller who wanted another one had to
+ * write a padded copy of every image, plan for the padded size and crop the rim.  Here the border is never materialised: the
+ * loads of the forward column pass map the indices.  An image extended by MAX_KERNEL - 1 samples per dimension is exactly
+ * DATA + MAX_KERNEL - 1 long -- the window every plan already transforms -- so a bordered map costs no larger transform.
+ *     mode                          beyond the data, 1-D, data a b c d
+ *     0 FFTCONV_BORDER_ZERO         the library as it is without this entry (default); every bit unchanged
+ *     1 FFTCONV_BORDER_CONSTANT     v v | a b c d | v v      (`value`, finite; ignored by the other modes)
+ *     2 FFTCONV_BORDER_REPLICATE    a a | a b c d | d d
+ *     3 FFTCONV_BORDER_SYMMETRIC    b a | a b c d | d c      (MATLAB 'symmetric', numpy 'symmetric', OpenCV BORDER_REFLECT)
+ *     4 FFTCONV_BORDER_REFLECT101   c b | a b c d | c b      (numpy 'reflect', OpenCV's default)
+ *     5 FFTCONV_BORDER_CIRCULAR     c d | a b c d | a b      (MATLAB 'circular', numpy 'wrap')
+ * Per dimension X in {H, W}: lead_X = MAX_KERNEL_X / 2 (integer division), trail_X = MAX_KERNEL_X - 1 - lead_X, c_X =
+ * (MAX_KERNEL_X - 1) / 2 (= trail_X).  With Iext the image extended by the mode over all integers, modes 1-5 define every map
+ * as the H x W "same" map anchored on the plan's MAX_KERNEL box:
+ *     map_k[i, j] = sum_f sum_{a < kh, b < kw} Iext_f[i + c_H - a, j + c_W - b] * K_{k,f}[a, b]
+ * -- the centred "same" map for a kernel of exactly MAX_KERNEL_H x MAX_KERNEL_W; a smaller kernel (ragged cells included) sits
+ * at the top-left of the MAX_KERNEL box; "flip_kernels" decides convolution or correlation as ever, inside the kernel's own
+ * kh x kw.  In window coordinates the forward pass transforms E[r, c] = Iext[r - lead_H, c - lead_W] for r < H + MAX_KERNEL_H - 1,
+ * c < W + MAX_KERNEL_W - 1 (zeros beyond, up to the transform length), and the map is rows [MAX_KERNEL_H - 1, MAX_KERNEL_H - 1
+ * + H) of columns [MAX_KERNEL_W - 1, MAX_KERNEL_W - 1 + W) of the window; everything outside that rectangle holds the cyclic
+ * wrap and partial sums and is unspecified.
+ * A mode other than 0 installs exactly that rectangle, as fftconv_plan_set_output_rect(MAX_KERNEL_H - 1, MAX_KERNEL_W - 1, H, W)
+ * does: the plan's stream is synchronised, prepared kernels are forgotten, "rect_direct" and the store form are decided as for
+ * any rectangle.  Afterwards the caller may set any other rectangle inside that one (a region of interest, in window
+ * coordinates).  Mode 0 restores "output_region" 0.  A call that changes mode or value leaves the plan WITHOUT an image (option
+ * "images" reads 0, a convolve fails with FFTCONV_ERR_NO_IMAGE): the spectrum belongs to (image, border).  A call that changes
+ * nothing keeps the image and the rectangle.
+ * Routes.  Direct: on a one-pass plan whose image column pass is the specialised kernel ("specialised_kernels" bit 1) that kernel
+ * maps rows and columns in its load (compares and selects; a CONSTANT sample outside the data is not loaded).  Staged: everywhere
+ * else (generic and Bluestein / exact_window column passes, kernel_path 1) and with option "border_store" 0 one small kernel
+ * writes the extended image into the plan's staging and the column pass runs on that.  Both routes return the same bits.
+ * Image batches compose (B * F planes).  A typed image (fftconv_plan_set_images_typed) is converted into the fp32 staging first
+ * and takes the border route from there ("pixel_direct" reads 0 meanwhile).  "defer_prepare" merges a recorded preparation with
+ * the column pass of zero-border images only: a bordered image launches the pending kernels' column pass by itself first.  A
+ * warm device-resident call allocates nothing, never synchronises and can be captured into a graph.
+ * plan_info.workspace_bytes counts the staging of the extended image.
+ * Options: "border_store" (1 (default): direct where possible; 0: always staged -- takes effect at the next image), read-only
+ * "border_direct" (1 if the next image on this plan, with the options as they are, is mapped in the column kernel's load),
+ * "border_mode", "border_lead_h", "border_lead_w" (lead_X while a border is on, else 0).
+ * Folds are single.  FFTCONV_ERR_INVALID_ARG, the plan's state untouched: a mode outside 0..5; a value that is not finite; modes
+ * 3 and 5 where MAX_KERNEL_X / 2 > DATA_X; mode 4 where MAX_KERNEL_X / 2 > DATA_X - 1; a block-wise plan ("blockwise" > 0); a plan
+ * with normalisation on -- likewise fftconv_plan_set_normalisation(1, ...) while a border is on (the window statistics assume
+ * zero padding) -- and fftconv_plan_import_spectrum / fftconv_plan_mark_spectrum_valid while a border is on (a foreign spectrum
+ * carries no border).
+ * The one-shot and two-step entries, fftconv_multi_*, the plan cache and the MEX gateways do not take the option. */
+enum { FFTCONV_BORDER_ZERO = 0, FFTCONV_BORDER_CONSTANT = 1, FFTCONV_BORDER_REPLICATE = 2, FFTCONV_BORDER_SYMMETRIC = 3,
+       FFTCONV_BORDER_REFLECT101 = 4, FFTCONV_BORDER_CIRCULAR = 5 };
+int fftconv_plan_set_border(fftconv_plan *plan, int mode, float value);
 /* Current value of an option, plus read-only ones: "tuned_candidates" (allocations tried by the last placement tuning)
  * and "tuned_best" (index of the one kept), "blockwise" (blocks of a block-wise plan, 0 = one pass), "overlap_save" (1: the blocks are stored by the output kernel),
  * "rows_slots_per_cu" (workgroups of the multi-map row kernel a CU holds at once: what the walk length is chosen for),
