@@ -36,6 +36,10 @@ namespace {
 std::mutex g_live_mutex;
 std::set<const fftconv_plan*> g_live_plans;
 
+}  // namespace
+
+namespace fc {
+
 int cols_threads(const Geometry& g) {
     long work = (long)g.T_cols * g.work_m;   // (work lengths: a Bluestein direction runs on its longer work transform)
     if (work >= 4096) return 512;
@@ -48,10 +52,6 @@ int rows_threads(const Geometry& g) {
     if (g.work_w >= 512) return 128;
     return 64;
 }
-
-}  // namespace
-
-namespace fc {
 
 int use_device(const fftconv_plan* p) {
     HIP_TRY(hipSetDevice(p->gpu_id));
@@ -140,8 +140,7 @@ int launch_kernel_cols(fftconv_plan* p, const float* dk, int a0, int na, int kh,
     }
     if (int rc = p->prof_begin(PK_KERNEL_COLS, na)) return rc;
     if (g.fast_fwd) {
-        FastColsFwdArgs fa = fast_cols_fwd_args(g, p->d, dk + (size_t)a0 * g.F * kh * kw, (size_t)kh * kw, kh, kh, kw, na * g.F,
-                                                p->A.p, (size_t)g.rows * a_pitch_for(kw), a_pitch_for(kw), true);
+        FastColsFwdArgs fa = kernels_fwd_args(g, p->d, dk + (size_t)a0 * g.F * kh * kw, kh, kw, na * g.F, p->A.p);
         HIP_TRY(launch_fast_cols_fwd(g.M, g.fast_cols.T, fast_cols_fwd_pruned_ok(g.fast_cols, kh), fa, p->num_cus, p->stream));
     } else {
         ColsR2CArgs ka = kernel_cols_args(g, p->t, p->d, dk + (size_t)a0 * g.F * kh * kw, kh, kw, p->A.p);
@@ -150,6 +149,9 @@ int launch_kernel_cols(fftconv_plan* p, const float* dk, int a0, int na, int kh,
     return p->prof_end();
 }
 
+}  // namespace
+
+namespace fc {
 // the deferred kernel-column pass of fftconv_plan_prepare_kernels_packed, on its own (no set_image came first)
 int flush_pending_prepare(fftconv_plan* p) {
     ColumnCache::Request pd;
@@ -161,6 +163,9 @@ int flush_pending_prepare(fftconv_plan* p) {
     if (!rc) p->a_holds.ready(pd);
     return rc;
 }
+}  // namespace fc
+
+namespace {
 
 // How the maps of a group leave the device: decided once per group (plan_delivery), read by every step of the loop.
 enum class Route {
@@ -731,302 +736,6 @@ int fftconv_plan_get_info(const fftconv_plan* plan, fftconv_plan_info* info) {
         if (fftconv_plan_get_info(ts->sub, &si) == 0)
             info->workspace_bytes = si.workspace_bytes + ts->big.bytes() + ts->tmp.bytes() + ts->blk.bytes() + ts->crop.bytes() + (ts->specs_x ? 0 : ts->specs.bytes());
     }
-    return 0;
-}
-
-// Zero-pad + forward transform of nimg images back to back at `data` ([b][f][w][h]): ONE forward pass over nimg * F planes -- the
-// spectra land [b][f][row][s_pitch] in the spectrum buffer, so the column and row kernels run as for one image with more planes
-// and rows, and the launch count is that of one image.
-// fmt: FFTCONV_PIXEL_* of the elements at `vdata` (fftconv_plan_set_images_typed; pixel_format.hpp).  F32 is the call as it always was.
-// A typed image takes one of two routes, decided here once (fftconv_plan::pixel_direct): DIRECT -- the specialised column kernel
-// converts in its load, and the window statistics read the typed elements too: no fp32 image exists; STAGED -- a small kernel
-// writes the fp32 image into I (after the H2D copy of a typed host image: the bytes that cross are the typed ones) and the call
-// goes on as an fp32 one from the device.
-static int set_images_impl(fftconv_plan* plan, const void* vdata, int fmt, int nimg, int location) {
-    if (nimg < 1) return api_fail(FFTCONV_ERR_INVALID_ARG, "n_images must be at least 1 (got %d)", nimg);
-    if (!plan || !vdata) return api_fail(FFTCONV_ERR_INVALID_ARG, "Invalid data input");
-    if (!fc_pixel_format_ok(fmt))
-        return api_fail(FFTCONV_ERR_INVALID_ARG, "pixel_format is 0 (fp32), 1 (uint8), 2 (uint16), 3 (fp16) or 4 (bfloat16), got %d", fmt);
-    if (location != FFTCONV_HOST && location != FFTCONV_DEVICE) return api_fail(FFTCONV_ERR_INVALID_ARG, "bad location");
-    fftconv_plan* p = plan;
-    const Geometry& g = p->g;
-    if (p->tiled && nimg > 1)
-        return api_fail(FFTCONV_ERR_INVALID_ARG, "a block-wise plan (%d blocks) holds one image: its block spectra are kept per image; "
-                        "call fftconv_plan_set_image per image, or create a one-pass plan (fftconv_plan_options.blockwise = 1)", p->tiled->nblk);
-    if (!p->tiled && p->Sx && p->Sx_bytes < (size_t)nimg * g.spectrum_elems() * sizeof(c32))
-        return api_fail(FFTCONV_ERR_INVALID_ARG, "the caller's spectrum buffer (fftconv_plan_use_spectrum_buffer) holds %zu bytes, %d images need %zu",
-                        p->Sx_bytes, nimg, (size_t)nimg * g.spectrum_elems() * sizeof(c32));
-    if (int rc = use_device(p)) return rc;
-    const bool typed = fmt != FC_PIXEL_F32;
-    const size_t eb = fc_pixel_elem_bytes(fmt);
-    if (p->tiled) {
-        if (!typed) {
-            const int rc = tiled_set_image(p, static_cast<const float*>(vdata), location);
-            if (!rc) p->pixel_format = FC_PIXEL_F32;
-            return rc;
-        }
-        // block-wise: the fp32 image on the device first (typed host pixels after their H2D copy), then the blocks as from a device image
-        const TiledState* ts = p->tiled;
-        const hipStream_t st = ts->sub->stream;
-        const size_t n = (size_t)ts->H * ts->W * ts->F;
-        const void* dtyped = vdata;
-        if (int rc = p->I.ensure(n)) return rc;
-        if (location == FFTCONV_HOST) {
-            if (int rc = p->IT.ensure(floats_for(n, eb))) return rc;
-            HIP_TRY(hipMemcpyAsync(p->IT.p, vdata, n * eb, hipMemcpyHostToDevice, st));
-            dtyped = p->IT.p;
-        }
-        FC_VERBOSE(p, "typed pixels (format %d): staged -- %zu elements converted into the fp32 image staging (block-wise plan)", fmt, n);
-        p->tiled->have_image = false;
-        HIP_TRY(launch_pixels_to_f32(dtyped, fmt, p->I.p, n, st));
-        if (location == FFTCONV_HOST) HIP_TRY(hipStreamSynchronize(st));      // the caller's array has been consumed
-        const int rc = tiled_set_image(p, p->I.p, FFTCONV_DEVICE);
-        if (!rc) p->pixel_format = fmt;
-        return rc;
-    }
-    const int planes = nimg * g.F;
-    const bool direct = typed && p->pixel_direct();
-    // A border (fftconv_plan_set_border; border.hpp): the forward pass transforms the image extended to eh x ew samples a plane, one
-    // of two routes, decided here once (fftconv_plan::border_direct): DIRECT -- the specialised column kernel maps the indices in
-    // its load; STAGED -- a small kernel writes the extended image into IE and the column pass runs on that.  A typed image is
-    // converted into I first (pixel_direct() reads 0 meanwhile) and goes on as an fp32 one from the device.
-    const bool border = p->border_mode != 0, bdirect = border && p->border_direct();
-    const int eh = g.H + g.max_kh - 1, ew = g.W + g.max_kw - 1;
-    const void* dimg_any = vdata;   // what the column pass reads: elements of `fmt` on the direct route and for fp32, else (staged) see below
-    bool image_pinned = false;      // the caller's array has been consumed by the CPU: no wait for the GPU at the end
-    const size_t n = (size_t)g.H * g.W * planes;      // (the pinned staging takes a whole batch of at most 1 MiB)
-    if (location == FFTCONV_HOST) {
-        // (typed pixels: the limits are compared against the typed bytes -- four times the uint8 pixels fit; the staged route
-        //  converts on the device, so its copy always lands in IT)
-        DevBuf<float>& dev = typed ? p->IT : p->I;
-        if (p->opt_host_pinned && n * eb <= FC_PIN_IMAGE_BYTES) {
-            if (int rc = p->pin_img.ensure(n * eb)) return rc;
-            if (int rc = p->pin_img.wait()) return rc;
-            memcpy(p->pin_img.p, vdata, n * eb);
-            image_pinned = true;
-            if (n * eb <= FC_PIN_INPLACE_BYTES && (!typed || direct)) {
-                dimg_any = p->pin_img.p;      // the column pass reads it in place
-            } else {
-                if (int rc = dev.ensure(floats_for(n, eb))) return rc;
-                HIP_TRY(hipMemcpyAsync(dev.p, p->pin_img.p, n * eb, hipMemcpyHostToDevice, p->stream));
-                dimg_any = dev.p;
-            }
-        } else {
-            if (int rc = dev.ensure(floats_for(n, eb))) return rc;
-            HIP_TRY(hipMemcpyAsync(dev.p, vdata, n * eb, hipMemcpyHostToDevice, p->stream));
-            dimg_any = dev.p;
-        }
-    }
-    if (typed && !direct)
-        if (int rc = p->I.ensure(n)) return rc;
-    if (border && !bdirect)
-        if (int rc = p->IE.ensure((size_t)eh * ew * planes)) return rc;
-    FC_VERBOSE(p, "Using GPU : %d", p->gpu_id);                                                    // src/cudaConvolutionFFT.cu:87
-    FC_VERBOSE(p, "Data size: h=%d, w=%d, f=%d", g.H, g.W, g.F);                                   // :100
-    if (nimg > 1) FC_VERBOSE(p, "Images: %d (one forward pass over %d planes)", nimg, planes);
-    char chirp[96] = "";          // windows that do not factor into the radices: Bluestein transforms on longer work lengths
-    if (g.bluestein_h() || g.bluestein_w()) {
-        char hs[32] = "", ws[32] = "";
-        if (g.bluestein_h()) snprintf(hs, sizeof(hs), " h %d via %d", g.M, g.work_m);
-        if (g.bluestein_w()) snprintf(ws, sizeof(ws), " w %d via %d", g.Lw, g.work_w);
-        snprintf(chirp, sizeof(chirp), ", chirp-z passes:%s%s%s", hs, (hs[0] && ws[0]) ? "," : "", ws);
-    }
-    FC_VERBOSE(p, "FFT size: h=%d, w=%d (internal transform %d x %d, %s column pass, %s row pass, %s intermediate%s)", g.fft_h, g.fft_w, g.Lh, g.Lw,   // :114
-               g.fast_fwd ? "specialised" : "generic", g.fast_rows.ok ? "specialised" : "generic", g.y_tiled() ? "tiled" : "row-major", chirp);
-    // (with the fast row kernel the w-pass stores the spectrum directly in that kernel's register order)
-    p->n_images = 0;      // (until the new spectra are queued: a larger batch reallocates the plan's own buffer)
-    p->pixel_format = FC_PIXEL_F32;
-    if (int rc = p->ensure_spectrum(nimg)) return rc;
-    if (p->opt_normalise) {
-        if (int rc = p->ND.ensure(g.map_elems() * (size_t)nimg)) return rc;
-        if (int rc = p->NS64.ensure((size_t)2 * g.F * ncc_strip_columns(g.fft_h, g.fft_w, g.F, (int)p->norm_box_w, FC_NCC_SCRATCH_BYTES) * g.fft_h)) return rc;
-    }
-    c32* sgen = p->spec();
-    // (the merged image + kernels launch is fp32-only and zero-border only: a typed image on the direct route and an image with a
-    //  border launch a pending kernels' column pass by itself)
-    if ((direct || border) ? p->a_holds.pending() : p->a_holds.pending_off_stream(p->stream))
-        if (int rc = flush_pending_prepare(p)) return rc;
-    int sfmt = fmt;                 // the format of what the column pass and the statistics read at dimg_any
-    if (int rc = p->prof_begin(PK_IMAGE_COLS, planes)) return rc;      // (the staged conversion counts as part of the image's column pass)
-    if (typed && !direct) {
-        FC_VERBOSE(p, "typed pixels (format %d): staged -- %zu elements converted into the fp32 image staging", fmt, n);
-        HIP_TRY(launch_pixels_to_f32(dimg_any, fmt, p->I.p, n, p->stream));
-        dimg_any = p->I.p;
-        sfmt = FC_PIXEL_F32;
-    }
-    const float* dimg = static_cast<const float*>(dimg_any);      // (direct route: opaque -- elements of sfmt)
-    if (border) {
-        const BorderLoad bd = border_load((int)p->border_mode, p->border_value, g.H, g.W, g.max_kh, g.max_kw);
-        if (bdirect) {      // the data as it lies; the counts are the extension's
-            FastColsFwdArgs fa = fast_cols_fwd_args(g, p->d, dimg, (size_t)g.H * g.W, g.H, eh, ew, planes, sgen, (size_t)g.rows * g.s_pitch, g.s_pitch, false);
-            FC_VERBOSE(p, "border (mode %ld): direct -- mapped in the column kernel's load", p->border_mode);
-            HIP_TRY(launch_fast_cols_fwd_border(g.M, g.fast_cols.T, fa, bd, p->num_cus, p->stream));
-        } else {
-            FC_VERBOSE(p, "border (mode %ld): staged -- %zu elements extended into the fp32 image staging", p->border_mode, (size_t)eh * ew * planes);
-            HIP_TRY(launch_extend_image(dimg, p->IE.p, g.H, g.W, eh, ew, (size_t)planes, bd, p->stream));
-            if (g.fast_fwd) {
-                FastColsFwdArgs fa = fast_cols_fwd_args(g, p->d, p->IE.p, (size_t)eh * ew, eh, eh, ew, planes, sgen, (size_t)g.rows * g.s_pitch, g.s_pitch, false);
-                HIP_TRY(launch_fast_cols_fwd(g.M, g.fast_cols.T, false, fa, p->num_cus, p->stream));
-            } else {
-                ColsR2CArgs ia = image_cols_args(g, p->t, p->d, p->IE.p, sgen);
-                ia.in_plane_stride = (size_t)eh * ew; ia.in_col_pitch = eh; ia.h_in = eh; ia.ncols = ew;
-                HIP_TRY(launch_cols_r2c(ia, tiles_for(ew, g.T_cols), planes, cols_threads(g), p->cols_lds(), p->stream));
-            }
-        }
-    } else if (direct) {
-        FastColsFwdArgs fa = fast_cols_fwd_args(g, p->d, dimg, (size_t)g.H * g.W, g.H, g.H, g.W, planes, sgen,
-                                                (size_t)g.rows * g.s_pitch, g.s_pitch, false);
-        const PixelLoad px = fast_cols_fwd_pixel_load(fa, fmt);
-        FC_VERBOSE(p, "typed pixels (format %d): direct -- converted in the column kernel's load, %s loads", fmt, px.wide ? "pair" : "element");
-        HIP_TRY(launch_fast_cols_fwd_px(g.M, g.fast_cols.T, fa, px, p->num_cus, p->stream));
-    } else if (g.fast_fwd) {
-        FastColsFwdArgs fa = fast_cols_fwd_args(g, p->d, dimg, (size_t)g.H * g.W, g.H, g.H, g.W, planes, sgen,
-                                                (size_t)g.rows * g.s_pitch, g.s_pitch, false);
-        ColumnCache::Request pd;
-        if (p->a_holds.take_pending(pd)) {
-            // the deferred kernel-column pass of fftconv_plan_prepare_kernels_packed and the image's column pass: ONE launch
-            FastColsFwdArgs fk = fast_cols_fwd_args(g, p->d, p->opt_normalise ? p->KN.p : pd.dk, (size_t)pd.kh * pd.kw, pd.kh, pd.kh, pd.kw, pd.na * g.F, p->A.p,
-                                                    (size_t)g.rows * a_pitch_for(pd.kw), a_pitch_for(pd.kw), true);
-            FC_VERBOSE(p, "image columns (%d tiles) and the columns of %d kernels (%d tiles) in one launch", fa.ntiles, pd.na, fk.ntiles);
-            HIP_TRY(launch_fast_cols_fwd_pair(g.M, g.fast_cols.T, fa, fk, fast_cols_fwd_pruned_ok(g.fast_cols, pd.kh), p->num_cus, p->stream));
-            p->a_holds.ready(pd);     // (pd.stream is p->stream: a request on another stream was flushed above)
-        } else
-            HIP_TRY(launch_fast_cols_fwd(g.M, g.fast_cols.T, false, fa, p->num_cus, p->stream));
-    } else {
-        ColsR2CArgs ia = image_cols_args(g, p->t, p->d, dimg, sgen);
-        HIP_TRY(launch_cols_r2c(ia, tiles_for(g.W, g.T_cols), planes, cols_threads(g), p->cols_lds(), p->stream));
-    }
-    if (int rc = p->prof_end()) return rc;
-    if (p->opt_normalise) {      // window statistics (ncc.hpp), while the pixels are still there: D of every image, in strips of columns
-        const int strip = ncc_strip_columns(g.fft_h, g.fft_w, g.F, (int)p->norm_box_w, FC_NCC_SCRATCH_BYTES);
-        FC_VERBOSE(p, "window statistics: box %ld x %ld, %d images, strips of %d columns (%zu bytes of float64 scratch)", p->norm_box_h, p->norm_box_w,
-                   nimg, strip, (size_t)2 * g.F * strip * g.fft_h * sizeof(double));
-        const size_t seb = fc_pixel_elem_bytes(sfmt);
-        for (int b = 0; b < nimg; b++)
-            HIP_TRY(launch_ncc_statistics_typed(static_cast<const char*>(dimg_any) + (size_t)b * g.F * g.H * g.W * seb, sfmt, g.H, g.W, g.F, g.fft_h, g.fft_w,
-                                                (int)p->norm_box_h, (int)p->norm_box_w, p->NS64.p, strip, p->ND.p + (size_t)b * g.map_elems(), p->stream));
-    }
-    if (image_pinned)
-        if (int rc = p->pin_img.mark(p->stream)) return rc;      // the column pass, the copy or the statistics: the last reader
-    if (int rc = p->prof_begin(PK_IMAGE_ROWS, planes)) return rc;
-    if (g.fast_rows.ok) {
-        HIP_TRY(launch_fast_rows_fwd(g.Lw, fast_rows_fwd_args(g, p->d, sgen, p->border_cols()), planes * g.rows, p->stream));
-    } else {
-        RowsFwdArgs ra = image_rows_args(g, p->t, p->d, sgen, p->border_cols());
-        HIP_TRY(launch_rows_fwd(ra, planes * g.rows, rows_threads(g), g.rows_fwd_lds_bytes(), p->stream));
-    }
-    if (int rc = p->prof_end()) return rc;
-    if (location == FFTCONV_HOST && !image_pinned) HIP_TRY(hipStreamSynchronize(p->stream));
-    p->n_images = nimg;
-    p->pixel_format = fmt;
-    return 0;
-}
-
-int fftconv_plan_set_image(fftconv_plan* plan, const float* data, int location) { return set_images_impl(plan, data, FC_PIXEL_F32, 1, location); }
-int fftconv_plan_set_images(fftconv_plan* plan, const float* data, int n_images, int location) {
-    return set_images_impl(plan, data, FC_PIXEL_F32, n_images, location);
-}
-int fftconv_plan_set_images_typed(fftconv_plan* plan, const void* data, int pixel_format, int n_images, int location) {
-    return set_images_impl(plan, data, pixel_format, n_images, location);
-}
-
-int fftconv_plan_spectrum(fftconv_plan* plan, void** device_ptr, size_t* bytes) {
-    if (!plan) return api_fail(FFTCONV_ERR_INVALID_ARG, "plan is NULL");
-    if (int rc = use_device(plan)) return rc;
-    if (TiledState* ts = plan->tiled) {          // every block's spectrum, one after the other
-        if (!ts->specs_x)
-            if (int rc = ts->specs.ensure(ts->spec_total())) return rc;
-        if (device_ptr) *device_ptr = ts->spec_base();
-        if (bytes) *bytes = ts->spec_total() * sizeof(c32);
-        return 0;
-    }
-    // (a plan holding B images: the whole buffer, image b at b * plan_info.spectrum_bytes)
-    if (int rc = plan->ensure_spectrum()) return rc;
-    if (device_ptr) *device_ptr = plan->spec();
-    if (bytes) *bytes = plan->g.spectrum_elems() * sizeof(c32) * (size_t)plan->images_held();
-    return 0;
-}
-
-static int spectrum_exchange(fftconv_plan* p, float* spectrum, int location, bool to_natural) {
-    if (!p || !spectrum) return api_fail(FFTCONV_ERR_INVALID_ARG, "NULL argument");
-    if (!to_natural && p->opt_normalise)
-        return api_fail(FFTCONV_ERR_INVALID_ARG, "normalisation is on (fftconv_plan_set_normalisation): an imported spectrum carries no window statistics");
-    if (!to_natural && p->border_mode)
-        return api_fail(FFTCONV_ERR_INVALID_ARG, "a border is on (fftconv_plan_set_border, mode %ld): an imported spectrum carries no border", p->border_mode);
-    if (location != FFTCONV_HOST && location != FFTCONV_DEVICE) return api_fail(FFTCONV_ERR_INVALID_ARG, "bad location");
-    if (p->tiled) return tiled_unsupported("the spectrum in the reference's order");
-    const Geometry& g = p->g;
-    if (!g.exact_window)
-        return api_fail(FFTCONV_ERR_UNSUPPORTED_SIZE,
-                    "this plan transforms %dx%d, not the %dx%d window: create it with fftconv_plan_options.exact_window = 1 to exchange "
-                    "spectra in the reference's order", g.Lh, g.Lw, g.fft_h, g.fft_w);
-    if (p->n_images > 1)
-        return api_fail(FFTCONV_ERR_INVALID_ARG, "the plan holds %d images (fftconv_plan_set_images): the spectrum in the reference's order is "
-                        "exchanged for one image -- call fftconv_plan_set_image first", p->n_images);
-    if (to_natural && !p->have_image()) return api_fail(FFTCONV_ERR_NO_IMAGE, "no image spectrum: call fftconv_plan_set_image first");
-    if (int rc = use_device(p)) return rc;
-    if (int rc = p->ensure_spectrum()) return rc;
-    if (!p->nat_col_of.p) {     // (the second of the two: both are there, or both are uploaded again)
-        if (int rc = upload(p->nat_row_of, p->t.nat_row_of)) return rc;
-        if (int rc = upload(p->nat_col_of, p->t.nat_col_of)) return rc;
-    }
-    const size_t n = (size_t)g.F * g.fft_w * g.rows;
-    c32* nat = reinterpret_cast<c32*>(spectrum);
-    if (location == FFTCONV_HOST) {
-        if (int rc = p->NS.ensure(n)) return rc;
-        nat = p->NS.p;
-        if (!to_natural) HIP_TRY(hipMemcpyAsync(nat, spectrum, n * sizeof(c32), hipMemcpyHostToDevice, p->stream));
-    }
-    // the folded 1/(Lh*Lw) of src/cudaConvolutionFFT.cu:270 comes off on the way out and goes on on the way in
-    const double norm = (double)g.Lh * (double)g.Lw;
-    HIP_TRY(launch_spectrum_reorder(to_natural, p->spec(), (size_t)g.rows * g.s_pitch, g.s_pitch, nat, g.fft_w, g.rows, g.F,
-                                    p->nat_row_of.p, p->nat_col_of.p, (float)(to_natural ? norm : 1.0 / norm), p->stream));
-    if (location == FFTCONV_HOST) {
-        if (to_natural) HIP_TRY(hipMemcpyAsync(spectrum, nat, n * sizeof(c32), hipMemcpyDeviceToHost, p->stream));
-        HIP_TRY(hipStreamSynchronize(p->stream));
-    }
-    if (!to_natural) { p->n_images = 1; p->pixel_format = FC_PIXEL_F32; }
-    return 0;
-}
-
-int fftconv_plan_export_spectrum(fftconv_plan* plan, float* spectrum, int location) { return spectrum_exchange(plan, spectrum, location, true); }
-int fftconv_plan_import_spectrum(fftconv_plan* plan, const float* spectrum, int location) {
-    return spectrum_exchange(plan, const_cast<float*>(spectrum), location, false);
-}
-
-int fftconv_plan_use_spectrum_buffer(fftconv_plan* plan, void* device_ptr, size_t bytes) {
-    if (!plan) return api_fail(FFTCONV_ERR_INVALID_ARG, "plan is NULL");
-    const size_t need = (plan->tiled ? plan->tiled->spec_total() : plan->g.spectrum_elems()) * sizeof(c32);
-    if (device_ptr) {
-        if (bytes < need || (reinterpret_cast<uintptr_t>(device_ptr) & 15))
-            return api_fail(FFTCONV_ERR_INVALID_ARG, "spectrum buffer too small (%zu < %zu bytes) or not 16-byte aligned", bytes, need);
-    }
-    if (plan->tiled) {
-        plan->tiled->specs_x = reinterpret_cast<c32*>(device_ptr);
-        plan->tiled->have_image = false;
-        return 0;
-    }
-    // (need: one image; fftconv_plan_set_images checks the size again for its batch)
-    plan->Sx = reinterpret_cast<c32*>(device_ptr);
-    plan->Sx_bytes = device_ptr ? bytes : 0;
-    plan->n_images = 0;
-    return 0;
-}
-
-int fftconv_plan_mark_spectrum_valid(fftconv_plan* plan) {
-    if (!plan) return api_fail(FFTCONV_ERR_INVALID_ARG, "plan is NULL");
-    if (plan->opt_normalise)
-        return api_fail(FFTCONV_ERR_INVALID_ARG, "normalisation is on (fftconv_plan_set_normalisation): a spectrum written by the caller carries no window statistics");
-    if (plan->border_mode)
-        return api_fail(FFTCONV_ERR_INVALID_ARG, "a border is on (fftconv_plan_set_border, mode %ld): a spectrum written by the caller carries no border", plan->border_mode);
-    if (plan->tiled) {
-        if (!plan->tiled->spec_base()) return api_fail(FFTCONV_ERR_NO_IMAGE, "the plan has no spectrum buffer yet (fftconv_plan_spectrum / fftconv_plan_use_spectrum_buffer)");
-        if (!plan->tiled->have_image) plan->pixel_format = FC_PIXEL_F32;
-        plan->tiled->have_image = true;
-        return 0;
-    }
-    if (!plan->spec()) return api_fail(FFTCONV_ERR_NO_IMAGE, "the plan has no spectrum buffer yet (fftconv_plan_spectrum / fftconv_plan_use_spectrum_buffer)");
-    if (plan->n_images < 1) { plan->n_images = 1; plan->pixel_format = FC_PIXEL_F32; }
     return 0;
 }
 

@@ -1,5 +1,5 @@
 // pipeline.hpp -- geometry of one plan and the argument blocks of its kernels.
-// Host-only, shared by the product library (fftconv_api.cpp) and the test-only emulator so
+// Host-only, shared by the product library (fftconv_api.cpp, plan_image.cpp) and the test-only emulator so
 // that both drive the workgroup bodies with identical arguments.
 #pragma once
 #include <algorithm>
@@ -223,10 +223,12 @@ struct DeviceTables {
 };
 
 // image columns: planes = F, columns = W, valid samples = H
+// (h_ext x w_ext: the dense planes at `image` are the extended image of the staged border route instead; 0 = the data's H x W)
 inline ColsR2CArgs image_cols_args(const Geometry& g, const Tables& t, const DeviceTables& d,
-                                   const float* image, c32* S) {
+                                   const float* image, c32* S, int h_ext = 0, int w_ext = 0) {
     ColsR2CArgs a{};
-    a.in = image; a.in_plane_stride = (size_t)g.H * g.W; a.in_col_pitch = g.H; a.h_in = g.H; a.ncols = g.W;
+    const int h = h_ext > 0 ? h_ext : g.H, w = w_ext > 0 ? w_ext : g.W;
+    a.in = image; a.in_plane_stride = (size_t)h * w; a.in_col_pitch = h; a.h_in = h; a.ncols = w;
     a.out = S; a.out_plane_stride = (size_t)g.rows * g.s_pitch; a.out_pitch = g.s_pitch;
     a.M = g.M; a.T = g.T_cols; a.lds_pitch = g.lds_pitch;
     a.fd = t.pm.desc; a.tw = d.tw_m; a.pairs = d.pairs; a.npairs = (int)t.pairs.size();
@@ -326,6 +328,17 @@ inline FastColsFwdArgs fast_cols_fwd_args(const Geometry& g, const DeviceTables&
     // that holds CUs: static deal unless "dynamic_tiles" = 2 asks for the queue (A/B, tests).
     a.queue = (d.queue && d.queue_fwd) ? d.queue + (of_kernels ? 9 : 8) * FC_QUEUE_STRIDE : nullptr;
     return a;
+}
+// the two passes a plan launches, in the long form's terms.  The image's: `planes` dense planes of h_data x w_data samples at `in`,
+// transformed as w_count columns of h_count samples -- the data's own counts, or the extension's where a border is mapped in the
+// load (the data then as it lies) -- into the spectrum layout at S
+inline FastColsFwdArgs image_fwd_args(const Geometry& g, const DeviceTables& d, const float* in, int h_data, int w_data, int h_count,
+                                      int w_count, int planes, c32* S) {
+    return fast_cols_fwd_args(g, d, in, (size_t)h_data * w_data, h_data, h_count, w_count, planes, S, (size_t)g.rows * g.s_pitch, g.s_pitch, false);
+}
+// ... and the kernels': `planes` packed kh x kw planes at dk into the column-spectrum layout at A
+inline FastColsFwdArgs kernels_fwd_args(const Geometry& g, const DeviceTables& d, const float* dk, int kh, int kw, int planes, c32* A) {
+    return fast_cols_fwd_args(g, d, dk, (size_t)kh * kw, kh, kh, kw, planes, A, (size_t)g.rows * a_pitch_for(kw), a_pitch_for(kw), true);
 }
 
 // Image batches: the image coordinate of a spectral-row launch (FastRowsArgs / SpectralRowsArgs) -- `images` spectra from a.S on,

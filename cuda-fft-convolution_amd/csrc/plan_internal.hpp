@@ -1,9 +1,12 @@
 // plan_internal.hpp -- what the host translation units of libfftconv.so share (not installed): the plan object behind
 // include/fftconv.h, its device / pinned buffers, and the internal entry points each unit offers the others.
 //   column_cache.hpp   what the column-spectrum buffer A holds between calls (KernelSet, ColumnCache): the one owner of that record
-//   fftconv_api.cpp    plan core: creation (plan_device_setup), image transform, the per-kernel loop (run_group: plan_delivery,
+//   image_route.hpp    the way of an image into a one-pass plan, decided once per call (ImageRoute, plan_image_route)
+//   fftconv_api.cpp    plan core: creation (plan_device_setup), the per-kernel loop (run_group: plan_delivery,
 //                      launch_spectral_rows_batch, launch_output_cols, deliver_batch), kernel preparation (prepare_kernels),
 //                      options (kLongOptions), two-step pair
+//   plan_image.cpp     image side of the plan core: set_image / set_images / set_images_typed as a sequence of stages that read the
+//                      ImageRoute, the spectrum buffer and the spectrum exchange in the reference's order
 //   plan_cache.cpp     plan cache of the one-shot entries + fftconv_convolution_fft[_ex] (the MEX body)
 //   host_ring.cpp      host-output streaming (copy threads, pinned ring, the two staging buffers of a streamed group)
 //   blockwise.cpp      block-wise plans (overlap-save / overlap-add) and their planner
@@ -23,6 +26,7 @@
 #include "../../include/fftconv.h"
 #include "api_internal.hpp"
 #include "column_cache.hpp"
+#include "image_route.hpp"
 #include "kernels.hpp"
 #include "ncc.hpp"
 #include "pipeline.hpp"
@@ -153,10 +157,8 @@ int upload(DevBuf<T>& buf, const std::vector<T>& v, const T** slot = nullptr) {
 // and the reference's entry makes one per kernel and one per map (src/cudaConvolutionFFT.cu:148,231,286).  Here the
 // CPU copies the caller's small arrays into / out of pinned buffers of the plan: an image or a kernel set of at most
 // FC_PIN_INPLACE_BYTES is then read by the column kernels IN PLACE over PCIe (no copy command at all), a larger one
-// (up to FC_PIN_IMAGE_BYTES) crosses in one asynchronous copy, and the maps of a launch come back in ONE copy.
-// `busy` is recorded behind the last GPU work that reads the buffer; the next fill waits for it.
-constexpr size_t FC_PIN_INPLACE_BYTES = (size_t)512 << 10;
-constexpr size_t FC_PIN_IMAGE_BYTES = (size_t)1 << 20;
+// (up to FC_PIN_IMAGE_BYTES) crosses in one asynchronous copy (both limits: image_route.hpp), and the maps of a launch come back
+// in ONE copy.  `busy` is recorded behind the last GPU work that reads the buffer; the next fill waits for it.
 constexpr size_t FC_PIN_OUT_BYTES = (size_t)8 << 20;
 constexpr size_t FC_PIN_ONE_MAP_BYTES = (size_t)64 << 10;
 struct PinBuf {
@@ -441,6 +443,11 @@ int use_device(const fftconv_plan* p);
 BatchSizes batch_sizes(const fftconv_plan* p, int n, int kw);
 int check_kernel_size(const fftconv_plan* p, int kh, int kw);
 int check_thread_size(const double* thread_size, int n_thread_size);
+// threads per workgroup of the generic column / row kernels
+int cols_threads(const Geometry& g);
+int rows_threads(const Geometry& g);
+// the deferred kernel-column pass of fftconv_plan_prepare_kernels_packed, launched by itself on the stream it was recorded for
+int flush_pending_prepare(fftconv_plan* p);
 // the plan's "output_region" of nmaps full-window maps at src, compacted into dst: 4 pads to the pow2 window, the others crop
 // scale: normalised maps -- the scale planes D of the plan's images; map m of the launch belongs to image image0 + m / per_image
 int launch_region(const fftconv_plan* p, const float* src, float* dst, int nmaps, hipStream_t s, const float* scale = nullptr, int image0 = 0,

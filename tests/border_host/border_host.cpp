@@ -238,7 +238,7 @@ int cmd_spectrum(int argc, char** argv) {
     std::vector<c32> lds(FC_LDS_BUDGET / sizeof(c32));
     const int eh = H + mkh - 1, ew = W + mkw - 1;
     const BorderLoad bd = border_load(mode, value, H, W, mkh, mkw);
-    const FastColsFwdArgs fa = fast_cols_fwd_args(g, s.d, img.data(), (size_t)H * W, H, eh, ew, F, S.data(), (size_t)g.rows * g.s_pitch, g.s_pitch, false);
+    const FastColsFwdArgs fa = image_fwd_args(g, s.d, img.data(), H, W, eh, ew, F, S.data());
     for (int wg = 0; wg < 3; wg++) {
         for (int i = 0; i < C16::LDS_ELEMS; i++) lds[i] = mk(1e30f, -1e30f);
         HostPhaseCtx<ColFwdState> ctx(C16::NT);

@@ -3,8 +3,9 @@
 //
 // Built by tests/test_column_cache_host.py with the host compiler from the product's header alone.  A miniature plan -- the cache, the
 // current stream and nothing else -- goes through the calls that touch the record in the library, each written as its call site is
-// (fftconv_api.cpp: prepare_kernels, flush_pending_prepare, set_images_impl, run_group_impl, fftconv_plan_convolve,
-// fftconv_plan_set_stream, kLongOptions; blockwise.cpp: tiled_convolve_save), next to a ground-truth model of A: which set's first
+// (fftconv_api.cpp: prepare_kernels, flush_pending_prepare, run_group_impl, fftconv_plan_convolve, fftconv_plan_set_stream,
+// kLongOptions; plan_image.cpp: the flush and the pair launch of set_images_impl, as image_route.hpp decides them; blockwise.cpp:
+// tiled_convolve_save), next to a ground-truth model of A: which set's first
 // chunk it holds, of which contents of the set's memory, written on which stream -- or garbage.  Modes:
 //   walk     EVERY sequence of those calls up to a fixed length: a hit (the kernels' column pass skipped) only where the model's A
 //            holds exactly the wanted set's first chunk, written on the wanted stream; a recorded request and a ready record never

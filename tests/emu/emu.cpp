@@ -63,7 +63,7 @@ int emu_image_spectrum(const float* data, int H, int W, int F, int max_kh, int m
     for (size_t i = 0; i < g.spectrum_elems(); i++) S[i] = mk(1e30f, -1e30f);
     if (g.fast_fwd) {
         d.fc_tw1 = t.fcl.tw1.data(); d.fc_tw2 = t.fcl.tw2.data(); d.fc_pairs = t.fcl.pairs.data();
-        FastColsFwdArgs fa = fast_cols_fwd_args(g, d, data, (size_t)H * W, H, H, W, F, S, (size_t)g.rows * g.s_pitch, g.s_pitch, false);
+        FastColsFwdArgs fa = image_fwd_args(g, d, data, H, W, H, W, F, S);
         EmuFastColsFwd run{fa, lds.data(), 3};
         if (!run_fast_cols_fwd(g.M, g.fast_cols.T, false, run)) return -8;
     } else {
@@ -138,8 +138,7 @@ int emu_convolve_spectrum(const float* spec, int H, int W, int F, int max_kh, in
             c32* Aj = A.data() + per_a * j;
             if (g.fast_fwd) {
                 d.fc_tw1 = t.fcl.tw1.data(); d.fc_tw2 = t.fcl.tw2.data(); d.fc_pairs = t.fcl.pairs.data();
-                FastColsFwdArgs fa = fast_cols_fwd_args(g, d, kernels[k0 + j], (size_t)khk * kwk, khk, khk, kwk, F, Aj,
-                                                        (size_t)g.rows * a_pitch_for(kwk), a_pitch_for(kwk), true);
+                FastColsFwdArgs fa = kernels_fwd_args(g, d, kernels[k0 + j], khk, kwk, F, Aj);
                 EmuFastColsFwd run{fa, lds.data(), 2};
                 if (!run_fast_cols_fwd(g.M, g.fast_cols.T, fast_cols_fwd_pruned_ok(g.fast_cols, khk), run)) return -8;
             } else {

@@ -18,8 +18,8 @@ for src in $SRC/kernels*.hip; do      # kernels.hip + one translation unit per k
   f=$(basename $src .hip)
   compile -I$SRC -c $src -o $OBJ/$f.o
 done
-for f in fftconv_api plan_cache host_ring blockwise placement fftconv_multi; do      # the host units (csrc/Makefile: HOSTUNITS)
-  compile -c $SRC/$f.cpp -o $OBJ/$f.o
+for src in $SRC/*.cpp; do      # the host units: every .cpp of csrc (csrc/Makefile: HOSTUNITS + fftconv_multi), so a new unit cannot be missed
+  compile -c $src -o $OBJ/$(basename $src .cpp).o
 done
 for p in $pids; do wait $p; done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $ROOT/cuda-fft-convolution_amd/ab/$NAME.so $OBJ/*.o -ldl
