@@ -82,6 +82,8 @@ _PIXEL_OF_DTYPE = {np.dtype(np.uint8): PIXEL_U8, np.dtype(np.uint16): PIXEL_U16,
 
 # Border modes (Plan.set_border / fftconv_plan_set_border): what the image is beyond its data.  NumPy's np.pad modes of the same
 # extension: constant, edge, symmetric, reflect, wrap.
+# matching scores (Plan.set_match_score; FFTCONV_SCORE_* of include/fftconv.h)
+SCORE_NONE, SCORE_CCOEFF_NORMED, SCORE_CCOEFF, SCORE_CCORR_NORMED, SCORE_SQDIFF = 0, 1, 2, 3, 4
 BORDER_ZERO, BORDER_CONSTANT, BORDER_REPLICATE, BORDER_SYMMETRIC, BORDER_REFLECT101, BORDER_CIRCULAR = 0, 1, 2, 3, 4, 5
 
 
@@ -134,7 +136,7 @@ EXPORTED_SYMBOLS = (
     "fftconv_plan_use_spectrum_buffer", "fftconv_plan_export_spectrum", "fftconv_plan_import_spectrum",
     "fftconv_plan_convolve", "fftconv_plan_convolve_packed", "fftconv_plan_prepare_kernels_packed",
     "fftconv_plan_synchronize", "fftconv_plan_set_stream",
-    "fftconv_plan_set_option", "fftconv_plan_set_output_rect", "fftconv_plan_set_normalisation", "fftconv_plan_set_border", "fftconv_plan_get_option", "fftconv_plan_get_profile",
+    "fftconv_plan_set_option", "fftconv_plan_set_output_rect", "fftconv_plan_set_normalisation", "fftconv_plan_set_match_score", "fftconv_plan_set_border", "fftconv_plan_get_option", "fftconv_plan_get_profile",
     "fftconv_fft_data", "fftconv_conv_fft_data",
     "fftconv_multi_create", "fftconv_multi_destroy", "fftconv_multi_set_image", "fftconv_multi_import_spectrum",
     "fftconv_multi_convolve", "fftconv_multi_set_option", "fftconv_multi_get_option",
@@ -210,6 +212,7 @@ def load_library():
     lib.fftconv_plan_set_option.argtypes = [vp, ctypes.c_char_p, ctypes.c_long]
     lib.fftconv_plan_set_output_rect.argtypes = [vp, ci, ci, ci, ci]
     lib.fftconv_plan_set_normalisation.argtypes = [vp, ci, ci, ci]
+    lib.fftconv_plan_set_match_score.argtypes = [vp, ci, ci, ci]
     lib.fftconv_plan_set_border.argtypes = [vp, ci, ctypes.c_float]
     lib.fftconv_plan_get_option.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_long)]
     lib.fftconv_plan_get_profile.argtypes = [vp, ctypes.POINTER(Profile), ci]
@@ -587,6 +590,13 @@ class Plan:
         output kernel scales in its store where the plan can; 0: always the staged crop), read-only "norm_direct", "normalise",
         "norm_box_h", "norm_box_w"."""
         _check(self._lib.fftconv_plan_set_normalisation(self._h, int(mode), int(box_h), int(box_w)))
+
+    def set_match_score(self, score, box_h=0, box_w=0):
+        """the template-matching score every map holds (fftconv_plan_set_match_score), over the box box_h x box_w -- the size every
+        kernel then has: SCORE_NONE (raw maps), SCORE_CCOEFF_NORMED (set_normalisation's mode 1: one state), SCORE_CCOEFF,
+        SCORE_CCORR_NORMED, SCORE_SQDIFF.  A call that changes score or box leaves the plan without an image.  Read-only options
+        "match_score", "norm_box_h", "norm_box_w", "norm_direct"; "norm_store" as for set_normalisation."""
+        _check(self._lib.fftconv_plan_set_match_score(self._h, int(score), int(box_h), int(box_w)))
 
     def set_border(self, mode, value=0.0):
         """what the image is beyond its data (fftconv_plan_set_border): BORDER_ZERO (the default), BORDER_CONSTANT (`value`),

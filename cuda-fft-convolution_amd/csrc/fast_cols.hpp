@@ -203,6 +203,19 @@ struct FastColsNormArgs {
     int pitch = 0, first = 0, per_image = 0;
 };
 
+// ADD instantiations only (matching score 4, SQDIFF: fftconv_plan_set_match_score; ncc.hpp): the planes Q of the plan's images, laid
+// out and indexed as FastColsNormArgs' d, and the constants c of the launch's kernels -- map `kernel` of the launch takes
+// c[(first + kernel) % per_image].  The value pair of rows 2n, 2n + 1 of window column w becomes v + (q + c), q the 8 bytes at
+// q + image * plane + w * pitch + 2n: first s = q + c, then v + s, one fp32 add each (ncc.hpp: score_sqdiff).  A kernel argument
+// of its own for the reason given above.
+struct FastColsSqdiffArgs {
+    const float* q = nullptr;
+    const float* c = nullptr;
+    size_t plane = 0;
+    int pitch = 0, first = 0, per_image = 0;
+};
+FC_HD bool fast_cols_sqdiff_args_ok(const FastColsSqdiffArgs& a) { return a.q && a.c && a.plane > 0 && a.pitch > 0 && a.first >= 0 && a.per_image >= 1; }
+
 template <class C>
 struct ColState {
     c32x2 pre[C::UPT];   // gather of the next tile
@@ -284,9 +297,13 @@ FC_HD int pair_of_unit(int u) {
 // words, and the first / last stored row of a column may be half a pair).
 // NORM (RECT, fp32 maps): normalised maps -- a value pair is multiplied by the pair of D at its window coordinate ahead of its
 // store (FastColsNormArgs, the body's last argument); the multiply is the only arithmetic added, and the store stays ONE predicated block per pair.
-template <class C, bool TILED, bool SLICED = false, bool DYN = false, bool OUT16 = false, bool RECT = false, bool NORM = false, class Ctx>
-FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int nwg, [[maybe_unused]] const FastColsNormArgs* nrm = nullptr) {
+// ADD (RECT, fp32 maps, never with NORM): matching score 4 -- a value pair becomes v + (q + c), q the pair of the plane Q at its
+// window coordinate and c the constant of the map's kernel (FastColsSqdiffArgs); the load sits where NORM's sits.
+template <class C, bool TILED, bool SLICED = false, bool DYN = false, bool OUT16 = false, bool RECT = false, bool NORM = false, bool ADD = false, class Ctx>
+FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int nwg, [[maybe_unused]] const FastColsNormArgs* nrm = nullptr,
+                          [[maybe_unused]] const FastColsSqdiffArgs* add = nullptr) {
     static_assert(!NORM || (RECT && !OUT16), "the fused scale exists on the fp32 rectangle family");
+    static_assert(!ADD || (RECT && !OUT16 && !NORM), "the fused additive store exists on the fp32 rectangle family, without the scale");
     static_assert(!RECT || (TILED && !SLICED), "the rectangle store exists for unsliced launches on the tiled intermediate");
     static_assert(!SLICED || TILED, "column slices exist for the tiled intermediate only");
     static_assert(!(SLICED && DYN), "the sliced tail round is dealt statically");
@@ -564,6 +581,13 @@ FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int
         // NORM: the scale plane of this tile's image (uniform over the tile)
         [[maybe_unused]] const float* dplane = nullptr;
         if constexpr (NORM) dplane = nrm->d + (size_t)((nrm->first + kernel) / nrm->per_image) * nrm->plane;
+        // ADD: the plane Q of this tile's image and the constant of its kernel (both uniform over the tile)
+        [[maybe_unused]] float addc = 0.f;
+        if constexpr (ADD) {
+            const int slot = add->first + kernel, image = slot / add->per_image;
+            dplane = add->q + (size_t)image * add->plane;
+            addc = add->c[slot - image * add->per_image];
+        }
         ctx.phase([&](int t, [[maybe_unused]] State& st) {
             // the next tile's gather (issued in C1) has had two stages to arrive: take it off the
             // memory counter now, so that landing it does not wait for the stores below
@@ -606,6 +630,7 @@ FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int
                         };
                         [[maybe_unused]] const float* dcol = nullptr;
                         if constexpr (NORM) dcol = dplane + (size_t)(w0 + col) * nrm->pitch;
+                        if constexpr (ADD) dcol = dplane + (size_t)(w0 + col) * add->pitch;
                         static_for<0, R1>([&](auto a_) {
                             constexpr int a = decltype(a_)::value;
                             const int hr = 2 * (j + a * m1) - g.h_lo;
@@ -614,6 +639,12 @@ FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int
                                     const c32 dv = *reinterpret_cast<const c32*>(dcol + 2 * (j + a * m1));
                                     v[a].x *= dv.x;
                                     v[a].y *= dv.y;
+                                }
+                                if constexpr (ADD) {               // (as NORM: both rows inside the plane, 8-byte aligned)
+                                    const c32 qv = *reinterpret_cast<const c32*>(dcol + 2 * (j + a * m1));
+                                    const float sx = qv.x + addc, sy = qv.y + addc;      // (the order of ncc.hpp's score_sqdiff)
+                                    v[a].x += sx;
+                                    v[a].y += sy;
                                 }
                                 if (g.rect_wide) {
                                     if constexpr (OUT16) FC_STREAM_STORE4(o + hr, fc_pack_map16(v[a].x, v[a].y, out_bf16));

@@ -588,6 +588,7 @@ struct FastColsShape {
     FastColsArgs a;
     int grid;
     FastColsNormArgs n{};      // the fused scale of normalised maps only (fast_cols_norm_launch_shape below)
+    FastColsSqdiffArgs q{};    // the fused additive store of score 4 only (fast_cols_sqdiff_launch_shape below)
 };
 inline FastColsShape fast_cols_launch_shape(int M, int T, const FastColsArgs& a, int want) {
     FastColsShape r{FastColsVariant::TILED_SLICED, a, 0};
@@ -673,6 +674,39 @@ inline FastColsShape fast_cols_norm_launch_shape(int T, const FastColsArgs& a, i
     r.n.pitch = win_h;
     r.n.first = image0 * per_image;
     r.n.per_image = per_image;
+    return r;
+}
+
+// Fused additive store of matching score 4, SQDIFF (fast_cols.hpp: ADD; plan entry fftconv_plan_set_match_score): the fp32 rectangle
+// kernel stores v + (Q + c) -- the plane Q at the pair's window coordinate, c the constant of the map's kernel.  Built by the NORM
+// family's rule: a configuration whose kernel spills a vector register, uses scratch or drops below 3 waves per SIMD in the build's
+// reports (csrc/kernels_cols_sqdiff_g*.rpt) is NOT built and listed here; its plans add while the staged window is cropped.
+constexpr int FC_COLS_SQDIFF_NOT_BUILT[] = {544, 2080};
+constexpr bool fast_cols_sqdiff_built(int M) {
+    for (int x : FC_COLS_SQDIFF_NOT_BUILT)
+        if (x == M) return false;
+    return true;
+}
+inline bool fast_cols_sqdiff_available(int M, bool y_tiled) { return y_tiled && fast_cols_lookup(M).ok && fast_cols_sqdiff_built(M); }
+// Whether the output kernel itself combines the maps of a plan with these settings (fftconv_plan::norm_direct for every score):
+// a score with a plane (1, 3: the NORM kernels; 4: the ADD kernels) under the conditions of fast_cols_norm_direct.  Scores 0 and 2
+// have nothing to combine.
+inline bool fast_cols_score_direct(int score, bool norm_store, bool blockwise, int map_format, long region, int M, bool y_tiled) {
+    if (score == FC_SCORE_SQDIFF)
+        return norm_store && !blockwise && map_format == FC_MAP_F32 && (region == 0 || region == 5) && fast_cols_sqdiff_available(M, y_tiled);
+    return fast_cols_norm_direct(score == FC_SCORE_CCOEFF_NORMED || score == FC_SCORE_CCORR_NORMED, norm_store, blockwise, map_format, region, M, y_tiled);
+}
+// The launch of nk score-4 maps: fast_cols_norm_launch_shape with the planes q in place of d, plus the constants c of the
+// per_image kernels of the launch (c[0]: the launch's first kernel)
+inline FastColsShape fast_cols_sqdiff_launch_shape(int T, const FastColsArgs& a, int off_h, int off_w, int out_h, int out_w, int want, const float* q,
+                                                   const float* c, int win_h, int win_w, int image0, int per_image) {
+    FastColsShape r = fast_cols_rect_launch_shape(T, a, off_h, off_w, out_h, out_w, want);
+    r.q.q = q;
+    r.q.c = c;
+    r.q.plane = (size_t)win_h * win_w;
+    r.q.pitch = win_h;
+    r.q.first = image0 * per_image;
+    r.q.per_image = per_image;
     return r;
 }
 

@@ -230,6 +230,9 @@ FC_HD c32 fma_js(float s, c32 a, c32 t) {
 // value once -- round to nearest even, subnormal results kept, fp16 overflow to +-inf.
 enum { FC_MAP_F32 = 0, FC_MAP_F16 = 1, FC_MAP_BF16 = 2 };
 FC_HD constexpr size_t fc_map_elem_bytes(int format) { return format == FC_MAP_F32 ? 4 : 2; }
+// matching scores (fftconv_plan_set_match_score, FFTCONV_SCORE_*; ncc.hpp): 1, 3 and 4 carry a per-image plane of window statistics
+enum { FC_SCORE_NONE = 0, FC_SCORE_CCOEFF_NORMED = 1, FC_SCORE_CCOEFF = 2, FC_SCORE_CCORR_NORMED = 3, FC_SCORE_SQDIFF = 4 };
+FC_HD constexpr bool score_has_plane(long score) { return score == FC_SCORE_CCOEFF_NORMED || score == FC_SCORE_CCORR_NORMED || score == FC_SCORE_SQDIFF; }
 
 FC_HD uint32_t fc_float_bits(float x) {
     uint32_t u;

@@ -90,7 +90,7 @@ BatchSizes batch_sizes(const fftconv_plan* p, int n, int kw) {
 int check_kernel_size(const fftconv_plan* p, int kh, int kw) {
     const Geometry& g = p->g;
     // normalised maps: the window statistics were taken over the plan's box, and a kernel of another size has another D
-    if (p->opt_normalise && (kh != p->norm_box_h || kw != p->norm_box_w))
+    if (p->opt_score && (kh != p->norm_box_h || kw != p->norm_box_w))
         return api_fail(FFTCONV_ERR_INVALID_ARG, "kernel %dx%d: while normalisation is on every kernel has the size of its box, %ldx%ld "
                         "(fftconv_plan_set_normalisation)", kh, kw, p->norm_box_h, p->norm_box_w);
     if (kh < 1 || kw < 1 || kh > g.fft_h || kw > g.fft_w)  // src/cudaConvolutionFFT.cu:242
@@ -112,12 +112,17 @@ namespace {
 
 // normalised maps (ncc.hpp): the na kernels at dk, centred per plane and scaled to unit joint norm, into the plan's scratch KN --
 // one kernel for every kernel location, so every entry returns the same bits
+// (the other scores, fftconv_plan_set_match_score: their preparation, and the constants c_k of the same na kernels into KC)
 int normalise_kernels(fftconv_plan* p, const float* dk, int na, int kh, int kw) {
     const Geometry& g = p->g;
     if (int rc = p->KN.ensure((size_t)na * g.F * kh * kw)) return rc;
     if (int rc = p->NS64.ensure((size_t)2 * na * g.F)) return rc;
-    FC_VERBOSE(p, "kernel normalisation: %d kernels centred per plane and scaled to unit norm", na);
-    HIP_TRY(launch_ncc_unit_kernels(dk, p->KN.p, na, g.F, kh * kw, p->NS64.p, p->stream));
+    if (p->opt_score == FC_SCORE_CCOEFF_NORMED) FC_VERBOSE(p, "kernel normalisation: %d kernels centred per plane and scaled to unit norm", na);
+    else {
+        if (int rc = p->KC.ensure((size_t)na)) return rc;
+        FC_VERBOSE(p, "kernel preparation for score %s: %d kernels", score_name(p->opt_score), na);
+    }
+    HIP_TRY(launch_score_kernels((int)p->opt_score, dk, p->KN.p, na, g.F, kh * kw, p->NS64.p, p->KC.p, p->stream));
     return 0;
 }
 
@@ -125,7 +130,7 @@ int normalise_kernels(fftconv_plan* p, const float* dk, int na, int kh, int kw) 
 // (normalised maps: the column pass reads the normalised kernels in KN; in_kn: they are there already -- a deferred request)
 int launch_kernel_cols(fftconv_plan* p, const float* dk, int a0, int na, int kh, int kw, bool in_kn = false) {
     const Geometry& g = p->g;
-    if (p->opt_normalise) {
+    if (p->opt_score) {
         if (!in_kn)
             if (int rc = normalise_kernels(p, dk + (size_t)a0 * g.F * kh * kw, na, kh, kw)) return rc;
         dk = p->KN.p;
@@ -197,9 +202,9 @@ struct Delivery {
 int plan_delivery(fftconv_plan* p, const Sink& sink, int nbY, Delivery& d) {
     const Geometry& g = p->g;
     if (sink.window && !g.fast_cols.ok) return api_fail(FFTCONV_ERR_INVALID_ARG, "an output window needs the specialised output kernel");
-    if (sink.window && p->opt_normalise) return api_fail(FFTCONV_ERR_INVALID_ARG, "an output window takes no normalisation");
+    if (sink.window && p->opt_score) return api_fail(FFTCONV_ERR_INVALID_ARG, "an output window takes no normalisation");
     d.rect = !sink.window && p->rect_direct();
-    d.norm = p->opt_normalise != 0;
+    d.norm = p->score_planes();
     d.norm_fused = d.norm && !sink.window && p->norm_direct();
     d.cropped = ((p->opt_region != 0 && !d.rect) || d.norm) && !d.norm_fused;
     d.stage = (d.cropped || d.rect || d.norm_fused) ? &p->OC : &p->O;
@@ -282,17 +287,35 @@ FastColsShape output_norm_shape(const fftconv_plan* p, const c32* y, float* out,
     return fast_cols_norm_launch_shape(g.fast_cols.T, fa, rect ? p->off_h : 0, rect ? p->off_w : 0, rect ? p->out_h : g.fft_h, rect ? p->out_w : g.fft_w,
                                        persistent_want(g.fast_cols.lds_bytes, g.fast_cols.NT, p->num_cus), p->ND.p, g.fft_h, g.fft_w, image0, per_image);
 }
+FastColsShape output_sqdiff_shape(const fftconv_plan* p, const c32* y, float* out, int ny, int image0, int per_image, const float* consts) {
+    const Geometry& g = p->g;
+    const bool rect = p->opt_region == 5;
+    const FastColsArgs fa = fast_cols_args(g, p->d, y, out, p->out_elems(), ny, FC_MAP_F32);
+    return fast_cols_sqdiff_launch_shape(g.fast_cols.T, fa, rect ? p->off_h : 0, rect ? p->off_w : 0, rect ? p->out_h : g.fft_h, rect ? p->out_w : g.fft_w,
+                                         persistent_want(g.fast_cols.lds_bytes, g.fast_cols.NT, p->num_cus), p->ND.p, consts, g.fft_h, g.fft_w, image0, per_image);
+}
 }  // namespace fc
 
 namespace {
 
 // output columns of ny maps: Y transformed along h into the maps at obase (or into the window of an overlap-save block)
 // (rect: the dense maps of the plan's rectangle, stored by the output kernel itself -- Delivery::rect)
+// (consts: score 4 -- the constant of the launch's first kernel, KC at the kernel's place in the chunk)
 int launch_output_cols(fftconv_plan* p, const OutWindow* win, float* obase, int ny, int format, bool rect, bool norm_fused = false, int image0 = 0,
-                       int per_image = 1) {
+                       int per_image = 1, const float* consts = nullptr) {
     const Geometry& g = p->g;
     if (int rc = p->prof_begin(PK_OUT_COLS, ny)) return rc;
-    if (norm_fused) {
+    if (norm_fused && p->opt_score == FC_SCORE_SQDIFF) {
+        const FastColsShape sh = output_sqdiff_shape(p, p->Y.p, obase, ny, image0, per_image, consts);
+        FC_VERBOSE(p, "output kernel: tiled rectangle plus Q + c (normalisation: fused SQDIFF), %d workgroups, fp32 elements, rows [%d, %d) of columns [%d, %d), images %d..",
+                   sh.grid, sh.a.h_lo, sh.a.fft_h, sh.a.rect_w_lo, sh.a.rect_w_lo + sh.a.rect_w_n, image0);
+        HIP_TRY(launch_fast_cols_sqdiff(g.M, g.fast_cols.T, sh, p->stream));
+    } else if (norm_fused && p->opt_score == FC_SCORE_CCORR_NORMED) {
+        const FastColsShape sh = output_norm_shape(p, p->Y.p, obase, ny, image0, per_image);
+        FC_VERBOSE(p, "output kernel: tiled rectangle scaled by Dc (normalisation: fused CCORR_NORMED), %d workgroups, fp32 elements, rows [%d, %d) of columns [%d, %d), images %d..",
+                   sh.grid, sh.a.h_lo, sh.a.fft_h, sh.a.rect_w_lo, sh.a.rect_w_lo + sh.a.rect_w_n, image0);
+        HIP_TRY(launch_fast_cols_norm(g.M, g.fast_cols.T, sh, p->stream));
+    } else if (norm_fused) {
         const FastColsShape sh = output_norm_shape(p, p->Y.p, obase, ny, image0, per_image);
         FC_VERBOSE(p, "output kernel: tiled rectangle scaled by D (normalisation: fused), %d workgroups, fp32 elements, rows [%d, %d) of columns [%d, %d), images %d..",
                    sh.grid, sh.a.h_lo, sh.a.fft_h, sh.a.rect_w_lo, sh.a.rect_w_lo + sh.a.rect_w_n, image0);
@@ -386,7 +409,7 @@ int run_group_impl(fftconv_plan* p, int n, const float* dk, int kh, int kw, cons
         // (several images: no automatic tuning -- the tuner's probe launches are shaped for the maps of one image)
         // (normalised maps: no tuning -- the probe launches are the plain output kernel's, not the scaled launch the group runs; the
         //  allocation stays marked fresh, so the first group after fftconv_plan_set_normalisation(0) tunes it as a fresh plan's)
-        if (p->opt_normalise) {}
+        if (p->score_planes()) {}
         else if (B > 1 && p->opt_tune_placement < 0) p->Y.fresh = false;
         else if (int rc = tune_intermediate_placement(p, sink, n * B, nbY, d.cropped ? p->O.p : d.staged() ? d.stage->p : sink.packed, !d.cropped && !d.staged(), d.kernel_format))
             return rc;
@@ -411,9 +434,10 @@ int run_group_impl(fftconv_plan* p, int n, const float* dk, int kh, int kw, cons
                 if (int rc = ring_claim_staging(p, &buf)) return rc;
             float* dest = sink.window ? sink.window->base + (size_t)first * sink.window->map_stride            // where the maps of this batch go
                           : d.staged() ? map_at(d.stage->p, (size_t)buf * nbY * d.oe, d.eb) : map_at(sink.packed, (size_t)first * d.oe, d.eb);
-            if (int rc = launch_output_cols(p, sink.window, d.cropped ? p->O.p : dest, ny, d.kernel_format, d.rect, d.norm_fused, l.b0, l.nk)) return rc;
+            const float* consts = p->KC.p ? p->KC.p + (l.k0 - l.a0) : nullptr;      // (KC holds the chunk's kernels, as A does)
+            if (int rc = launch_output_cols(p, sink.window, d.cropped ? p->O.p : dest, ny, d.kernel_format, d.rect, d.norm_fused, l.b0, l.nk, consts)) return rc;
             if (d.cropped)
-                if (int rc = launch_region(p, p->O.p, dest, ny, p->stream, d.norm ? p->ND.p : nullptr, l.b0, l.nk)) return rc;
+                if (int rc = launch_region(p, p->O.p, dest, ny, p->stream, d.norm ? p->ND.p : nullptr, l.b0, l.nk, consts)) return rc;
             if (int rc = deliver_batch(p, d, sink, first, ny, buf, dest)) return rc;
         }
     }
@@ -462,7 +486,7 @@ const LongOption kLongOptions[] = {
     {"norm_store", &fftconv_plan::opt_norm_store, 0, 1, OPT_BOOL},       // (the kernel column spectra are the same either way: no OPT_FORGETS)
     {"pixel_store", &fftconv_plan::opt_pixel_store, 0, 1, OPT_BOOL},     // (it only chooses the route of the next typed call: no OPT_FORGETS)
     {"border_store", &fftconv_plan::opt_border_store, 0, 1, OPT_BOOL},   // (it only chooses the route of the next image: no OPT_FORGETS)
-    {"normalise", &fftconv_plan::opt_normalise, 0, 0, OPT_GET_ONLY},     // (fftconv_plan_set_normalisation sets the three)
+    {"match_score", &fftconv_plan::opt_score, 0, 0, OPT_GET_ONLY},       // (fftconv_plan_set_match_score / _set_normalisation set the three; "normalise": get_option)
     {"norm_box_h", &fftconv_plan::norm_box_h, 0, 0, OPT_GET_ONLY},
     {"norm_box_w", &fftconv_plan::norm_box_w, 0, 0, OPT_GET_ONLY},
 };
@@ -476,12 +500,26 @@ const LongOption* find_option(const char* name, unsigned not_flag) {
 
 namespace fc {
 
-int launch_region(const fftconv_plan* p, const float* src, float* dst, int nmaps, hipStream_t s, const float* scale, int image0, int per_image) {
+int launch_region(const fftconv_plan* p, const float* src, float* dst, int nmaps, hipStream_t s, const float* scale, int image0, int per_image,
+                  const float* consts) {
     const Geometry& g = p->g;      // (block-wise plans: g holds the whole window)
     const int format = (int)p->opt_map_format;      // of dst; src is fp32
     if (scale) {     // normalised maps: the same pass multiplies by D at the window coordinate; region 0 is the crop of the whole window
         const int oh = p->opt_region ? p->out_h : g.fft_h, ow = p->opt_region ? p->out_w : g.fft_w;
         const int fh = p->opt_region ? p->off_h : 0, fw = p->opt_region ? p->off_w : 0;
+        if (p->opt_score == FC_SCORE_SQDIFF) {
+            FC_VERBOSE(p, "normalisation: staged SQDIFF -- %d maps of images %d.. plus Q + c while %s from the fp32 window into %d x %d %s maps", nmaps, image0,
+                       p->opt_region == 4 ? "padded" : "cropped", oh, ow, kMapFormatNames[format]);
+            if (p->opt_region == 4)
+                HIP_TRY(launch_pad_maps_sqdiff(src, g.fft_h, g.fft_w, g.map_elems(), dst, oh, ow, p->out_elems(), nmaps, scale, consts, image0, per_image, s, format));
+            else
+                HIP_TRY(launch_crop_maps_sqdiff(src, g.fft_h, g.map_elems(), dst, oh, ow, p->out_elems(), fh, fw, nmaps, scale, consts, image0, per_image, s, format));
+            return 0;
+        }
+        if (p->opt_score == FC_SCORE_CCORR_NORMED)
+            FC_VERBOSE(p, "normalisation: staged CCORR_NORMED -- %d maps of images %d.. scaled by Dc while %s from the fp32 window into %d x %d %s maps", nmaps,
+                       image0, p->opt_region == 4 ? "padded" : "cropped", oh, ow, kMapFormatNames[format]);
+        else
         FC_VERBOSE(p, "normalisation: staged -- %d maps of images %d.. scaled by D while %s from the fp32 window into %d x %d %s maps", nmaps, image0,
                    p->opt_region == 4 ? "padded" : "cropped", oh, ow, kMapFormatNames[format]);
         if (p->opt_region == 4)
@@ -519,7 +557,7 @@ int prepare_kernels(fftconv_plan* p, int n, const float* dk, int kh, int kw, boo
     const int na = std::min(bs.nbA, n);
     const bool timed_apart = p->profile && (p->profile_mask & ((1u << PK_KERNEL_COLS) | (1u << PK_IMAGE_COLS)));   // per-kind figures wanted
     if ((force_defer || p->opt_defer_prepare) && p->g.fast_fwd && !p->opt_flip_kernels && !timed_apart) {   // deferred: rides in the launch of the next image's column pass
-        if (p->opt_normalise)      // (now, while the caller's kernels are there: the deferred column pass reads KN)
+        if (p->opt_score)      // (now, while the caller's kernels are there: the deferred column pass reads KN)
             if (int rc = normalise_kernels(p, dk, na, kh, kw)) return rc;
         p->a_holds.request(ks, na);
         return 0;
@@ -728,7 +766,7 @@ int fftconv_plan_get_info(const fftconv_plan* plan, fftconv_plan_info* info) {
     info->out_w = plan->opt_region ? plan->out_w : g.fft_w;
     info->out_map_bytes = plan->out_map_bytes();
     info->workspace_bytes = plan->A.bytes() + plan->Y.bytes() + plan->K.bytes() + plan->O.bytes() + plan->I.bytes() + plan->IT.bytes() + plan->IE.bytes() +
-                            plan->ND.bytes() + plan->KN.bytes() + plan->NS64.bytes();      // (normalised maps: all 0 until the mode is on)
+                            plan->ND.bytes() + plan->KN.bytes() + plan->KC.bytes() + plan->NS64.bytes();      // (matching scores: all 0 until one is on)
     if (const TiledState* ts = plan->tiled) {     // block-wise: the window of the whole image; the spectrum is every block's
         info->spectrum_bytes = ts->spec_total() * sizeof(c32);
         info->map_bytes = ts->big_map() * sizeof(float);
@@ -946,26 +984,39 @@ int fftconv_plan_set_output_rect(fftconv_plan* plan, int off_h, int off_w, int o
     return 0;
 }
 
+// fftconv_plan_set_normalisation and fftconv_plan_set_match_score behind their argument checks: one state, one set of rules
+static int set_score(fftconv_plan* plan, int score, int box_h, int box_w) {
+    if (plan->tiled)
+        return api_fail(FFTCONV_ERR_INVALID_ARG, "normalisation is not available on a block-wise plan (%d blocks: the window statistics span blocks); "
+                        "create a one-pass plan (fftconv_plan_options.blockwise = 1)", plan->tiled->nblk);
+    if (score != 0 && plan->border_mode)
+        return api_fail(FFTCONV_ERR_INVALID_ARG, "a border is on (fftconv_plan_set_border, mode %ld): the window statistics of normalised maps assume zero padding",
+                        plan->border_mode);
+    if (score == 0) box_h = box_w = 0;
+    if (plan->opt_score == score && plan->norm_box_h == box_h && plan->norm_box_w == box_w) return 0;      // nothing changes: the image stays
+    if (int rc = use_device(plan)) return rc;
+    HIP_TRY(hipStreamSynchronize(plan->stream));
+    // the kernel column spectra are those of the prepared kernels, or not; the plane belongs to (image, score, box) and the pixels are gone
+    plan->a_holds.forget();
+    plan->n_images = 0;
+    plan->opt_score = score; plan->norm_box_h = box_h; plan->norm_box_w = box_w;
+    return 0;
+}
+
 int fftconv_plan_set_normalisation(fftconv_plan* plan, int mode, int box_h, int box_w) {
     if (!plan) return api_fail(FFTCONV_ERR_INVALID_ARG, "plan is NULL");
     const Geometry& g = plan->g;
     if (const char* why = ncc_args_error(mode, box_h, box_w, g.max_kh, g.max_kw))
         return api_fail(FFTCONV_ERR_INVALID_ARG, "%s (mode %d, box %d x %d asked of a plan with MAX_KERNEL %d x %d)", why, mode, box_h, box_w, g.max_kh, g.max_kw);
-    if (plan->tiled)
-        return api_fail(FFTCONV_ERR_INVALID_ARG, "normalisation is not available on a block-wise plan (%d blocks: the window statistics span blocks); "
-                        "create a one-pass plan (fftconv_plan_options.blockwise = 1)", plan->tiled->nblk);
-    if (mode != 0 && plan->border_mode)
-        return api_fail(FFTCONV_ERR_INVALID_ARG, "a border is on (fftconv_plan_set_border, mode %ld): the window statistics of normalised maps assume zero padding",
-                        plan->border_mode);
-    if (mode == 0) box_h = box_w = 0;
-    if (plan->opt_normalise == mode && plan->norm_box_h == box_h && plan->norm_box_w == box_w) return 0;      // nothing changes: the image stays
-    if (int rc = use_device(plan)) return rc;
-    HIP_TRY(hipStreamSynchronize(plan->stream));
-    // the kernel column spectra are those of the normalised kernels, or not; D belongs to (image, box) and the pixels are gone
-    plan->a_holds.forget();
-    plan->n_images = 0;
-    plan->opt_normalise = mode; plan->norm_box_h = box_h; plan->norm_box_w = box_w;
-    return 0;
+    return set_score(plan, mode, box_h, box_w);
+}
+
+int fftconv_plan_set_match_score(fftconv_plan* plan, int score, int box_h, int box_w) {
+    if (!plan) return api_fail(FFTCONV_ERR_INVALID_ARG, "plan is NULL");
+    const Geometry& g = plan->g;
+    if (const char* why = score_args_error(score, box_h, box_w, g.max_kh, g.max_kw))
+        return api_fail(FFTCONV_ERR_INVALID_ARG, "%s (score %d, box %d x %d asked of a plan with MAX_KERNEL %d x %d)", why, score, box_h, box_w, g.max_kh, g.max_kw);
+    return set_score(plan, score, box_h, box_w);
 }
 
 int fftconv_plan_set_border(fftconv_plan* plan, int mode, float value) {
@@ -977,7 +1028,7 @@ int fftconv_plan_set_border(fftconv_plan* plan, int mode, float value) {
     if (plan->tiled)
         return api_fail(FFTCONV_ERR_INVALID_ARG, "a border is not available on a block-wise plan (%d blocks: the blocks' own rims lie inside the image); "
                         "create a one-pass plan (fftconv_plan_options.blockwise = 1)", plan->tiled->nblk);
-    if (mode != 0 && plan->opt_normalise)
+    if (mode != 0 && plan->opt_score)
         return api_fail(FFTCONV_ERR_INVALID_ARG, "normalisation is on (fftconv_plan_set_normalisation): the window statistics of normalised maps assume zero padding");
     if (mode != FC_BORDER_CONSTANT) value = 0.f;
     if (plan->border_mode == mode && plan->border_value == value) return 0;      // nothing changes: the image and the rectangle stay
@@ -1011,6 +1062,7 @@ int fftconv_plan_get_option(fftconv_plan* plan, const char* name, long* value) {
     if (!strcmp(name, "rect_direct")) { *value = plan->rect_direct() ? 1 : 0; return 0; }
     if (!strcmp(name, "rect_store")) { *value = plan->opt_rect_store; return 0; }
     // read-only: 1 if, with the plan's current settings, the output kernel itself scales normalised maps (else the staged crop does)
+    if (!strcmp(name, "normalise")) { *value = plan->opt_score == FC_SCORE_CCOEFF_NORMED ? 1 : 0; return 0; }      // (mode 1 is score 1)
     if (!strcmp(name, "norm_direct")) { *value = plan->norm_direct() ? 1 : 0; return 0; }
     // read-only: 1 if, with the plan's current settings, a spectral-row launch of more than one image walks over images
     if (!strcmp(name, "image_walk_active")) { *value = plan->image_walk_active() ? 1 : 0; return 0; }

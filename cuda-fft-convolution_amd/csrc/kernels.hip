@@ -233,6 +233,13 @@ hipError_t launch_fast_cols_norm(int M, int T, const FastColsShape& shape, hipSt
     return in_first_group<FC_COL_GROUPS>([&](auto g) { return launch_fast_cols_norm_group<g.value>(M, T, shape, s); });
 }
 
+hipError_t launch_fast_cols_sqdiff(int M, int T, const FastColsShape& shape, hipStream_t s) {
+    if (shape.a.ntiles <= 0) return hipSuccess;
+    if (!shape.a.y_tiled || (shape.variant != FastColsVariant::TILED && shape.variant != FastColsVariant::TILED_DYN)) return hipErrorInvalidValue;
+    if (shape.a.out_format != FC_MAP_F32 || !fast_cols_sqdiff_args_ok(shape.q)) return hipErrorInvalidValue;
+    return in_first_group<FC_COL_GROUPS>([&](auto g) { return launch_fast_cols_sqdiff_group<g.value>(M, T, shape, s); });
+}
+
 hipError_t launch_fast_cols_fwd(int M, int T, bool pruned, const FastColsFwdArgs& a, int num_cus, hipStream_t s) {
     if (a.ntiles <= 0) return hipSuccess;
     return in_first_group<FC_COL_GROUPS>([&](auto g) { return launch_fast_cols_fwd_group<g.value>(M, T, pruned, a, num_cus, s); });

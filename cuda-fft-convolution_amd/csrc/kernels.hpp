@@ -46,6 +46,24 @@ hipError_t launch_crop_maps_norm(const float* src, int src_h, size_t src_map_str
                                  int off_h, int off_w, int nmaps, const float* D, int image0, int per_image, hipStream_t s, int format = FC_MAP_F32);
 hipError_t launch_pad_maps_norm(const float* src, int src_h, int src_w, size_t src_map_stride, float* dst, int dst_h, int dst_w,
                                 size_t dst_map_stride, int nmaps, const float* D, int image0, int per_image, hipStream_t s, int format = FC_MAP_F32);
+// ---- the other matching scores (fftconv_plan_set_match_score; ncc.hpp): FC_SCORE_*
+// launch_ncc_statistics_typed for a score with a plane: 1 the call above, 3 Dc = E^(-1/2), 4 Q = E at d
+hipError_t launch_score_statistics_typed(int score, const void* img, int pixel_format, int H, int W, int F, int fft_h, int fft_w, int box_h, int box_w,
+                                         double* scratch, int strip_cols, float* d, hipStream_t s);
+// (pass 2 of scores 3 and 4 over one strip, kernels_score.hip, and the plane statistics of kernels_ncc.hip for score 2's means; errors
+//  are collected by the caller's hipGetLastError)
+void launch_score_plane(int score, const double* c2, int ncols, int nout, int fft_h, int F, int box_w, float* d, hipStream_t s);
+void launch_ncc_plane_stats(const float* src, int planes, int plane_elems, double* stats, hipStream_t s);
+// launch_ncc_unit_kernels for any score: 2 centred, 3 T / sqrt(t2), 4 -2 T; consts[k] = (float) t2 of kernel k (scores 2-4; n floats)
+hipError_t launch_score_kernels(int score, const float* src, float* dst, int n, int F, int plane_elems, double* stats, float* consts, hipStream_t s);
+// launch_crop_maps / launch_pad_maps of score 4: element s becomes s + (Q + c), Q ([image][src_w][src_h]) at its window coordinate,
+// c = consts[m % per_image] for map m of the launch
+hipError_t launch_crop_maps_sqdiff(const float* src, int src_h, size_t src_map_stride, float* dst, int dst_h, int dst_w, size_t dst_map_stride,
+                                   int off_h, int off_w, int nmaps, const float* Q, const float* consts, int image0, int per_image, hipStream_t s,
+                                   int format = FC_MAP_F32);
+hipError_t launch_pad_maps_sqdiff(const float* src, int src_h, int src_w, size_t src_map_stride, float* dst, int dst_h, int dst_w,
+                                  size_t dst_map_stride, int nmaps, const float* Q, const float* consts, int image0, int per_image, hipStream_t s,
+                                  int format = FC_MAP_F32);
 hipError_t launch_cols_r2c(const ColsR2CArgs& a, int tiles, int planes, int threads, size_t lds_bytes, hipStream_t s);
 hipError_t launch_rows_fwd(const RowsFwdArgs& a, int rows, int threads, size_t lds_bytes, hipStream_t s);
 // specialised forward image rows (fast_rows_fwd.hpp); hipErrorInvalidValue if L has no configuration
@@ -65,6 +83,8 @@ hipError_t launch_fast_cols(int M, int T, const FastColsArgs& a, int num_cus, hi
 hipError_t launch_fast_cols_rect(int M, int T, const FastColsShape& shape, hipStream_t s);
 // the fused scale of normalised maps (fast_cols.hpp: NORM): `shape` from fast_cols_norm_launch_shape (fast_paths.hpp)
 hipError_t launch_fast_cols_norm(int M, int T, const FastColsShape& shape, hipStream_t s);
+// the fused additive store of score 4 (fast_cols.hpp: ADD): `shape` from fast_cols_sqdiff_launch_shape (fast_paths.hpp)
+hipError_t launch_fast_cols_sqdiff(int M, int T, const FastColsShape& shape, hipStream_t s);
 hipError_t launch_fast_cols_fwd(int M, int T, bool pruned, const FastColsFwdArgs& a, int num_cus, hipStream_t s);
 // image columns of typed pixels (kernels_cols_fwd_px_g<G>.hip; pixel_format.hpp): a.in holds elements of px.format, px from
 // fast_cols_fwd_pixel_load; hipErrorInvalidValue for fp32 pixels and for a configuration that is not built (fast_cols_fwd_px_built)
@@ -99,6 +119,8 @@ template <int G> GroupResult launch_fast_cols_rect_group(int M, int T, const Fas
 template <int G> GroupResult launch_fast_cols_rect16_group(int M, int T, const FastColsShape& shape, hipStream_t s);
 // (the fused scale of normalised maps, fp32: kernels_cols_norm_g<G>.hip)
 template <int G> GroupResult launch_fast_cols_norm_group(int M, int T, const FastColsShape& shape, hipStream_t s);
+// (the fused additive store of score 4, fp32: kernels_cols_sqdiff_g<G>.hip)
+template <int G> GroupResult launch_fast_cols_sqdiff_group(int M, int T, const FastColsShape& shape, hipStream_t s);
 template <int G> GroupResult launch_fast_cols_fwd_group(int M, int T, bool pruned, const FastColsFwdArgs& a, int num_cus, hipStream_t s);
 // (typed image pixels: kernels_cols_fwd_px_g<G>.hip)
 template <int G> GroupResult launch_fast_cols_fwd_px_group(int M, int T, const FastColsFwdArgs& a, const PixelLoad& px, int num_cus, hipStream_t s);

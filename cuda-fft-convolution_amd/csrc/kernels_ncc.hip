@@ -3,6 +3,7 @@
 // fp32 window by D on its way into the maps.  None of the first two is on the hot path.
 #include "kernels.hpp"
 #include "ncc.hpp"
+#include "ncc_device.hpp"
 
 namespace fc {
 namespace {
@@ -33,17 +34,6 @@ __global__ void __launch_bounds__(256) k_ncc_scale(const double* __restrict__ c1
 
 // kernels: one workgroup of FC_NCC_LANES threads per plane (mean, sum of squares around it: ncc.hpp's lanes and fold), then
 // T'' -- every thread of a kernel's workgroup sums the F plane figures in the same order
-__device__ __forceinline__ double fold_lanes(double* part, int t, double mine) {
-    part[t] = mine;
-    __syncthreads();
-    for (int s = FC_NCC_LANES / 2; s > 0; s >>= 1) {
-        if (t < s) part[t] += part[t + s];
-        __syncthreads();
-    }
-    const double r = part[0];
-    __syncthreads();
-    return r;
-}
 __global__ void __launch_bounds__(FC_NCC_LANES) k_ncc_plane_stats(const float* __restrict__ src, int pe, double* __restrict__ stats) {
     __shared__ double part[FC_NCC_LANES];
     const int t = (int)threadIdx.x;
@@ -63,16 +53,6 @@ __global__ void __launch_bounds__(256) k_ncc_unit_kernels(const float* __restric
     const double norm = ncc_kernel_norm(st, F);
     const size_t base = (size_t)k * F * pe;
     for (int e = (int)threadIdx.x; e < F * pe; e += (int)blockDim.x) dst[base + e] = ncc_unit(src[base + e], st[2 * (e / pe)], norm);
-}
-
-template <bool OUT16>
-FC_D void put(std::conditional_t<OUT16, uint16_t, float>* d, float x, [[maybe_unused]] int bf16) {
-    if constexpr (OUT16) {
-        // a 16-bit map is the ROUNDED fp32 product: behind this the compiler cannot merge the multiply and the conversion into one
-        // mixed-precision instruction that rounds the exact product once
-        asm volatile("" : "+v"(x));
-        *d = fc_map16(x, bf16 != 0);
-    } else *d = x;
 }
 
 // NORM siblings of k_crop_maps / k_crop_maps16 (kernels.hip): the element is scaled by D at its WINDOW coordinate while it is
@@ -112,6 +92,12 @@ hipError_t launch_ncc_statistics(const float* img, int H, int W, int F, int fft_
 
 hipError_t launch_ncc_statistics_typed(const void* vimg, int pixel_format, int H, int W, int F, int fft_h, int fft_w, int box_h, int box_w,
                                        double* scratch, int strip_cols, float* d, hipStream_t s) {
+    return launch_score_statistics_typed(FC_SCORE_CCOEFF_NORMED, vimg, pixel_format, H, W, F, fft_h, fft_w, box_h, box_w, scratch, strip_cols, d, s);
+}
+
+hipError_t launch_score_statistics_typed(int score, const void* vimg, int pixel_format, int H, int W, int F, int fft_h, int fft_w, int box_h, int box_w,
+                                         double* scratch, int strip_cols, float* d, hipStream_t s) {
+    if (!score_has_plane(score)) return hipErrorInvalidValue;
     if (fft_h <= 0 || fft_w <= 0 || F <= 0) return hipSuccess;
     if (box_h < 1 || box_w < 1 || strip_cols < box_w || !fc_pixel_format_ok(pixel_format)) return hipErrorInvalidValue;
     const float* img = static_cast<const float*>(vimg);
@@ -128,7 +114,9 @@ hipError_t launch_ncc_statistics_typed(const void* vimg, int pixel_format, int H
             hipLaunchKernelGGL(k_ncc_column_sums, grid, dim3(256), 0, s, img, H, W, fft_h, box_h, j0 - (box_w - 1), ncols, c1, c2);
         else      // (typed pixels: the kernel lives in kernels_pixels.hip, so that this unit's device code stays what it was)
             launch_ncc_column_sums_px(vimg, px, H, W, F, fft_h, box_h, j0 - (box_w - 1), ncols, c1, c2, s);
-        hipLaunchKernelGGL(k_ncc_scale, dim3((unsigned)nout, zr), dim3(256), 0, s, c1, c2, ncols, fft_h, F, box_w, box_h * box_w, d + (size_t)j0 * fft_h);
+        if (score == FC_SCORE_CCOEFF_NORMED)
+            hipLaunchKernelGGL(k_ncc_scale, dim3((unsigned)nout, zr), dim3(256), 0, s, c1, c2, ncols, fft_h, F, box_w, box_h * box_w, d + (size_t)j0 * fft_h);
+        else launch_score_plane(score, c2, ncols, nout, fft_h, F, box_w, d + (size_t)j0 * fft_h, s);      // (kernels_score.hip)
     }
     return hipGetLastError();
 }
@@ -138,6 +126,10 @@ hipError_t launch_ncc_unit_kernels(const float* src, float* dst, int n, int F, i
     hipLaunchKernelGGL(k_ncc_plane_stats, dim3((unsigned)((long)n * F)), dim3(FC_NCC_LANES), 0, s, src, plane_elems, stats);
     hipLaunchKernelGGL(k_ncc_unit_kernels, dim3((unsigned)n), dim3(256), 0, s, src, dst, F, plane_elems, stats);
     return hipGetLastError();
+}
+
+void launch_ncc_plane_stats(const float* src, int planes, int plane_elems, double* stats, hipStream_t s) {
+    hipLaunchKernelGGL(k_ncc_plane_stats, dim3((unsigned)planes), dim3(FC_NCC_LANES), 0, s, src, plane_elems, stats);
 }
 
 hipError_t launch_crop_maps_norm(const float* src, int src_h, size_t src_map_stride, float* dst, int dst_h, int dst_w, size_t dst_map_stride,

@@ -58,6 +58,32 @@ FC_HD float ncc_scale(const double* c1, const double* c2, size_t plane, int pitc
     return (float)(1.0 / sqrt(den2));
 }
 
+// Matching scores beside mode 1 (fftconv_plan_set_match_score; the table of include/fftconv.h).  The planes of scores 3 and 4
+// come from the pass-1 sums of squares alone: E(u) = sum_f s2_f(u), summed in the order ncc_scale sums its e.
+//   score 3 (CCORR_NORMED): Dc = (float) E^(-1/2), 0 where E == 0.  No relative floor is needed: E is a sum of non-negative float64
+//   terms (exact squares of fp32 values), so it is exactly 0 if and only if every pixel under the box is 0 -- no cancellation can
+//   produce a small non-zero E -- and otherwise it is accurate to a relative 2^-52.
+//   score 4 (SQDIFF): Q = (float) E.
+inline const char* score_name(long score) {
+    static const char* const names[] = {"none", "CCOEFF_NORMED", "CCOEFF", "CCORR_NORMED", "SQDIFF"};
+    return score >= 0 && score <= 4 ? names[score] : "?";
+}
+FC_HD double ncc_energy(const double* c2, size_t plane, int pitch, int F, int col_hi, int i, int box_w) {
+    double e = 0.0;
+    for (int f = 0; f < F; f++) {
+        double s2 = 0.0;
+        for (int b = 0; b < box_w; b++) s2 += c2[(size_t)f * plane + (size_t)(col_hi - b) * pitch + i];
+        e += s2;
+    }
+    return e;
+}
+// pass 2 of scores 3 and 4, one element (the arguments of ncc_scale; c2 only)
+FC_HD float score_plane(int score, const double* c2, size_t plane, int pitch, int F, int col_hi, int i, int box_w) {
+    const double e = ncc_energy(c2, plane, pitch, F, col_hi, i, box_w);
+    if (score == FC_SCORE_SQDIFF) return (float)e;
+    return e == 0.0 ? 0.f : (float)(1.0 / sqrt(e));
+}
+
 // kernel normalisation: the sums of one plane of `pe` floats are taken by FC_NCC_LANES lanes -- lane t adds the elements t,
 // t + FC_NCC_LANES, ... in ascending order -- whose partial sums are then folded by halves (lane t += lane t + s for s =
 // FC_NCC_LANES / 2 ... 1): one fixed order, whoever runs the lanes (a workgroup per plane on the device, a loop on the host)
@@ -94,6 +120,28 @@ FC_HD double ncc_kernel_norm(const double* stats, int F) {
 // ... and one element of T'': all zeros where the norm is 0
 FC_HD float ncc_unit(float x, double mean, double norm) { return norm > 0.0 ? (float)(((double)x - mean) / norm) : 0.f; }
 
+// ... and of the other scores' kernels.  `t2`: the joint sum of squares sum_f sum T_f^2 of a kernel's F planes, each plane's taken
+// with centre 0 by the lanes and the fold above, the planes added in ascending order.
+//   score 2: centred per plane, not scaled;  score 3: T / sqrt(t2), all zeros where t2 = 0;  score 4: -2 T (exact in fp32)
+FC_HD float score_kernel_elem(int score, float x, double mean, double norm, double t2) {
+    if (score == FC_SCORE_CCOEFF_NORMED) return ncc_unit(x, mean, norm);
+    if (score == FC_SCORE_CCOEFF) return (float)((double)x - mean);
+    if (score == FC_SCORE_CCORR_NORMED) return t2 > 0.0 ? (float)((double)x / sqrt(t2)) : 0.f;
+    return -2.f * x;
+}
+// sum of squares (centre 0) of one plane, host form (tests/match_score_host)
+inline double score_plane_t2(const float* plane, int pe) {
+    double part[FC_NCC_LANES];
+    for (int t = 0; t < FC_NCC_LANES; t++) part[t] = ncc_lane_sum(plane, pe, t, 0.0, true);
+    return ncc_fold(part);
+}
+// score 4, one element of a map: first s = q + c, one fp32 add, then x + s, one fp32 add -- on every route.  Written with
+// intrinsic-free plain adds: an addition cannot be contracted with another addition, so fused and staged stores agree to the bit.
+FC_HD float score_sqdiff(float x, float q, float c) {
+    const float s = q + c;
+    return x + s;
+}
+
 // image of map `slot` of a launch that covers the images from image0 on with per_image kernels each (slots are image-major)
 FC_HD int ncc_image_of(int image0, int slot, int per_image) { return image0 + slot / per_image; }
 
@@ -101,6 +149,14 @@ FC_HD int ncc_image_of(int image0, int slot, int per_image) { return image0 + sl
 inline const char* ncc_args_error(long mode, long box_h, long box_w, int max_kh, int max_kw) {
     if (mode != 0 && mode != 1) return "normalisation mode is 0 (off) or 1 (zero-mean normalised cross-correlation)";
     if (mode == 1 && (box_h < 1 || box_w < 1 || box_h > max_kh || box_w > max_kw)) return "normalisation box: 1 <= box <= MAX_KERNEL per dimension";
+    return nullptr;
+}
+
+// fftconv_plan_set_match_score: why (score, box) is refused, or nullptr
+inline const char* score_args_error(long score, long box_h, long box_w, int max_kh, int max_kw) {
+    if (score < FC_SCORE_NONE || score > FC_SCORE_SQDIFF)
+        return "matching score is 0 (none), 1 (CCOEFF_NORMED), 2 (CCOEFF), 3 (CCORR_NORMED) or 4 (SQDIFF)";
+    if (score != 0 && (box_h < 1 || box_w < 1 || box_h > max_kh || box_w > max_kw)) return "matching score box: 1 <= box <= MAX_KERNEL per dimension";
     return nullptr;
 }
 

@@ -48,7 +48,7 @@ ImageRoute image_route_of(const fftconv_plan* p, int fmt, int nimg, int location
     in.H = g.H; in.W = g.W; in.F = g.F; in.max_kh = g.max_kh; in.max_kw = g.max_kw;
     in.host_pinned = p->opt_host_pinned != 0;
     in.pixel_direct = p->pixel_direct(); in.border_direct = p->border_direct();
-    in.border_mode = p->border_mode != 0; in.fast_fwd = g.fast_fwd; in.normalise = p->opt_normalise != 0;
+    in.border_mode = p->border_mode != 0; in.fast_fwd = g.fast_fwd; in.normalise = p->score_planes();
     in.request = !p->a_holds.pending() ? KernelRequest::None : p->a_holds.pending_off_stream(p->stream) ? KernelRequest::OtherStream : KernelRequest::ThisStream;
     return plan_image_route(in);
 }
@@ -102,7 +102,7 @@ int prepare_image_state(fftconv_plan* p, int nimg) {
     p->n_images = 0;
     p->pixel_format = FC_PIXEL_F32;
     if (int rc = p->ensure_spectrum(nimg)) return rc;
-    if (p->opt_normalise) {
+    if (p->score_planes()) {
         if (int rc = p->ND.ensure(g.map_elems() * (size_t)nimg)) return rc;
         if (int rc = p->NS64.ensure((size_t)2 * g.F * ncc_strip_columns(g.fft_h, g.fft_w, g.F, (int)p->norm_box_w, FC_NCC_SCRATCH_BYTES) * g.fft_h)) return rc;
     }
@@ -156,7 +156,7 @@ int launch_image_cols(fftconv_plan* p, const ImageRoute& r, const void* dimg, in
             HIP_TRY(launch_fast_cols_fwd(g.M, g.fast_cols.T, false, fa, p->num_cus, p->stream));
             break;
         }
-        const FastColsFwdArgs fk = kernels_fwd_args(g, p->d, p->opt_normalise ? p->KN.p : pd.dk, pd.kh, pd.kw, pd.na * g.F, p->A.p);
+        const FastColsFwdArgs fk = kernels_fwd_args(g, p->d, p->opt_score ? p->KN.p : pd.dk, pd.kh, pd.kw, pd.na * g.F, p->A.p);
         FC_VERBOSE(p, "image columns (%d tiles) and the columns of %d kernels (%d tiles) in one launch", fa.ntiles, pd.na, fk.ntiles);
         HIP_TRY(launch_fast_cols_fwd_pair(g.M, g.fast_cols.T, fa, fk, fast_cols_fwd_pruned_ok(g.fast_cols, pd.kh), p->num_cus, p->stream));
         p->a_holds.ready(pd);
@@ -176,7 +176,7 @@ int launch_window_statistics(fftconv_plan* p, const void* pixels, int format, in
                nimg, strip, (size_t)2 * g.F * strip * g.fft_h * sizeof(double));
     const size_t image_bytes = (size_t)g.F * g.H * g.W * fc_pixel_elem_bytes(format);
     for (int b = 0; b < nimg; b++)
-        HIP_TRY(launch_ncc_statistics_typed(static_cast<const char*>(pixels) + b * image_bytes, format, g.H, g.W, g.F, g.fft_h, g.fft_w,
+        HIP_TRY(launch_score_statistics_typed((int)p->opt_score, static_cast<const char*>(pixels) + b * image_bytes, format, g.H, g.W, g.F, g.fft_h, g.fft_w,
                                             (int)p->norm_box_h, (int)p->norm_box_w, p->NS64.p, strip, p->ND.p + (size_t)b * g.map_elems(), p->stream));
     return 0;
 }
@@ -222,7 +222,7 @@ int set_images_impl(fftconv_plan* p, const void* vdata, int fmt, int nimg, int l
     if (r.flush_first)
         if (int rc = flush_pending_prepare(p)) return rc;
     if (int rc = launch_image_cols(p, r, dimg, fmt, nimg, &pixels)) return rc;
-    if (p->opt_normalise)
+    if (p->score_planes())
         if (int rc = launch_window_statistics(p, pixels, r.stats_format, nimg)) return rc;
     if (r.pinned)
         if (int rc = p->pin_img.mark(p->stream)) return rc;      // the column pass, the copy or the statistics: the last reader
@@ -264,7 +264,7 @@ int fftconv_plan_spectrum(fftconv_plan* plan, void** device_ptr, size_t* bytes) 
 
 static int spectrum_exchange(fftconv_plan* p, float* spectrum, int location, bool to_natural) {
     if (!p || !spectrum) return api_fail(FFTCONV_ERR_INVALID_ARG, "NULL argument");
-    if (!to_natural && p->opt_normalise)
+    if (!to_natural && p->score_planes())
         return api_fail(FFTCONV_ERR_INVALID_ARG, "normalisation is on (fftconv_plan_set_normalisation): an imported spectrum carries no window statistics");
     if (!to_natural && p->border_mode)
         return api_fail(FFTCONV_ERR_INVALID_ARG, "a border is on (fftconv_plan_set_border, mode %ld): an imported spectrum carries no border", p->border_mode);
@@ -330,7 +330,7 @@ int fftconv_plan_use_spectrum_buffer(fftconv_plan* plan, void* device_ptr, size_
 
 int fftconv_plan_mark_spectrum_valid(fftconv_plan* plan) {
     if (!plan) return api_fail(FFTCONV_ERR_INVALID_ARG, "plan is NULL");
-    if (plan->opt_normalise)
+    if (plan->score_planes())
         return api_fail(FFTCONV_ERR_INVALID_ARG, "normalisation is on (fftconv_plan_set_normalisation): a spectrum written by the caller carries no window statistics");
     if (plan->border_mode)
         return api_fail(FFTCONV_ERR_INVALID_ARG, "a border is on (fftconv_plan_set_border, mode %ld): a spectrum written by the caller carries no border", plan->border_mode);

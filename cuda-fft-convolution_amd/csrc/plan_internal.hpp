@@ -33,6 +33,7 @@
 
 // default of plan option "norm_store": fused -- it beat the staged route beyond the spread of alternating runs at both geometries
 // measured (cfg3's with 64 maps: 3.90 against 4.98 ms per convolve; cfg2's with 16: 107 against 125 us; profiles/ncc_ab.txt)
+// (score 4's additive store by the same rule: 3.96 against 4.97 ms and 103 against 121 us; profiles/match_score_ab.txt)
 constexpr long FC_NORM_STORE_DEFAULT = 1;
 // default of plan option "pixel_store" (typed image pixels, fftconv_plan_set_images_typed): direct -- the conversion in the column
 // kernel's load (profiles/pixel_format_ab.txt)
@@ -256,8 +257,9 @@ struct fftconv_plan {
     // "rect_store" 1: the specialised output kernel stores the rectangle of region 5 itself (fast_cols.hpp: RECT) where it can --
     // rect_direct(); 0, and every plan it cannot serve: the window goes through the fp32 staging O and is cropped like regions 1-3
     long opt_rect_store = 1;
-    // (normalised maps are scaled while the staged window is cropped: never direct)
-    bool rect_direct() const { return opt_region == 5 && opt_rect_store && !opt_normalise && !tiled && fast_cols_rect_available(g.M, g.y_tiled()); }
+    // (maps of a score with a plane are combined while the staged window is cropped: never direct; score 2 is a kernel preparation
+    //  and nothing else, its maps leave as raw maps do)
+    bool rect_direct() const { return opt_region == 5 && opt_rect_store && !score_has_plane(opt_score) && !tiled && fast_cols_rect_available(g.M, g.y_tiled()); }
     // "image_walk" 1: a spectral-row launch of more than one image runs the kernel that keeps the transformed KERNEL row in
     // registers and walks over images (fast_rows_images.hpp) where the plan has it -- image_walk_active(); 0 (default), and
     // every plan it cannot serve: the walk over kernels.  Nothing cached depends on it.
@@ -274,12 +276,18 @@ struct fftconv_plan {
     // (16-bit maps, "output_region" 1-4, generic / Bluestein / kernel_path 1 or 2 output kernels, configurations that are not
     // built): STAGED -- the output kernel stores the fp32 window into O as for a cropped region, and the crop / pad kernel
     // multiplies by D at the window coordinate on the way into the maps (kernels_ncc.hip).
-    long opt_normalise = 0, norm_box_h = 0, norm_box_w = 0;
+    // fftconv_plan_set_match_score: ONE state for both entries -- opt_score is FC_SCORE_* (fc_common.hpp; 1 is the mode 1 above, which
+    // fftconv_plan_set_normalisation sets), over the same box.  Every score != 0 prepares the kernels into KN; the scores with a
+    // plane (1, 3, 4: score_has_plane) fill ND -- D, Dc = E^(-1/2) or Q = E -- and combine in the output kernel's store (1, 3: NORM,
+    // 4: ADD) or in the staged crop, as described above.  KC: the constants c_k = (float) t2 of the kernels in KN, written with
+    // them by the same launch (score 4 reads them), so they are found wherever KN's column spectra are.
+    long opt_score = 0, norm_box_h = 0, norm_box_w = 0;
     long opt_norm_store = FC_NORM_STORE_DEFAULT;
+    bool score_planes() const { return score_has_plane(opt_score); }
     bool norm_direct() const {
-        return fast_cols_norm_direct(opt_normalise != 0, opt_norm_store != 0, tiled != nullptr, (int)opt_map_format, opt_region, g.M, g.y_tiled());
+        return fast_cols_score_direct((int)opt_score, opt_norm_store != 0, tiled != nullptr, (int)opt_map_format, opt_region, g.M, g.y_tiled());
     }
-    DevBuf<float> ND, KN;
+    DevBuf<float> ND, KN, KC;
     DevBuf<double> NS64;
     DevBuf<float> OC;  // cropped maps staged for the copy-out
     size_t out_elems() const { return opt_region ? (size_t)out_h * out_w : g.map_elems(); }   // (block-wise plans: g holds the whole window)
@@ -401,7 +409,7 @@ struct fftconv_plan {
         fr_tw1.release(); fr_tw2.release(); fr_map.release();
         fc_tw1.release(); fc_tw2.release(); fc_pairs.release(); fc_rowoff.release(); fc_pair_row_of.release();
         nat_row_of.release(); nat_col_of.release(); NS.release(); queue.release();
-        ND.release(); KN.release(); NS64.release();
+        ND.release(); KN.release(); KC.release(); NS64.release();
         pin_img.release(); pin_k.release(); pin_out.release();
         for (int h = 0; h < 2; h++) { if (pin_out_done[h]) (void)hipEventDestroy(pin_out_done[h]); pin_out_done[h] = nullptr; }
     }
@@ -449,9 +457,10 @@ int rows_threads(const Geometry& g);
 // the deferred kernel-column pass of fftconv_plan_prepare_kernels_packed, launched by itself on the stream it was recorded for
 int flush_pending_prepare(fftconv_plan* p);
 // the plan's "output_region" of nmaps full-window maps at src, compacted into dst: 4 pads to the pow2 window, the others crop
-// scale: normalised maps -- the scale planes D of the plan's images; map m of the launch belongs to image image0 + m / per_image
+// scale: maps of a score with a plane -- the planes of the plan's images (D, Dc: multiplied; Q: added with consts[m % per_image], the
+// constants of the launch's kernels); map m of the launch belongs to image image0 + m / per_image
 int launch_region(const fftconv_plan* p, const float* src, float* dst, int nmaps, hipStream_t s, const float* scale = nullptr, int image0 = 0,
-                  int per_image = 1);
+                  int per_image = 1, const float* consts = nullptr);
 // Core of the per-kernel loop for n kernels of one size, packed on the device at dk ([n][F][kw][kh]); on failure nothing of the
 // host-output ring is still writing into the caller's buffers when the error is returned
 int run_group(fftconv_plan* p, int n, const float* dk, int kh, int kw, const Sink& sink);
@@ -467,6 +476,8 @@ FastColsShape output_rect_shape(const fftconv_plan* p, const c32* y, float* out,
 // the launch that stores ny normalised maps (fftconv_plan::norm_direct) of the window or of the plan's rectangle: image-major from
 // image image0 on, per_image kernels each
 FastColsShape output_norm_shape(const fftconv_plan* p, const c32* y, float* out, int ny, int image0, int per_image);
+// ... of score 4: consts[0] is the constant of the launch's first kernel
+FastColsShape output_sqdiff_shape(const fftconv_plan* p, const c32* y, float* out, int ny, int image0, int per_image, const float* consts);
 
 // ---- host-output streaming (host_ring.cpp) ----
 // A streamed group (run_group, host maps of at least host_min_kb) has two staging buffers on the device: batch b is computed into

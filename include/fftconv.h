@@ -510,6 +510,43 @@ int fftconv_plan_set_output_rect(fftconv_plan *plan, int off_h, int off_w, int o
  * fftconv_plan_import_spectrum / fftconv_plan_mark_spectrum_valid (a spectrum carries no window statistics).
  * The one-shot and two-step entries, fftconv_multi_*, the plan cache and the MEX gateways do not take the option. */
 int fftconv_plan_set_normalisation(fftconv_plan *plan, int mode, int box_h, int box_w);
+/* Template-matching scores: the map of a kernel (template) T of F planes of box_h x box_w, n = box_h * box_w, as one of the scores
+ * a matcher chooses from.  ONE state with fftconv_plan_set_normalisation: mode 1 there is score 1 here, and either entry reads
+ * and replaces what the other set.  Notation: I is the zero-padded image; R(u) = sum_f (I_f (*) T_f)(u) is the plan's raw map --
+ * convolution, or correlation with "flip_kernels" 1; the scores below are then those of the flipped template, exactly as mode 1
+ * handles it; s2_f(u) is the float64 direct sum of I_f^2 over the box that ends at window position u (the sums and the fixed
+ * order of mode 1); E(u) = sum_f s2_f(u); t2 = sum_f sum T_f^2, taken in float64 in the fixed lane order of the kernel
+ * normalisation.
+ *   score                   value of a map                               kernel preparation           per-image plane     store
+ *   0 FFTCONV_SCORE_NONE          raw (as without this entry)                  none                         none                plain
+ *   1 FFTCONV_SCORE_CCOEFF_NORMED exactly mode 1 of fftconv_plan_set_normalisation   T''                    D                   x * D
+ *   2 FFTCONV_SCORE_CCOEFF        sum_f I_f (*) (T_f - mean(T_f))              centred per plane, not scaled   none             plain
+ *   3 FFTCONV_SCORE_CCORR_NORMED  R(u) * E(u)^(-1/2), and 0 where E(u) = 0     T / sqrt(t2) (not centred; all zeros where t2 = 0)
+ *                                                                                                       Dc = (float) E^(-1/2), 0 where E == 0   x * Dc
+ *   4 FFTCONV_SCORE_SQDIFF        E(u) - 2 R(u) + t2 = sum_f sum_box (I - T)^2  -2 * T (exact in fp32)       Q = (float) E       x + (Q(u) + c_k), c_k = (float) t2
+ * Score 2 equals OpenCV's TM_CCOEFF wherever the box lies inside the data (sum (I - mean_u I)(T - mean T) = sum I (T - mean T)).
+ * Score 3 has no relative floor: E is a sum of non-negative float64 terms, so it is exactly 0 if and only if every pixel under the
+ * box is 0, and otherwise it is accurate to a relative 2^-52.  Score 4 is always evaluated in one fixed order -- first s = Q + c_k,
+ * one fp32 add, then x + s, one fp32 add -- on every route.  Where no data lies under the box (the slack of the window behind
+ * DATA + box - 1) score 4 returns t2, the true sum of squared differences against zeros, and score 3 returns 0; what an
+ * "output_region" 4 adds beyond the window is 0, as for every map.
+ * The kernels are prepared on the device in float64 ahead of their transform, for every kernel location; the planes are computed
+ * once per image by fftconv_plan_set_image / _set_images beside the forward transform, as D is.  Score 2 is a kernel preparation
+ * and nothing else: no statistics, no plane, and its maps are delivered exactly as raw maps are ("rect_direct", 16-bit maps,
+ * regions; "norm_direct" reads 0).  Scores 3 and 4 are combined in the store of the specialised output kernel under the conditions
+ * of mode 1 (score 3 by mode 1's kernels with Dc in D's place; score 4 by kernels of its own, built for every transform but the
+ * 1088- and 4160-point ones) and in the staged crop / pad everywhere else; both routes return the same bits.  "norm_store" and
+ * "norm_direct" keep their meaning for every score.  plan_info.workspace_bytes counts the planes, the prepared kernels and their
+ * constants.
+ * The rules are those of fftconv_plan_set_normalisation, for every score, 2 included: a call that changes score or box leaves the
+ * plan without an image, one that changes nothing keeps it; while a score is on EVERY kernel must be exactly box_h x box_w.
+ * Read-only options: "match_score"; "normalise" (1 exactly when the score is 1); "norm_box_h", "norm_box_w" (the box of any score).
+ * FFTCONV_ERR_INVALID_ARG, the plan's state untouched: a bad score or box; a block-wise plan; a border being on (and
+ * fftconv_plan_set_border while any score is on); kernels of another size; fftconv_plan_import_spectrum /
+ * fftconv_plan_mark_spectrum_valid under scores 1, 3 and 4, which carry window statistics (allowed under 0 and 2).
+ * The one-shot and two-step entries, fftconv_multi_*, the plan cache and the MEX gateways do not take the option. */
+enum { FFTCONV_SCORE_NONE = 0, FFTCONV_SCORE_CCOEFF_NORMED = 1, FFTCONV_SCORE_CCOEFF = 2, FFTCONV_SCORE_CCORR_NORMED = 3, FFTCONV_SCORE_SQDIFF = 4 };
+int fftconv_plan_set_match_score(fftconv_plan *plan, int score, int box_h, int box_w);
 
 /* Border modes: what the image is beyond its data.  The library's own border is zero; a caller who wanted another one had to
  * write a padded copy of every image, plan for the padded size and crop the rim.  Here the border is never materialised: the
