@@ -195,7 +195,8 @@ static int tiled_deliver(fftconv_plan* p, float* big, int nk, int k0, bool more,
     const float* src = big;
     if (p->opt_region != 0) {
         float* dst = out_packed ? out_packed + (size_t)k0 * oe : ts->crop.p;
-        if (int rc = launch_region(p, big, dst, nk, sub->stream)) return rc;
+        // (the route of this plan's region: a block-wise plan never stores it densely itself and has no plane -- a plain crop or pad)
+        if (int rc = launch_region(p, plan_output_route(output_route_in(p, SinkKind::Packed)), big, dst, nk, sub->stream)) return rc;
         src = dst;
     } else if (out_packed) {
         return 0;

@@ -216,6 +216,15 @@ struct FastColsSqdiffArgs {
 };
 FC_HD bool fast_cols_sqdiff_args_ok(const FastColsSqdiffArgs& a) { return a.q && a.c && a.plane > 0 && a.pitch > 0 && a.first >= 0 && a.per_image >= 1; }
 
+// What the last phase of fast_cols_body stores (its template parameter STORE, described there), and the argument a store takes
+// beside FastColsArgs: the plane's device struct, or nothing (void)
+enum class ColStore { PAIRS, PAIRS16, RECT, RECT16, RECT_SCALE, RECT_ADD };
+template <ColStore S> struct ColStorePlane { using type = void; };
+template <> struct ColStorePlane<ColStore::RECT_SCALE> { using type = FastColsNormArgs; };
+template <> struct ColStorePlane<ColStore::RECT_ADD> { using type = FastColsSqdiffArgs; };
+template <class A>
+FC_HD const A* col_store_plane(const A& a) { return &a; }
+
 template <class C>
 struct ColState {
     c32x2 pre[C::UPT];   // gather of the next tile
@@ -299,11 +308,23 @@ FC_HD int pair_of_unit(int u) {
 // store (FastColsNormArgs, the body's last argument); the multiply is the only arithmetic added, and the store stays ONE predicated block per pair.
 // ADD (RECT, fp32 maps, never with NORM): matching score 4 -- a value pair becomes v + (q + c), q the pair of the plane Q at its
 // window coordinate and c the constant of the map's kernel (FastColsSqdiffArgs); the load sits where NORM's sits.
-template <class C, bool TILED, bool SLICED = false, bool DYN = false, bool OUT16 = false, bool RECT = false, bool NORM = false, bool ADD = false, class Ctx>
-FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int nwg, [[maybe_unused]] const FastColsNormArgs* nrm = nullptr,
-                          [[maybe_unused]] const FastColsSqdiffArgs* add = nullptr) {
-    static_assert(!NORM || (RECT && !OUT16), "the fused scale exists on the fp32 rectangle family");
-    static_assert(!ADD || (RECT && !OUT16 && !NORM), "the fused additive store exists on the fp32 rectangle family, without the scale");
+// STORE names what C4 stores, one of the six stores that exist -- the properties above in the combinations that are legal:
+//   PAIRS, PAIRS16             the window (or an OutWindow), a pair of rows per store: fp32, 16-bit (OUT16)
+//   RECT, RECT16               the dense rectangle: fp32, 16-bit (RECT, RECT + OUT16)
+//   RECT_SCALE, RECT_ADD       the fp32 rectangle times a scale plane (RECT + NORM), plus Q + c (RECT + ADD)
+// The last two take one more argument, the plane's device struct (FastColsNormArgs, FastColsSqdiffArgs); the others take none.
+template <class C, bool TILED, bool SLICED = false, bool DYN = false, ColStore STORE = ColStore::PAIRS, class Ctx, class... PlaneArgs>
+FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int nwg, const PlaneArgs&... plane_args) {
+    constexpr bool OUT16 = STORE == ColStore::PAIRS16 || STORE == ColStore::RECT16;
+    constexpr bool RECT = STORE != ColStore::PAIRS && STORE != ColStore::PAIRS16;
+    constexpr bool NORM = STORE == ColStore::RECT_SCALE, ADD = STORE == ColStore::RECT_ADD;
+    using Plane = typename ColStorePlane<STORE>::type;
+    static_assert(sizeof...(PlaneArgs) == (std::is_void_v<Plane> ? 0 : 1) && (std::is_same_v<Plane, PlaneArgs> && ...),
+                  "RECT_SCALE takes FastColsNormArgs, RECT_ADD FastColsSqdiffArgs, the other stores nothing");
+    [[maybe_unused]] const FastColsNormArgs* nrm = nullptr;
+    [[maybe_unused]] const FastColsSqdiffArgs* add = nullptr;
+    if constexpr (NORM) nrm = col_store_plane(plane_args...);
+    if constexpr (ADD) add = col_store_plane(plane_args...);
     static_assert(!RECT || (TILED && !SLICED), "the rectangle store exists for unsliced launches on the tiled intermediate");
     static_assert(!SLICED || TILED, "column slices exist for the tiled intermediate only");
     static_assert(!(SLICED && DYN), "the sliced tail round is dealt statically");

@@ -583,12 +583,26 @@ inline bool fast_cols_fwd_pair_queues_ok(const FastColsFwdArgs& a, const FastCol
 // (fast_cols_slice_plan), statically: that wins over the dynamic tile queue (fast_cols.hpp; chunks of one tile per workgroup
 // of an XCD), which the row-major intermediate ignores.
 enum class FastColsVariant { ROW_MAJOR, TILED, TILED_SLICED, TILED_DYN };
+// The plane a launch combines its maps with, on the host: the planes of the plan's images ([image][window column][pitch rows] fp32,
+// plane_elems apart) multiplied into the values (Scale: D, Dc) or added to them with the constant of the map's kernel (Add: Q and
+// consts, consts[0] the launch's first kernel).  Map m of the launch belongs to image (first + m) / per_image and, Add, takes
+// consts[(first + m) % per_image].  The rectangle family's launch fills the device argument structs of fast_cols.hpp from it
+// (fast_cols_norm_args, fast_cols_sqdiff_args); the crop / pad launchers of kernels.hpp take it as it is.
+enum class PlaneKind { None, Scale, Add };
+struct MapPlane {
+    PlaneKind kind = PlaneKind::None;
+    const float* plane = nullptr;
+    const float* consts = nullptr;
+    size_t plane_elems = 0;
+    int pitch = 0, first = 0, per_image = 0;
+};
+inline FastColsNormArgs fast_cols_norm_args(const MapPlane& p) { return {p.plane, p.plane_elems, p.pitch, p.first, p.per_image}; }
+inline FastColsSqdiffArgs fast_cols_sqdiff_args(const MapPlane& p) { return {p.plane, p.consts, p.plane_elems, p.pitch, p.first, p.per_image}; }
 struct FastColsShape {
     FastColsVariant variant;
     FastColsArgs a;
     int grid;
-    FastColsNormArgs n{};      // the fused scale of normalised maps only (fast_cols_norm_launch_shape below)
-    FastColsSqdiffArgs q{};    // the fused additive store of score 4 only (fast_cols_sqdiff_launch_shape below)
+    MapPlane plane{};          // the rectangle family's fused scale / additive store only (fast_cols_rect_launch_shape below)
 };
 inline FastColsShape fast_cols_launch_shape(int M, int T, const FastColsArgs& a, int want) {
     FastColsShape r{FastColsVariant::TILED_SLICED, a, 0};
@@ -627,8 +641,10 @@ inline bool fast_cols_rect_available(int M, bool y_tiled) { return y_tiled && fa
 // of the rectangle are launched (the others are never gathered or transformed); the pair store is kept where every pair of
 // rows is whole and aligned -- off_h, out_h, the map stride and the element offset of `out` from a pair boundary all even --
 // which is uniform over the launch.  The rectangle must lie inside the window (pipeline.hpp: output_rect_error).
-inline FastColsShape fast_cols_rect_launch_shape(int T, const FastColsArgs& a, int off_h, int off_w, int out_h, int out_w, int want) {
-    FastColsShape r{a.queue ? FastColsVariant::TILED_DYN : FastColsVariant::TILED, a, 0};
+// `plane`: the fused scale of normalised maps (fast_cols.hpp: NORM) or the fused additive store of score 4 (ADD) -- fp32 maps, the
+// rectangle the plan's or, on a plan without one, the whole window (which keeps the pair stores).
+inline FastColsShape fast_cols_rect_launch_shape(int T, const FastColsArgs& a, int off_h, int off_w, int out_h, int out_w, int want, const MapPlane& plane = {}) {
+    FastColsShape r{a.queue ? FastColsVariant::TILED_DYN : FastColsVariant::TILED, a, 0, plane};
     const int nk = a.tiles_per_kernel > 0 ? a.ntiles / a.tiles_per_kernel : 0;
     const int tile_lo = off_w / T, tile_hi = (off_w + out_w + T - 1) / T;
     r.a.h_lo = off_h; r.a.fft_h = off_h + out_h; r.a.out_pitch = out_h;
@@ -657,25 +673,6 @@ constexpr bool fast_cols_norm_built(int M) {
     return true;
 }
 inline bool fast_cols_norm_available(int M, bool y_tiled) { return y_tiled && fast_cols_lookup(M).ok && fast_cols_norm_built(M); }
-// Whether the output kernel itself scales the normalised maps of a plan with these settings (fftconv_plan::norm_direct, read-only
-// option "norm_direct"): mode 1 with "norm_store" 1 on a one-pass plan that stores fp32 maps of the window (region 0) or of the
-// caller's rectangle (region 5) and has the kernel.  Everything else is staged.
-inline bool fast_cols_norm_direct(bool normalise, bool norm_store, bool blockwise, int map_format, long region, int M, bool y_tiled) {
-    return normalise && norm_store && !blockwise && map_format == FC_MAP_F32 && (region == 0 || region == 5) && fast_cols_norm_available(M, y_tiled);
-}
-// The launch of nk normalised maps: fast_cols_rect_launch_shape of the rectangle (a plan without one: the whole window, which
-// keeps the pair stores) plus the scale planes d ([image][win_w][win_h]); the maps of the launch are image-major from image
-// image0 on with per_image kernels each (ncc.hpp: ncc_image_of)
-inline FastColsShape fast_cols_norm_launch_shape(int T, const FastColsArgs& a, int off_h, int off_w, int out_h, int out_w, int want, const float* d,
-                                                 int win_h, int win_w, int image0, int per_image) {
-    FastColsShape r = fast_cols_rect_launch_shape(T, a, off_h, off_w, out_h, out_w, want);
-    r.n.d = d;
-    r.n.plane = (size_t)win_h * win_w;
-    r.n.pitch = win_h;
-    r.n.first = image0 * per_image;
-    r.n.per_image = per_image;
-    return r;
-}
 
 // Fused additive store of matching score 4, SQDIFF (fast_cols.hpp: ADD; plan entry fftconv_plan_set_match_score): the fp32 rectangle
 // kernel stores v + (Q + c) -- the plane Q at the pair's window coordinate, c the constant of the map's kernel.  Built by the NORM
@@ -688,27 +685,7 @@ constexpr bool fast_cols_sqdiff_built(int M) {
     return true;
 }
 inline bool fast_cols_sqdiff_available(int M, bool y_tiled) { return y_tiled && fast_cols_lookup(M).ok && fast_cols_sqdiff_built(M); }
-// Whether the output kernel itself combines the maps of a plan with these settings (fftconv_plan::norm_direct for every score):
-// a score with a plane (1, 3: the NORM kernels; 4: the ADD kernels) under the conditions of fast_cols_norm_direct.  Scores 0 and 2
-// have nothing to combine.
-inline bool fast_cols_score_direct(int score, bool norm_store, bool blockwise, int map_format, long region, int M, bool y_tiled) {
-    if (score == FC_SCORE_SQDIFF)
-        return norm_store && !blockwise && map_format == FC_MAP_F32 && (region == 0 || region == 5) && fast_cols_sqdiff_available(M, y_tiled);
-    return fast_cols_norm_direct(score == FC_SCORE_CCOEFF_NORMED || score == FC_SCORE_CCORR_NORMED, norm_store, blockwise, map_format, region, M, y_tiled);
-}
-// The launch of nk score-4 maps: fast_cols_norm_launch_shape with the planes q in place of d, plus the constants c of the
-// per_image kernels of the launch (c[0]: the launch's first kernel)
-inline FastColsShape fast_cols_sqdiff_launch_shape(int T, const FastColsArgs& a, int off_h, int off_w, int out_h, int out_w, int want, const float* q,
-                                                   const float* c, int win_h, int win_w, int image0, int per_image) {
-    FastColsShape r = fast_cols_rect_launch_shape(T, a, off_h, off_w, out_h, out_w, want);
-    r.q.q = q;
-    r.q.c = c;
-    r.q.plane = (size_t)win_h * win_w;
-    r.q.pitch = win_h;
-    r.q.first = image0 * per_image;
-    r.q.per_image = per_image;
-    return r;
-}
+// (whether a group's maps take the fused store or the staged combination: output_route.hpp)
 
 struct FastColsTables {
     Plan1D plan;                   // radices (R1, R2, R3)

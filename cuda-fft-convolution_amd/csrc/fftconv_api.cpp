@@ -172,66 +172,6 @@ int flush_pending_prepare(fftconv_plan* p) {
 
 namespace {
 
-// How the maps of a group leave the device: decided once per group (plan_delivery), read by every step of the loop.
-enum class Route {
-    Packed,   // the caller's packed device buffer: the output kernel (or the crop kernel) writes there
-    Window,   // block plan of an overlap-save plan: the output kernel stores its window of the full maps (OutWindow)
-    Copies,   // staged on the device, then one copy per map on the plan's stream (device pointers; host maps no other route takes)
-    Pinned,   // small host maps: staged, a launch's maps come back in ONE copy into the plan's pinned buffer (deliver_pinned)
-    Ring,     // host maps of at least host_min_kb: two staging buffers, the copy-out of batch b overlaps the compute of batch b + 1
-};
-struct Delivery {
-    Route route = Route::Packed;
-    // a region other than the whole window: the output kernel writes the window into O, a crop
-    // kernel compacts the region into the destination (the caller's packed buffer or the staging OC)
-    bool cropped = false;
-    // the caller's rectangle, stored by the output kernel itself (fftconv_plan::rect_direct): no full window, no crop, no O
-    bool rect = false;
-    // normalised maps, decided once per group and read by the launch and its verbose line: fused -- the output kernel scales by D
-    // itself (fftconv_plan::norm_direct; delivered like `rect`: dense maps straight from the output kernel) -- or staged: scaled
-    // while the staged window is cropped (`cropped` is then set whatever the region)
-    bool norm = false, norm_fused = false;
-    DevBuf<float>* stage = nullptr;    // staged routes: where the maps wait for their copy (OC for region maps, else O)
-    size_t oe = 0;                     // elements per delivered map
-    size_t eb = sizeof(float);         // bytes per element ("map_format")
-    size_t mb() const { return oe * eb; }
-    int kernel_format = FC_MAP_F32;    // what the output kernel stores: the plan's format, or fp32 into the staging a crop reads
-    bool staged() const { return route == Route::Copies || route == Route::Pinned || route == Route::Ring; }
-};
-
-int plan_delivery(fftconv_plan* p, const Sink& sink, int nbY, Delivery& d) {
-    const Geometry& g = p->g;
-    if (sink.window && !g.fast_cols.ok) return api_fail(FFTCONV_ERR_INVALID_ARG, "an output window needs the specialised output kernel");
-    if (sink.window && p->opt_score) return api_fail(FFTCONV_ERR_INVALID_ARG, "an output window takes no normalisation");
-    d.rect = !sink.window && p->rect_direct();
-    d.norm = p->score_planes();
-    d.norm_fused = d.norm && !sink.window && p->norm_direct();
-    d.cropped = ((p->opt_region != 0 && !d.rect) || d.norm) && !d.norm_fused;
-    d.stage = (d.cropped || d.rect || d.norm_fused) ? &p->OC : &p->O;
-    d.oe = p->out_elems();
-    d.eb = p->elem_bytes();
-    d.kernel_format = d.cropped ? FC_MAP_F32 : (int)p->opt_map_format;
-    const size_t map_bytes = d.mb();
-    // host output: the ring for maps of at least host_min_kb (1 MiB).  Smaller ones leave by blocking copies on the plan's stream:
-    // the copy threads buy them nothing (a one-shot call would start and join them for a few hundred KB), and
-    // small destination buffers are heap neighbours that share pages, which the runtime pins in place from
-    // several threads at once.  A one-shot call on 92-KB maps died (SIGABRT / SIGSEGV, no message) about once
-    // in 50-100 runs of tests/test_gpu_parity.py::test_blockwise_one_shot_matches_oracle on some boxes of the
-    // pool and never on others; the cause was not isolated, these threads are what that call had to itself.
-    if (sink.window) d.route = Route::Window;
-    else if (sink.packed) d.route = Route::Packed;
-    else if (sink.location != FFTCONV_HOST) d.route = Route::Copies;
-    else if (p->opt_host_stream != 0 && map_bytes >= ((size_t)p->opt_host_min_kb << 10)) d.route = Route::Ring;
-    else if (p->opt_host_pinned && map_bytes <= FC_PIN_OUT_BYTES / 2) d.route = Route::Pinned;
-    else d.route = Route::Copies;
-    if (d.cropped)
-        if (int rc = p->O.ensure(g.map_elems() * nbY)) return rc;
-    if (d.staged())
-        if (int rc = d.stage->ensure(floats_for(d.oe * nbY * (d.route == Route::Ring ? 2 : 1), d.eb))) return rc;
-    if (d.route == Route::Ring) return ring_begin(p);
-    return 0;
-}
-
 // spectral rows of nb x nk maps: the nk column spectra at `a` times the spectra of the images [b0, b0 + nb), transformed along w into
 // the slots (b - b0) * nk + k of Y -- one launch, the image is a grid coordinate of the kernels (pipeline.hpp: rows_args_set_images;
 // fast_paths.hpp: rows_walk_3d, rows_walk_flat, rows_shift_to_image, rows_generic_slot)
@@ -268,124 +208,6 @@ int launch_spectral_rows_batch(fftconv_plan* p, const c32* a, int kw, int b0, in
     return p->prof_end();
 }
 
-const char* const kMapFormatNames[] = {"fp32", "fp16", "bf16"};      // FC_MAP_*
-
-}  // namespace
-
-namespace fc {
-// the launch that stores ny maps of the plan's rectangle (fftconv_plan::rect_direct) from the intermediate y, dense from `out` on
-FastColsShape output_rect_shape(const fftconv_plan* p, const c32* y, float* out, int ny, int format) {
-    const Geometry& g = p->g;
-    const FastColsArgs fa = fast_cols_args(g, p->d, y, out, p->out_elems(), ny, format);
-    return fast_cols_rect_launch_shape(g.fast_cols.T, fa, p->off_h, p->off_w, p->out_h, p->out_w,
-                                       persistent_want(g.fast_cols.lds_bytes, g.fast_cols.NT, p->num_cus));
-}
-FastColsShape output_norm_shape(const fftconv_plan* p, const c32* y, float* out, int ny, int image0, int per_image) {
-    const Geometry& g = p->g;
-    const bool rect = p->opt_region == 5;      // (else the whole window as the rectangle)
-    const FastColsArgs fa = fast_cols_args(g, p->d, y, out, p->out_elems(), ny, FC_MAP_F32);
-    return fast_cols_norm_launch_shape(g.fast_cols.T, fa, rect ? p->off_h : 0, rect ? p->off_w : 0, rect ? p->out_h : g.fft_h, rect ? p->out_w : g.fft_w,
-                                       persistent_want(g.fast_cols.lds_bytes, g.fast_cols.NT, p->num_cus), p->ND.p, g.fft_h, g.fft_w, image0, per_image);
-}
-FastColsShape output_sqdiff_shape(const fftconv_plan* p, const c32* y, float* out, int ny, int image0, int per_image, const float* consts) {
-    const Geometry& g = p->g;
-    const bool rect = p->opt_region == 5;
-    const FastColsArgs fa = fast_cols_args(g, p->d, y, out, p->out_elems(), ny, FC_MAP_F32);
-    return fast_cols_sqdiff_launch_shape(g.fast_cols.T, fa, rect ? p->off_h : 0, rect ? p->off_w : 0, rect ? p->out_h : g.fft_h, rect ? p->out_w : g.fft_w,
-                                         persistent_want(g.fast_cols.lds_bytes, g.fast_cols.NT, p->num_cus), p->ND.p, consts, g.fft_h, g.fft_w, image0, per_image);
-}
-}  // namespace fc
-
-namespace {
-
-// output columns of ny maps: Y transformed along h into the maps at obase (or into the window of an overlap-save block)
-// (rect: the dense maps of the plan's rectangle, stored by the output kernel itself -- Delivery::rect)
-// (consts: score 4 -- the constant of the launch's first kernel, KC at the kernel's place in the chunk)
-int launch_output_cols(fftconv_plan* p, const OutWindow* win, float* obase, int ny, int format, bool rect, bool norm_fused = false, int image0 = 0,
-                       int per_image = 1, const float* consts = nullptr) {
-    const Geometry& g = p->g;
-    if (int rc = p->prof_begin(PK_OUT_COLS, ny)) return rc;
-    if (norm_fused && p->opt_score == FC_SCORE_SQDIFF) {
-        const FastColsShape sh = output_sqdiff_shape(p, p->Y.p, obase, ny, image0, per_image, consts);
-        FC_VERBOSE(p, "output kernel: tiled rectangle plus Q + c (normalisation: fused SQDIFF), %d workgroups, fp32 elements, rows [%d, %d) of columns [%d, %d), images %d..",
-                   sh.grid, sh.a.h_lo, sh.a.fft_h, sh.a.rect_w_lo, sh.a.rect_w_lo + sh.a.rect_w_n, image0);
-        HIP_TRY(launch_fast_cols_sqdiff(g.M, g.fast_cols.T, sh, p->stream));
-    } else if (norm_fused && p->opt_score == FC_SCORE_CCORR_NORMED) {
-        const FastColsShape sh = output_norm_shape(p, p->Y.p, obase, ny, image0, per_image);
-        FC_VERBOSE(p, "output kernel: tiled rectangle scaled by Dc (normalisation: fused CCORR_NORMED), %d workgroups, fp32 elements, rows [%d, %d) of columns [%d, %d), images %d..",
-                   sh.grid, sh.a.h_lo, sh.a.fft_h, sh.a.rect_w_lo, sh.a.rect_w_lo + sh.a.rect_w_n, image0);
-        HIP_TRY(launch_fast_cols_norm(g.M, g.fast_cols.T, sh, p->stream));
-    } else if (norm_fused) {
-        const FastColsShape sh = output_norm_shape(p, p->Y.p, obase, ny, image0, per_image);
-        FC_VERBOSE(p, "output kernel: tiled rectangle scaled by D (normalisation: fused), %d workgroups, fp32 elements, rows [%d, %d) of columns [%d, %d), images %d..",
-                   sh.grid, sh.a.h_lo, sh.a.fft_h, sh.a.rect_w_lo, sh.a.rect_w_lo + sh.a.rect_w_n, image0);
-        HIP_TRY(launch_fast_cols_norm(g.M, g.fast_cols.T, sh, p->stream));
-    } else if (rect) {
-        const FastColsShape sh = output_rect_shape(p, p->Y.p, obase, ny, format);
-        FC_VERBOSE(p, "output kernel: tiled rectangle, %d workgroups, %s elements, rows [%d, %d) of columns [%d, %d)", sh.grid, kMapFormatNames[format],
-                   p->off_h, p->off_h + p->out_h, p->off_w, p->off_w + p->out_w);
-        HIP_TRY(launch_fast_cols_rect(g.M, g.fast_cols.T, sh, p->stream));
-    } else if (g.fast_cols.ok) {
-        FastColsArgs fa = fast_cols_args(g, p->d, p->Y.p, obase, win ? win->map_stride : g.map_elems(), ny, format);
-        if (win) {
-            fa.h_lo = win->h_lo; fa.fft_h = win->h_hi; fa.w_first = win->w_first; fa.out_pitch = win->pitch;
-            fa.tiles_per_kernel = win->ncols / g.fast_cols.T; fa.ntiles = fa.tiles_per_kernel * ny;
-        }
-        if (p->opt_verbose) {      // which instantiation the launch layer picks (fast_paths.hpp: fast_cols_launch_shape), and what it stores
-            static const char* const variants[] = {"row-major", "tiled", "tiled, sliced tail round", "tiled, dynamic tile queue"};
-            const FastColsShape sh = fast_cols_launch_shape(g.M, g.fast_cols.T, fa, persistent_want(g.fast_cols.lds_bytes, g.fast_cols.NT, p->num_cus));
-            FC_VERBOSE(p, "output kernel: %s intermediate, %d workgroups, %s elements", variants[(int)sh.variant], sh.grid, kMapFormatNames[format]);
-        }
-        HIP_TRY(launch_fast_cols(g.M, g.fast_cols.T, fa, p->num_cus, p->stream));
-    } else {
-        FC_VERBOSE(p, "output kernel: generic%s, %s elements", g.bluestein_h() ? " (chirp-z)" : "", kMapFormatNames[format]);
-        ColsC2RArgs ca = cols_c2r_args(g, p->t, p->d, p->Y.p, obase, g.map_elems(), format);
-        HIP_TRY(launch_cols_c2r(ca, tiles_for(g.fft_w, g.T_cols), ny, cols_threads(g), p->cols_lds(), p->stream));
-    }
-    return p->prof_end();
-}
-
-// Route::Pinned -- small maps to host arrays: as many as fit the plan's pinned buffer come back in ONE copy and are handed
-// out by the CPU (a copy into pageable memory is a blocking runtime call per map)
-// (two halves: the copy of the next chunk runs while the CPU hands out the current one; a single map above
-//  FC_PIN_ONE_MAP_BYTES takes the plain copy of deliver_batch: the CPU's pass over it costs more than the runtime's pinning --
-//  one 324-KiB map: 77 against 60 us per convolve, four of them: 131 against 166, profiles/r04s_small_call_latency.txt)
-int deliver_pinned(fftconv_plan* p, const Delivery& d, float* const* out, int ny) {
-    const size_t mb = d.mb();
-    const int per_copy = (int)std::min<size_t>((size_t)ny, (FC_PIN_OUT_BYTES / 2) / mb);
-    const int nchunks = (ny + per_copy - 1) / per_copy;
-    if (int rc = p->pin_out.ensure((size_t)per_copy * mb * (nchunks > 1 ? 2 : 1))) return rc;
-    for (int h = 0; h < 2; h++)
-        if (!p->pin_out_done[h]) HIP_TRY(hipEventCreateWithFlags(&p->pin_out_done[h], hipEventDisableTiming));
-    auto copy_chunk = [&](int c) -> hipError_t {
-        const int j0 = c * per_copy, nj = std::min(per_copy, ny - j0);
-        hipError_t e = hipMemcpyAsync(p->pin_out.p + (size_t)(c & 1) * per_copy * mb, map_at(d.stage->p, (size_t)j0 * d.oe, d.eb), (size_t)nj * mb,
-                                      hipMemcpyDeviceToHost, p->stream);
-        if (e == hipSuccess) e = hipEventRecord(p->pin_out_done[c & 1], p->stream);
-        return e;
-    };
-    HIP_TRY(copy_chunk(0));
-    for (int c = 0; c < nchunks; c++) {
-        if (c + 1 < nchunks) HIP_TRY(copy_chunk(c + 1));
-        HIP_TRY(hipEventSynchronize(p->pin_out_done[c & 1]));
-        const int j0 = c * per_copy, nj = std::min(per_copy, ny - j0);
-        for (int j = 0; j < nj; j++)
-            memcpy(out[j0 + j], p->pin_out.p + ((size_t)(c & 1) * per_copy + j) * mb, mb);
-    }
-    return 0;   // (the staging buffer is free again: its last copy has been waited for)
-}
-
-// the maps [first, first + ny) are queued into `dest` (staging buffer buf of a streamed group): their way to the caller
-int deliver_batch(fftconv_plan* p, const Delivery& d, const Sink& sink, int first, int ny, int buf, const float* dest) {
-    if (d.route == Route::Ring) return ring_batch_launched(p, sink, first, ny, buf, dest);
-    if (d.route == Route::Pinned && (ny > 1 || d.mb() <= FC_PIN_ONE_MAP_BYTES)) return deliver_pinned(p, d, sink.ptrs + first, ny);
-    if (!d.staged()) return 0;         // the kernels wrote where the caller reads
-    for (int j = 0; j < ny; j++)
-        HIP_TRY(hipMemcpyAsync(sink.ptrs[first + j], map_at(dest, (size_t)j * d.oe, d.eb), d.mb(), copy_kind(sink.location, false), p->stream));
-    if (sink.location == FFTCONV_HOST) HIP_TRY(hipStreamSynchronize(p->stream));
-    return 0;
-}
-
 // Core of the per-kernel loop (src/cudaConvolutionFFT.cu:204-291) for n kernels of one size,
 // packed on the device at dk ([n][F][kw][kh]).  Per batch of maps: kernel columns (once per chunk), spectral rows, the wait
 // for the staging buffer, output columns, crop or pad, then the batch's delivery.
@@ -409,10 +231,9 @@ int run_group_impl(fftconv_plan* p, int n, const float* dk, int kh, int kw, cons
         // (several images: no automatic tuning -- the tuner's probe launches are shaped for the maps of one image)
         // (normalised maps: no tuning -- the probe launches are the plain output kernel's, not the scaled launch the group runs; the
         //  allocation stays marked fresh, so the first group after fftconv_plan_set_normalisation(0) tunes it as a fresh plan's)
-        if (p->score_planes()) {}
+        if (d.r.probe == TuneProbe::Skip) {}
         else if (B > 1 && p->opt_tune_placement < 0) p->Y.fresh = false;
-        else if (int rc = tune_intermediate_placement(p, sink, n * B, nbY, d.cropped ? p->O.p : d.staged() ? d.stage->p : sink.packed, !d.cropped && !d.staged(), d.kernel_format))
-            return rc;
+        else if (int rc = tune_intermediate_placement(p, d.r, n * B, nbY, d.r.need_O ? p->O.p : d.stage ? d.stage->p : sink.packed)) return rc;
     }
     LaunchCutter cutter(B, n, image_stride, nbA, nbY);
     for (LaunchRect l; cutter.next(l);) {
@@ -430,18 +251,18 @@ int run_group_impl(fftconv_plan* p, int n, const float* dk, int kh, int kw, cons
                        route.image_walk ? "images" : "maps", g.fast_cols.ok ? "specialised" : "generic", g.M, g.fast_cols.ok ? g.fast_cols.T : g.T_cols);
             if (int rc = launch_spectral_rows_batch(p, p->A.p + (size_t)(l.k0 - l.a0) * bs.per_a, kw, l.b0, l.nb, l.nk, route)) return rc;
             int buf = 0;
-            if (d.route == Route::Ring)
+            if (d.r.route == Route::Ring)
                 if (int rc = ring_claim_staging(p, &buf)) return rc;
             float* dest = sink.window ? sink.window->base + (size_t)first * sink.window->map_stride            // where the maps of this batch go
-                          : d.staged() ? map_at(d.stage->p, (size_t)buf * nbY * d.oe, d.eb) : map_at(sink.packed, (size_t)first * d.oe, d.eb);
-            const float* consts = p->KC.p ? p->KC.p + (l.k0 - l.a0) : nullptr;      // (KC holds the chunk's kernels, as A does)
-            if (int rc = launch_output_cols(p, sink.window, d.cropped ? p->O.p : dest, ny, d.kernel_format, d.rect, d.norm_fused, l.b0, l.nk, consts)) return rc;
-            if (d.cropped)
-                if (int rc = launch_region(p, p->O.p, dest, ny, p->stream, d.norm ? p->ND.p : nullptr, l.b0, l.nk, consts)) return rc;
+                          : d.stage ? map_at(d.stage->p, (size_t)buf * nbY * d.oe, d.eb) : map_at(sink.packed, (size_t)first * d.oe, d.eb);
+            const OutLaunch ol{l.b0, l.nk, p->KC.p ? p->KC.p + (l.k0 - l.a0) : nullptr};      // (KC holds the chunk's kernels, as A does)
+            if (int rc = launch_output_cols(p, d.r, sink.window, d.r.need_O ? p->O.p : dest, ny, ol)) return rc;
+            if (d.r.after != OutAfter::None)
+                if (int rc = launch_region(p, d.r, p->O.p, dest, ny, p->stream, ol)) return rc;
             if (int rc = deliver_batch(p, d, sink, first, ny, buf, dest)) return rc;
         }
     }
-    if (d.route == Route::Ring)
+    if (d.r.route == Route::Ring)
         if (int rc = ring_finish(p, sink)) return rc;
     FC_VERBOSE(p, "FFT done");                                        // src/cudaConvolutionFFT.cu:258
     return 0;
@@ -499,44 +320,6 @@ const LongOption* find_option(const char* name, unsigned not_flag) {
 }  // namespace
 
 namespace fc {
-
-int launch_region(const fftconv_plan* p, const float* src, float* dst, int nmaps, hipStream_t s, const float* scale, int image0, int per_image,
-                  const float* consts) {
-    const Geometry& g = p->g;      // (block-wise plans: g holds the whole window)
-    const int format = (int)p->opt_map_format;      // of dst; src is fp32
-    if (scale) {     // normalised maps: the same pass multiplies by D at the window coordinate; region 0 is the crop of the whole window
-        const int oh = p->opt_region ? p->out_h : g.fft_h, ow = p->opt_region ? p->out_w : g.fft_w;
-        const int fh = p->opt_region ? p->off_h : 0, fw = p->opt_region ? p->off_w : 0;
-        if (p->opt_score == FC_SCORE_SQDIFF) {
-            FC_VERBOSE(p, "normalisation: staged SQDIFF -- %d maps of images %d.. plus Q + c while %s from the fp32 window into %d x %d %s maps", nmaps, image0,
-                       p->opt_region == 4 ? "padded" : "cropped", oh, ow, kMapFormatNames[format]);
-            if (p->opt_region == 4)
-                HIP_TRY(launch_pad_maps_sqdiff(src, g.fft_h, g.fft_w, g.map_elems(), dst, oh, ow, p->out_elems(), nmaps, scale, consts, image0, per_image, s, format));
-            else
-                HIP_TRY(launch_crop_maps_sqdiff(src, g.fft_h, g.map_elems(), dst, oh, ow, p->out_elems(), fh, fw, nmaps, scale, consts, image0, per_image, s, format));
-            return 0;
-        }
-        if (p->opt_score == FC_SCORE_CCORR_NORMED)
-            FC_VERBOSE(p, "normalisation: staged CCORR_NORMED -- %d maps of images %d.. scaled by Dc while %s from the fp32 window into %d x %d %s maps", nmaps,
-                       image0, p->opt_region == 4 ? "padded" : "cropped", oh, ow, kMapFormatNames[format]);
-        else
-        FC_VERBOSE(p, "normalisation: staged -- %d maps of images %d.. scaled by D while %s from the fp32 window into %d x %d %s maps", nmaps, image0,
-                   p->opt_region == 4 ? "padded" : "cropped", oh, ow, kMapFormatNames[format]);
-        if (p->opt_region == 4)
-            HIP_TRY(launch_pad_maps_norm(src, g.fft_h, g.fft_w, g.map_elems(), dst, oh, ow, p->out_elems(), nmaps, scale, image0, per_image, s, format));
-        else
-            HIP_TRY(launch_crop_maps_norm(src, g.fft_h, g.map_elems(), dst, oh, ow, p->out_elems(), fh, fw, nmaps, scale, image0, per_image, s, format));
-        return 0;
-    }
-    if (p->opt_region == 5)
-        FC_VERBOSE(p, "output rectangle: %d maps cropped from the fp32 window, rows [%d, %d) of columns [%d, %d), into %s maps", nmaps, p->off_h,
-                   p->off_h + p->out_h, p->off_w, p->off_w + p->out_w, kMapFormatNames[format]);
-    else FC_VERBOSE(p, "output region %ld: %d maps %s from the fp32 window into %d x %d %s maps", p->opt_region, nmaps, p->opt_region == 4 ? "padded" : "cropped",
-               p->out_h, p->out_w, kMapFormatNames[format]);
-    if (p->opt_region == 4) HIP_TRY(launch_pad_maps(src, g.fft_h, g.fft_w, g.map_elems(), dst, p->out_h, p->out_w, p->out_elems(), nmaps, s, format));
-    else HIP_TRY(launch_crop_maps(src, g.fft_h, g.map_elems(), dst, p->out_h, p->out_w, p->out_elems(), p->off_h, p->off_w, nmaps, s, format));
-    return 0;
-}
 
 // run_group_impl + on failure: nothing of the host-output ring may still be writing into the
 // caller's buffers when the error is returned

@@ -132,17 +132,21 @@ __global__ void __launch_bounds__(256) k_pad_maps16(const float* __restrict__ sr
 
 }  // namespace
 
+// the plane of a crop / pad launch is filled in (fast_paths.hpp: MapPlane)
+static bool maps_plane_ok(const MapPlane& pl) {
+    if (pl.kind == PlaneKind::None) return true;
+    return pl.plane && pl.per_image >= 1 && pl.first >= 0 && pl.first % pl.per_image == 0 && (pl.kind != PlaneKind::Add || pl.consts);
+}
+
 hipError_t launch_pad_maps(const float* src, int src_h, int src_w, size_t src_map_stride, float* dst, int dst_h, int dst_w,
-                           size_t dst_map_stride, int nmaps, hipStream_t s, int format) {
+                           size_t dst_map_stride, int nmaps, hipStream_t s, int format, const MapPlane& plane) {
     if (nmaps <= 0 || dst_h <= 0 || dst_w <= 0) return hipSuccess;
-    if (format != FC_MAP_F32) {
-        hipLaunchKernelGGL(k_pad_maps16, dim3((unsigned)dst_w, (unsigned)nmaps), dim3(256), 0, s, src, src_h, src_w, src_map_stride,
-                           reinterpret_cast<uint16_t*>(dst), dst_h, dst_map_stride, format == FC_MAP_BF16 ? 1 : 0);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(k_pad_maps, dim3((unsigned)dst_w, (unsigned)nmaps), dim3(256), 0, s, src, src_h, src_w, src_map_stride, dst, dst_h,
-                       dst_map_stride);
-    return hipGetLastError();
+    if (!maps_plane_ok(plane) || (plane.kind != PlaneKind::None && dst_h < src_h)) return hipErrorInvalidValue;
+    const MapsLaunch l{src, src_h, src_w, src_map_stride, dst, dst_h, dst_w, dst_map_stride, 0, 0, nmaps, format, s};
+    if (plane.kind == PlaneKind::Scale) return pad_maps_scaled(l, plane);
+    if (plane.kind == PlaneKind::Add) return pad_maps_added(l, plane);
+    return l.run([&](dim3 g, dim3 b, uint16_t* d, int bf16) { hipLaunchKernelGGL(k_pad_maps16, g, b, 0, s, src, src_h, src_w, src_map_stride, d, dst_h, dst_map_stride, bf16); },
+                 [&](dim3 g, dim3 b, float* d, int) { hipLaunchKernelGGL(k_pad_maps, g, b, 0, s, src, src_h, src_w, src_map_stride, d, dst_h, dst_map_stride); });
 }
 
 hipError_t launch_spectrum_reorder(bool to_natural, c32* S, size_t s_plane, int s_pitch, c32* nat, int fw, int ch, int planes,
@@ -170,16 +174,14 @@ hipError_t launch_add_window(float* dst, int dst_h, int dst_w, size_t dst_map_st
 }
 
 hipError_t launch_crop_maps(const float* src, int src_h, size_t src_map_stride, float* dst, int dst_h, int dst_w, size_t dst_map_stride,
-                            int off_h, int off_w, int nmaps, hipStream_t s, int format) {
+                            int off_h, int off_w, int nmaps, hipStream_t s, int format, const MapPlane& plane) {
     if (nmaps <= 0 || dst_h <= 0 || dst_w <= 0) return hipSuccess;
-    if (format != FC_MAP_F32) {
-        hipLaunchKernelGGL(k_crop_maps16, dim3((unsigned)dst_w, (unsigned)nmaps), dim3(256), 0, s, src, src_h, src_map_stride,
-                           reinterpret_cast<uint16_t*>(dst), dst_h, dst_w, dst_map_stride, off_h, off_w, format == FC_MAP_BF16 ? 1 : 0);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(k_crop_maps, dim3((unsigned)dst_w, (unsigned)nmaps), dim3(256), 0, s, src, src_h, src_map_stride, dst, dst_h, dst_w,
-                       dst_map_stride, off_h, off_w);
-    return hipGetLastError();
+    if (!maps_plane_ok(plane)) return hipErrorInvalidValue;
+    const MapsLaunch l{src, src_h, 0, src_map_stride, dst, dst_h, dst_w, dst_map_stride, off_h, off_w, nmaps, format, s};
+    if (plane.kind == PlaneKind::Scale) return crop_maps_scaled(l, plane);
+    if (plane.kind == PlaneKind::Add) return crop_maps_added(l, plane);
+    return l.run([&](dim3 g, dim3 b, uint16_t* d, int bf16) { hipLaunchKernelGGL(k_crop_maps16, g, b, 0, s, src, src_h, src_map_stride, d, dst_h, dst_w, dst_map_stride, off_h, off_w, bf16); },
+                 [&](dim3 g, dim3 b, float* d, int) { hipLaunchKernelGGL(k_crop_maps, g, b, 0, s, src, src_h, src_map_stride, d, dst_h, dst_w, dst_map_stride, off_h, off_w); });
 }
 
 // ---- the specialised kernels: their translation units (kernels_*_g<G>.hip) hold one group of configurations each; the
@@ -221,23 +223,18 @@ hipError_t launch_fast_cols(int M, int T, const FastColsArgs& a, int num_cus, hi
 hipError_t launch_fast_cols_rect(int M, int T, const FastColsShape& shape, hipStream_t s) {
     if (shape.a.ntiles <= 0) return hipSuccess;
     if (!shape.a.y_tiled || (shape.variant != FastColsVariant::TILED && shape.variant != FastColsVariant::TILED_DYN)) return hipErrorInvalidValue;
-    if (shape.a.out_format != FC_MAP_F32)
-        return in_first_group<FC_COL_GROUPS>([&](auto g) { return launch_fast_cols_rect16_group<g.value>(M, T, shape, s); });
+    const bool f32 = shape.a.out_format == FC_MAP_F32;
+    const MapPlane& pl = shape.plane;
+    if (pl.kind == PlaneKind::Scale) {
+        if (!f32 || !pl.plane || pl.per_image < 1) return hipErrorInvalidValue;
+        return in_first_group<FC_COL_GROUPS>([&](auto g) { return launch_fast_cols_rect_scale_group<g.value>(M, T, shape, s); });
+    }
+    if (pl.kind == PlaneKind::Add) {
+        if (!f32 || !fast_cols_sqdiff_args_ok(fast_cols_sqdiff_args(pl))) return hipErrorInvalidValue;
+        return in_first_group<FC_COL_GROUPS>([&](auto g) { return launch_fast_cols_rect_add_group<g.value>(M, T, shape, s); });
+    }
+    if (!f32) return in_first_group<FC_COL_GROUPS>([&](auto g) { return launch_fast_cols_rect16_group<g.value>(M, T, shape, s); });
     return in_first_group<FC_COL_GROUPS>([&](auto g) { return launch_fast_cols_rect_group<g.value>(M, T, shape, s); });
-}
-
-hipError_t launch_fast_cols_norm(int M, int T, const FastColsShape& shape, hipStream_t s) {
-    if (shape.a.ntiles <= 0) return hipSuccess;
-    if (!shape.a.y_tiled || (shape.variant != FastColsVariant::TILED && shape.variant != FastColsVariant::TILED_DYN)) return hipErrorInvalidValue;
-    if (shape.a.out_format != FC_MAP_F32 || !shape.n.d || shape.n.per_image < 1) return hipErrorInvalidValue;
-    return in_first_group<FC_COL_GROUPS>([&](auto g) { return launch_fast_cols_norm_group<g.value>(M, T, shape, s); });
-}
-
-hipError_t launch_fast_cols_sqdiff(int M, int T, const FastColsShape& shape, hipStream_t s) {
-    if (shape.a.ntiles <= 0) return hipSuccess;
-    if (!shape.a.y_tiled || (shape.variant != FastColsVariant::TILED && shape.variant != FastColsVariant::TILED_DYN)) return hipErrorInvalidValue;
-    if (shape.a.out_format != FC_MAP_F32 || !fast_cols_sqdiff_args_ok(shape.q)) return hipErrorInvalidValue;
-    return in_first_group<FC_COL_GROUPS>([&](auto g) { return launch_fast_cols_sqdiff_group<g.value>(M, T, shape, s); });
 }
 
 hipError_t launch_fast_cols_fwd(int M, int T, bool pruned, const FastColsFwdArgs& a, int num_cus, hipStream_t s) {

@@ -19,14 +19,42 @@ hipError_t launch_add_window(float* dst, int dst_h, int dst_w, size_t dst_map_st
                              int src_w, size_t src_map_stride, int nmaps, hipStream_t s);
 // dst[map] (dst_h x dst_w, contiguous) = window of src[map] at (off_h, off_w); src has src_h rows per column
 // (format: FC_MAP_* of dst -- a 16-bit dst is an opaque pointer whose stride counts 2-byte elements; src is fp32 whatever the format)
+// (plane: every element is combined with the plane at its WINDOW coordinate on the way -- Scale: times D; Add: s + (Q + c), c =
+//  consts[m % per_image] for map m of the launch -- the planes [image][src_w][src_h], src_map_stride apart; map m belongs to image
+//  first / per_image + m / per_image, first a multiple of per_image.  The kernels: kernels_ncc.hip (Scale), kernels_score.hip (Add))
 hipError_t launch_crop_maps(const float* src, int src_h, size_t src_map_stride, float* dst, int dst_h, int dst_w, size_t dst_map_stride,
-                            int off_h, int off_w, int nmaps, hipStream_t s, int format = FC_MAP_F32);
+                            int off_h, int off_w, int nmaps, hipStream_t s, int format = FC_MAP_F32, const MapPlane& plane = {});
 // natural [f][fw][ch] <-> internal image-spectrum order (see kernels.hip: k_spectrum_reorder)
 hipError_t launch_spectrum_reorder(bool to_natural, c32* S, size_t s_plane, int s_pitch, c32* nat, int fw, int ch, int planes,
                                    const int* row_of, const int* col_of, float scale, hipStream_t s);
-// dst[map] (dst_h x dst_w >= src) = src[map] in the top-left corner, zero elsewhere
+// dst[map] (dst_h x dst_w >= src) = src[map] in the top-left corner, zero elsewhere (format, plane: as launch_crop_maps)
 hipError_t launch_pad_maps(const float* src, int src_h, int src_w, size_t src_map_stride, float* dst, int dst_h, int dst_w,
-                           size_t dst_map_stride, int nmaps, hipStream_t s, int format = FC_MAP_F32);
+                           size_t dst_map_stride, int nmaps, hipStream_t s, int format = FC_MAP_F32, const MapPlane& plane = {});
+// One crop or pad launch as its unit's entry takes it -- the kernels of the three combinations live in three units (kernels.hip,
+// kernels_ncc.hip, kernels_score.hip), so that each unit compiles the device code it always did: launch_crop_maps / launch_pad_maps
+// check the arguments and pick the entry, the entry launches its kernel for the element class (pad: off_h, off_w unused)
+struct MapsLaunch {
+    const float* src;
+    int src_h, src_w;
+    size_t src_map_stride;
+    float* dst;
+    int dst_h, dst_w;
+    size_t dst_map_stride;
+    int off_h, off_w, nmaps, format;
+    hipStream_t s;
+    // k16 / k32(grid, block, dst as the kernel takes it, bf16): the fp32 and the 16-bit launch of a crop or pad kernel, written once
+    template <class K16, class K32>
+    hipError_t run(K16&& k16, K32&& k32) const {
+        const dim3 grid((unsigned)dst_w, (unsigned)nmaps), block(256);
+        if (format != FC_MAP_F32) k16(grid, block, reinterpret_cast<uint16_t*>(dst), format == FC_MAP_BF16 ? 1 : 0);
+        else k32(grid, block, dst, 0);
+        return hipGetLastError();
+    }
+};
+hipError_t crop_maps_scaled(const MapsLaunch& l, const MapPlane& plane);      // kernels_ncc.hip
+hipError_t pad_maps_scaled(const MapsLaunch& l, const MapPlane& plane);
+hipError_t crop_maps_added(const MapsLaunch& l, const MapPlane& plane);       // kernels_score.hip
+hipError_t pad_maps_added(const MapsLaunch& l, const MapPlane& plane);
 // ---- normalised cross-correlation maps (kernels_ncc.hip; ncc.hpp)
 // window statistics of ONE image ([f][W][H] at img): the fp32 plane D [fft_w][fft_h] at d, in strips of window columns --
 // scratch holds 2 * F * strip_cols * fft_h doubles (ncc_strip_columns)
@@ -40,12 +68,6 @@ void launch_ncc_column_sums_px(const void* img, const PixelLoad& px, int H, int 
                                double* c2, hipStream_t s);
 // dst = the n kernels at src ([n][F][plane_elems]) centred per plane and scaled to unit joint norm; stats: 2 * n * F doubles of scratch
 hipError_t launch_ncc_unit_kernels(const float* src, float* dst, int n, int F, int plane_elems, double* stats, hipStream_t s);
-// launch_crop_maps / launch_pad_maps with every element scaled by D ([image][src_w][src_h], images src_map_stride apart) at its
-// window coordinate; map m of the launch belongs to image image0 + m / per_image
-hipError_t launch_crop_maps_norm(const float* src, int src_h, size_t src_map_stride, float* dst, int dst_h, int dst_w, size_t dst_map_stride,
-                                 int off_h, int off_w, int nmaps, const float* D, int image0, int per_image, hipStream_t s, int format = FC_MAP_F32);
-hipError_t launch_pad_maps_norm(const float* src, int src_h, int src_w, size_t src_map_stride, float* dst, int dst_h, int dst_w,
-                                size_t dst_map_stride, int nmaps, const float* D, int image0, int per_image, hipStream_t s, int format = FC_MAP_F32);
 // ---- the other matching scores (fftconv_plan_set_match_score; ncc.hpp): FC_SCORE_*
 // launch_ncc_statistics_typed for a score with a plane: 1 the call above, 3 Dc = E^(-1/2), 4 Q = E at d
 hipError_t launch_score_statistics_typed(int score, const void* img, int pixel_format, int H, int W, int F, int fft_h, int fft_w, int box_h, int box_w,
@@ -56,14 +78,6 @@ void launch_score_plane(int score, const double* c2, int ncols, int nout, int ff
 void launch_ncc_plane_stats(const float* src, int planes, int plane_elems, double* stats, hipStream_t s);
 // launch_ncc_unit_kernels for any score: 2 centred, 3 T / sqrt(t2), 4 -2 T; consts[k] = (float) t2 of kernel k (scores 2-4; n floats)
 hipError_t launch_score_kernels(int score, const float* src, float* dst, int n, int F, int plane_elems, double* stats, float* consts, hipStream_t s);
-// launch_crop_maps / launch_pad_maps of score 4: element s becomes s + (Q + c), Q ([image][src_w][src_h]) at its window coordinate,
-// c = consts[m % per_image] for map m of the launch
-hipError_t launch_crop_maps_sqdiff(const float* src, int src_h, size_t src_map_stride, float* dst, int dst_h, int dst_w, size_t dst_map_stride,
-                                   int off_h, int off_w, int nmaps, const float* Q, const float* consts, int image0, int per_image, hipStream_t s,
-                                   int format = FC_MAP_F32);
-hipError_t launch_pad_maps_sqdiff(const float* src, int src_h, int src_w, size_t src_map_stride, float* dst, int dst_h, int dst_w,
-                                  size_t dst_map_stride, int nmaps, const float* Q, const float* consts, int image0, int per_image, hipStream_t s,
-                                  int format = FC_MAP_F32);
 hipError_t launch_cols_r2c(const ColsR2CArgs& a, int tiles, int planes, int threads, size_t lds_bytes, hipStream_t s);
 hipError_t launch_rows_fwd(const RowsFwdArgs& a, int rows, int threads, size_t lds_bytes, hipStream_t s);
 // specialised forward image rows (fast_rows_fwd.hpp); hipErrorInvalidValue if L has no configuration
@@ -79,12 +93,11 @@ hipError_t fast_rows_multi_wgs_per_cu(int L, int nz2, const FastRowsArgs& a, int
 // (fast_paths.hpp: fast_rows_images_built)
 hipError_t launch_fast_rows_images(int L, const FastRowsArgs& a, int rows, int images_per_wg, hipStream_t s);
 hipError_t launch_fast_cols(int M, int T, const FastColsArgs& a, int num_cus, hipStream_t s);
-// the rectangle store of the output kernel (fast_cols.hpp: RECT): `shape` from fast_cols_rect_launch_shape (fast_paths.hpp)
+// the rectangle family of the output kernel (fast_cols.hpp: RECT, and on it NORM and ADD): `shape` from fast_cols_rect_launch_shape
+// (fast_paths.hpp) -- shape.plane picks the fused scale of normalised maps (Scale) or the fused additive store of score 4 (Add), both
+// fp32 only; without a plane the rectangle store in shape.a.out_format.  hipErrorInvalidValue for a launch the family does not have
+// (row-major or sliced), for a plane that is not filled in, and for a configuration whose kernel is not built (fast_cols_*_built)
 hipError_t launch_fast_cols_rect(int M, int T, const FastColsShape& shape, hipStream_t s);
-// the fused scale of normalised maps (fast_cols.hpp: NORM): `shape` from fast_cols_norm_launch_shape (fast_paths.hpp)
-hipError_t launch_fast_cols_norm(int M, int T, const FastColsShape& shape, hipStream_t s);
-// the fused additive store of score 4 (fast_cols.hpp: ADD): `shape` from fast_cols_sqdiff_launch_shape (fast_paths.hpp)
-hipError_t launch_fast_cols_sqdiff(int M, int T, const FastColsShape& shape, hipStream_t s);
 hipError_t launch_fast_cols_fwd(int M, int T, bool pruned, const FastColsFwdArgs& a, int num_cus, hipStream_t s);
 // image columns of typed pixels (kernels_cols_fwd_px_g<G>.hip; pixel_format.hpp): a.in holds elements of px.format, px from
 // fast_cols_fwd_pixel_load; hipErrorInvalidValue for fp32 pixels and for a configuration that is not built (fast_cols_fwd_px_built)
@@ -114,13 +127,13 @@ template <int G> GroupResult launch_fast_rows_images_group(int L, const FastRows
 template <int G> GroupResult launch_fast_cols_group(int M, int T, const FastColsArgs& a, int num_cus, hipStream_t s);
 // (the 16-bit-map instantiations of the same configurations: kernels_cols16_g<G>.hip)
 template <int G> GroupResult launch_fast_cols16_group(int M, int T, const FastColsArgs& a, int num_cus, hipStream_t s);
-// (the rectangle store, fp32 and 16-bit maps: kernels_cols_rect_g<G>.hip, kernels_cols_rect16_g<G>.hip)
+// (the rectangle family, all from kernels_cols_rect.inc: the store in fp32 and 16-bit maps -- kernels_cols_rect_g<G>.hip,
+//  kernels_cols_rect16_g<G>.hip -- the fused scale of normalised maps -- kernels_cols_norm_g<G>.hip -- and the fused additive store of
+//  score 4 -- kernels_cols_sqdiff_g<G>.hip; launch_fast_cols_rect picks among them)
 template <int G> GroupResult launch_fast_cols_rect_group(int M, int T, const FastColsShape& shape, hipStream_t s);
 template <int G> GroupResult launch_fast_cols_rect16_group(int M, int T, const FastColsShape& shape, hipStream_t s);
-// (the fused scale of normalised maps, fp32: kernels_cols_norm_g<G>.hip)
-template <int G> GroupResult launch_fast_cols_norm_group(int M, int T, const FastColsShape& shape, hipStream_t s);
-// (the fused additive store of score 4, fp32: kernels_cols_sqdiff_g<G>.hip)
-template <int G> GroupResult launch_fast_cols_sqdiff_group(int M, int T, const FastColsShape& shape, hipStream_t s);
+template <int G> GroupResult launch_fast_cols_rect_scale_group(int M, int T, const FastColsShape& shape, hipStream_t s);
+template <int G> GroupResult launch_fast_cols_rect_add_group(int M, int T, const FastColsShape& shape, hipStream_t s);
 template <int G> GroupResult launch_fast_cols_fwd_group(int M, int T, bool pruned, const FastColsFwdArgs& a, int num_cus, hipStream_t s);
 // (typed image pixels: kernels_cols_fwd_px_g<G>.hip)
 template <int G> GroupResult launch_fast_cols_fwd_px_group(int M, int T, const FastColsFwdArgs& a, const PixelLoad& px, int num_cus, hipStream_t s);

@@ -18,7 +18,7 @@ namespace {
 template <class Cfg, bool TILED, bool SLICED = false, bool DYN = false>
 __global__ void __launch_bounds__(Cfg::NT, 3) k_fast_cols16(FastColsArgs a) {
     DevPhaseCtx<std::conditional_t<TILED, ColPairState<Cfg>, ColState<Cfg>>> ctx;
-    fast_cols_body<Cfg, TILED, SLICED, DYN, true>(ctx, reinterpret_cast<c32*>(fc_smem), a, (int)blockIdx.x, (int)gridDim.x);
+    fast_cols_body<Cfg, TILED, SLICED, DYN, ColStore::PAIRS16>(ctx, reinterpret_cast<c32*>(fc_smem), a, (int)blockIdx.x, (int)gridDim.x);
 }
 #else
 #define FC_K_FAST_COLS k_fast_cols

@@ -1,4 +1,5 @@
 // kernels_cols_norm_g0.hip -- output-column kernels with the fused scale of normalised maps (fftconv_plan_set_normalisation), fp32 maps,
 // configurations of group 0 of fast_paths.hpp (one translation unit per kernel family and group: they compile in parallel, and each defines its group's entry points).
 #define FC_TU_GROUP 0
-#include "kernels_cols_norm.inc"
+#define FC_TU_NORM 1
+#include "kernels_cols_rect.inc"

@@ -1,4 +1,5 @@
 // kernels_cols_sqdiff_g1.hip -- output-column kernels with the fused additive store of matching score 4 (fftconv_plan_set_match_score), fp32 maps,
 // configurations of group 1 of fast_paths.hpp (one translation unit per kernel family and group: they compile in parallel, and each defines its group's entry points).
 #define FC_TU_GROUP 1
-#include "kernels_cols_sqdiff.inc"
+#define FC_TU_SQDIFF 1
+#include "kernels_cols_rect.inc"

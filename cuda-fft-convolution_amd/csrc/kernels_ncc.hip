@@ -1,6 +1,6 @@
 // kernels_ncc.hip -- normalised cross-correlation maps (fftconv_plan_set_normalisation; ncc.hpp): the window statistics of an
 // image (once per image), the normalisation of the kernels (once per kernel), and the crop / pad kernels that scale a staged
-// fp32 window by D on its way into the maps.  None of the first two is on the hot path.
+// fp32 window by D on its way into the maps (the Scale plane of launch_crop_maps / launch_pad_maps).  None of the first two is on the hot path.
 #include "kernels.hpp"
 #include "ncc.hpp"
 #include "ncc_device.hpp"
@@ -132,32 +132,23 @@ void launch_ncc_plane_stats(const float* src, int planes, int plane_elems, doubl
     hipLaunchKernelGGL(k_ncc_plane_stats, dim3((unsigned)planes), dim3(FC_NCC_LANES), 0, s, src, plane_elems, stats);
 }
 
-hipError_t launch_crop_maps_norm(const float* src, int src_h, size_t src_map_stride, float* dst, int dst_h, int dst_w, size_t dst_map_stride,
-                                 int off_h, int off_w, int nmaps, const float* D, int image0, int per_image, hipStream_t s, int format) {
-    if (nmaps <= 0 || dst_h <= 0 || dst_w <= 0) return hipSuccess;
-    if (!D || per_image < 1) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)dst_w, (unsigned)nmaps);
-    if (format != FC_MAP_F32)
-        hipLaunchKernelGGL(k_crop_maps_norm<true>, grid, dim3(256), 0, s, src, src_h, src_map_stride, reinterpret_cast<uint16_t*>(dst), dst_h,
-                           dst_map_stride, off_h, off_w, D, image0, per_image, format == FC_MAP_BF16 ? 1 : 0);
-    else
-        hipLaunchKernelGGL(k_crop_maps_norm<false>, grid, dim3(256), 0, s, src, src_h, src_map_stride, dst, dst_h, dst_map_stride, off_h, off_w, D,
-                           image0, per_image, 0);
-    return hipGetLastError();
+// the Scale entries of launch_crop_maps / launch_pad_maps (kernels.hpp: the arguments are checked there)
+hipError_t crop_maps_scaled(const MapsLaunch& l, const MapPlane& pl) {
+    const int image0 = pl.first / pl.per_image;
+    auto launch = [&](auto kernel, dim3 g, dim3 b, auto* d, int bf16) {
+        hipLaunchKernelGGL(kernel, g, b, 0, l.s, l.src, l.src_h, l.src_map_stride, d, l.dst_h, l.dst_map_stride, l.off_h, l.off_w, pl.plane, image0, pl.per_image, bf16);
+    };
+    return l.run([&](dim3 g, dim3 b, uint16_t* d, int bf16) { launch(k_crop_maps_norm<true>, g, b, d, bf16); },
+                 [&](dim3 g, dim3 b, float* d, int bf16) { launch(k_crop_maps_norm<false>, g, b, d, bf16); });
 }
 
-hipError_t launch_pad_maps_norm(const float* src, int src_h, int src_w, size_t src_map_stride, float* dst, int dst_h, int dst_w,
-                                size_t dst_map_stride, int nmaps, const float* D, int image0, int per_image, hipStream_t s, int format) {
-    if (nmaps <= 0 || dst_h <= 0 || dst_w <= 0) return hipSuccess;
-    if (!D || per_image < 1 || dst_h < src_h) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)dst_w, (unsigned)nmaps);
-    if (format != FC_MAP_F32)
-        hipLaunchKernelGGL(k_pad_maps_norm<true>, grid, dim3(256), 0, s, src, src_h, src_w, src_map_stride, reinterpret_cast<uint16_t*>(dst), dst_h,
-                           dst_map_stride, D, image0, per_image, format == FC_MAP_BF16 ? 1 : 0);
-    else
-        hipLaunchKernelGGL(k_pad_maps_norm<false>, grid, dim3(256), 0, s, src, src_h, src_w, src_map_stride, dst, dst_h, dst_map_stride, D, image0,
-                           per_image, 0);
-    return hipGetLastError();
+hipError_t pad_maps_scaled(const MapsLaunch& l, const MapPlane& pl) {
+    const int image0 = pl.first / pl.per_image;
+    auto launch = [&](auto kernel, dim3 g, dim3 b, auto* d, int bf16) {
+        hipLaunchKernelGGL(kernel, g, b, 0, l.s, l.src, l.src_h, l.src_w, l.src_map_stride, d, l.dst_h, l.dst_map_stride, pl.plane, image0, pl.per_image, bf16);
+    };
+    return l.run([&](dim3 g, dim3 b, uint16_t* d, int bf16) { launch(k_pad_maps_norm<true>, g, b, d, bf16); },
+                 [&](dim3 g, dim3 b, float* d, int bf16) { launch(k_pad_maps_norm<false>, g, b, d, bf16); });
 }
 
 }  // namespace fc

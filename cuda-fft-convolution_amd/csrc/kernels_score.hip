@@ -76,34 +76,24 @@ hipError_t launch_score_kernels(int score, const float* src, float* dst, int n, 
     return hipGetLastError();
 }
 
-hipError_t launch_crop_maps_sqdiff(const float* src, int src_h, size_t src_map_stride, float* dst, int dst_h, int dst_w, size_t dst_map_stride,
-                                   int off_h, int off_w, int nmaps, const float* Q, const float* consts, int image0, int per_image, hipStream_t s,
-                                   int format) {
-    if (nmaps <= 0 || dst_h <= 0 || dst_w <= 0) return hipSuccess;
-    if (!Q || !consts || per_image < 1) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)dst_w, (unsigned)nmaps);
-    if (format != FC_MAP_F32)
-        hipLaunchKernelGGL(k_crop_maps_sqdiff<true>, grid, dim3(256), 0, s, src, src_h, src_map_stride, reinterpret_cast<uint16_t*>(dst), dst_h,
-                           dst_map_stride, off_h, off_w, Q, consts, image0, per_image, format == FC_MAP_BF16 ? 1 : 0);
-    else
-        hipLaunchKernelGGL(k_crop_maps_sqdiff<false>, grid, dim3(256), 0, s, src, src_h, src_map_stride, dst, dst_h, dst_map_stride, off_h, off_w, Q,
-                           consts, image0, per_image, 0);
-    return hipGetLastError();
+// the Add entries of launch_crop_maps / launch_pad_maps (kernels.hpp: the arguments are checked there)
+hipError_t crop_maps_added(const MapsLaunch& l, const MapPlane& pl) {
+    const int image0 = pl.first / pl.per_image;
+    auto launch = [&](auto kernel, dim3 g, dim3 b, auto* d, int bf16) {
+        hipLaunchKernelGGL(kernel, g, b, 0, l.s, l.src, l.src_h, l.src_map_stride, d, l.dst_h, l.dst_map_stride, l.off_h, l.off_w, pl.plane, pl.consts, image0,
+                           pl.per_image, bf16);
+    };
+    return l.run([&](dim3 g, dim3 b, uint16_t* d, int bf16) { launch(k_crop_maps_sqdiff<true>, g, b, d, bf16); },
+                 [&](dim3 g, dim3 b, float* d, int bf16) { launch(k_crop_maps_sqdiff<false>, g, b, d, bf16); });
 }
 
-hipError_t launch_pad_maps_sqdiff(const float* src, int src_h, int src_w, size_t src_map_stride, float* dst, int dst_h, int dst_w,
-                                  size_t dst_map_stride, int nmaps, const float* Q, const float* consts, int image0, int per_image, hipStream_t s,
-                                  int format) {
-    if (nmaps <= 0 || dst_h <= 0 || dst_w <= 0) return hipSuccess;
-    if (!Q || !consts || per_image < 1 || dst_h < src_h) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)dst_w, (unsigned)nmaps);
-    if (format != FC_MAP_F32)
-        hipLaunchKernelGGL(k_pad_maps_sqdiff<true>, grid, dim3(256), 0, s, src, src_h, src_w, src_map_stride, reinterpret_cast<uint16_t*>(dst), dst_h,
-                           dst_map_stride, Q, consts, image0, per_image, format == FC_MAP_BF16 ? 1 : 0);
-    else
-        hipLaunchKernelGGL(k_pad_maps_sqdiff<false>, grid, dim3(256), 0, s, src, src_h, src_w, src_map_stride, dst, dst_h, dst_map_stride, Q, consts,
-                           image0, per_image, 0);
-    return hipGetLastError();
+hipError_t pad_maps_added(const MapsLaunch& l, const MapPlane& pl) {
+    const int image0 = pl.first / pl.per_image;
+    auto launch = [&](auto kernel, dim3 g, dim3 b, auto* d, int bf16) {
+        hipLaunchKernelGGL(kernel, g, b, 0, l.s, l.src, l.src_h, l.src_w, l.src_map_stride, d, l.dst_h, l.dst_map_stride, pl.plane, pl.consts, image0, pl.per_image, bf16);
+    };
+    return l.run([&](dim3 g, dim3 b, uint16_t* d, int bf16) { launch(k_pad_maps_sqdiff<true>, g, b, d, bf16); },
+                 [&](dim3 g, dim3 b, float* d, int bf16) { launch(k_pad_maps_sqdiff<false>, g, b, d, bf16); });
 }
 
 }  // namespace fc

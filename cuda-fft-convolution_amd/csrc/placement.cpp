@@ -26,15 +26,17 @@ static int placement_auto_candidates(const fftconv_plan* p, size_t launch_map_by
 // freed.  The probes write into `out`, which the convolve that follows overwrites; they read the candidates as
 // allocated (the driver hands out zeroed memory).  Blocking (~70 ms), once per allocation: what FFTW calls
 // measuring at plan time.
-int tune_intermediate_placement(fftconv_plan* p, const Sink& sink, int n, int nbY, float* out, bool direct, int format) {
+int tune_intermediate_placement(fftconv_plan* p, const OutputRoute& route, int n, int nbY, float* out) {
     const Geometry& g = p->g;
     p->Y.fresh = false;
     // (an overlap-save block's window is a rectangle inside the maps, not what the probes would write: never tuned)
-    int k = sink.window ? 0 : (int)p->opt_tune_placement;
-    const size_t eb = fc_map_elem_bytes(format);      // of what the output kernel writes
-    // (a plan whose output kernel stores the caller's rectangle itself -- rect_direct -- is probed with exactly that launch:
-    // `out` is sized for the dense rectangles, full-window probes would overrun it)
-    const bool rect = !sink.window && p->rect_direct();
+    int k = route.probe == TuneProbe::None ? 0 : (int)p->opt_tune_placement;
+    const int format = route.kernel_format;           // of what the output kernel writes at `out` (fp32 into the full-window staging of a cropped region)
+    const size_t eb = fc_map_elem_bytes(format);
+    // (a route whose output kernel stores the caller's rectangle itself is probed with exactly that launch: `out` is sized for
+    // the dense rectangles, full-window probes would overrun it)
+    const bool rect = route.probe == TuneProbe::Rect;
+    const bool direct = route.target == OutBuffer::Caller;      // the output kernel writes the caller's packed maps, from `out` on
     if (k < 0) k = placement_auto_candidates(p, (size_t)std::min(nbY, n) * (rect ? p->out_elems() : g.map_elems()) * eb);
     // (direct: the call's batches write to out + first_map * stride, and every batch's destination is probed -- an 18-GB map
     // buffer spans several placement regions; otherwise one launch into the one staging buffer)
@@ -79,7 +81,7 @@ int tune_intermediate_placement(fftconv_plan* p, const Sink& sink, int n, int nb
             float* dest = map_at(out, (size_t)b * nbY * out_stride_per_map, eb);
             hipError_t e;
             if (rect) {
-                e = launch_fast_cols_rect(g.M, g.fast_cols.T, output_rect_shape(p, y.p, dest, ny, format), p->stream);
+                e = launch_fast_cols_rect(g.M, g.fast_cols.T, output_rect_shape(p, route, y.p, dest, ny), p->stream);
             } else {
                 FastColsArgs fa = fast_cols_args(g, p->d, y.p, dest, g.map_elems(), ny, format);
                 e = launch_fast_cols(g.M, g.fast_cols.T, fa, p->num_cus, p->stream);

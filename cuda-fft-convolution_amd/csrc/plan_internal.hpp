@@ -2,9 +2,12 @@
 // include/fftconv.h, its device / pinned buffers, and the internal entry points each unit offers the others.
 //   column_cache.hpp   what the column-spectrum buffer A holds between calls (KernelSet, ColumnCache): the one owner of that record
 //   image_route.hpp    the way of an image into a one-pass plan, decided once per call (ImageRoute, plan_image_route)
-//   fftconv_api.cpp    plan core: creation (plan_device_setup), the per-kernel loop (run_group: plan_delivery,
-//                      launch_spectral_rows_batch, launch_output_cols, deliver_batch), kernel preparation (prepare_kernels),
+//   output_route.hpp   the way of a group's maps out of a plan, decided once per group (OutputRoute, plan_output_route)
+//   fftconv_api.cpp    plan core: creation (plan_device_setup), the per-kernel loop (run_group: launch_kernel_cols,
+//                      launch_spectral_rows_batch, then the output stages), kernel preparation (prepare_kernels),
 //                      options (kLongOptions), two-step pair
+//   plan_output.cpp    output side of the plan core: plan_delivery (the OutputRoute and its buffers) and the stages that read it --
+//                      launch_output_cols, launch_region, deliver_batch
 //   plan_image.cpp     image side of the plan core: set_image / set_images / set_images_typed as a sequence of stages that read the
 //                      ImageRoute, the spectrum buffer and the spectrum exchange in the reference's order
 //   plan_cache.cpp     plan cache of the one-shot entries + fftconv_convolution_fft[_ex] (the MEX body)
@@ -29,6 +32,7 @@
 #include "image_route.hpp"
 #include "kernels.hpp"
 #include "ncc.hpp"
+#include "output_route.hpp"
 #include "pipeline.hpp"
 
 // default of plan option "norm_store": fused -- it beat the staged route beyond the spread of alternating runs at both geometries
@@ -159,9 +163,8 @@ int upload(DevBuf<T>& buf, const std::vector<T>& v, const T** slot = nullptr) {
 // CPU copies the caller's small arrays into / out of pinned buffers of the plan: an image or a kernel set of at most
 // FC_PIN_INPLACE_BYTES is then read by the column kernels IN PLACE over PCIe (no copy command at all), a larger one
 // (up to FC_PIN_IMAGE_BYTES) crosses in one asynchronous copy (both limits: image_route.hpp), and the maps of a launch come back
-// in ONE copy.  `busy` is recorded behind the last GPU work that reads the buffer; the next fill waits for it.
-constexpr size_t FC_PIN_OUT_BYTES = (size_t)8 << 20;
-constexpr size_t FC_PIN_ONE_MAP_BYTES = (size_t)64 << 10;
+// in ONE copy (FC_PIN_OUT_BYTES, FC_PIN_ONE_MAP_BYTES: output_route.hpp).  `busy` is recorded behind the last GPU work that reads
+// the buffer; the next fill waits for it.
 struct PinBuf {
     char* p = nullptr;
     size_t cap = 0;
@@ -210,6 +213,11 @@ struct PinBuf {
 #include "host_ring.hpp"
 
 struct TiledState;
+struct fftconv_plan;
+namespace fc {
+// what plan_output_route decides on for this plan as it stands and a sink of that kind (plan_output.cpp)
+OutputRouteIn output_route_in(const fftconv_plan* p, SinkKind sink);
+}
 
 // Where the block plan of an overlap-save block-wise plan stores its maps (Sink::window, built per block by tiled_convolve_save): rows
 // [h_lo, h_hi) of columns [w_first, w_first + ncols) of the block's circular result, row h of column w of map j at
@@ -255,11 +263,12 @@ struct fftconv_plan {
     long opt_region = 0;
     int out_h = 0, out_w = 0, off_h = 0, off_w = 0;
     // "rect_store" 1: the specialised output kernel stores the rectangle of region 5 itself (fast_cols.hpp: RECT) where it can --
-    // rect_direct(); 0, and every plan it cannot serve: the window goes through the fp32 staging O and is cropped like regions 1-3
-    long opt_rect_store = 1;
-    // (maps of a score with a plane are combined while the staged window is cropped: never direct; score 2 is a kernel preparation
+    // OutStore::Rect; 0, and every plan it cannot serve: the window goes through the fp32 staging O and is cropped like regions 1-3
+    // (output_route.hpp: a score with a plane takes the fused or the staged combination instead; score 2 is a kernel preparation
     //  and nothing else, its maps leave as raw maps do)
-    bool rect_direct() const { return opt_region == 5 && opt_rect_store && !score_has_plane(opt_score) && !tiled && fast_cols_rect_available(g.M, g.y_tiled()); }
+    long opt_rect_store = 1;
+    // read-only option "rect_direct": the store of the route of a sink that is not a window
+    bool rect_direct() const { return plan_output_route(output_route_in(this, SinkKind::Packed)).store == OutStore::Rect; }
     // "image_walk" 1: a spectral-row launch of more than one image runs the kernel that keeps the transformed KERNEL row in
     // registers and walks over images (fast_rows_images.hpp) where the plan has it -- image_walk_active(); 0 (default), and
     // every plan it cannot serve: the walk over kernels.  Nothing cached depends on it.
@@ -272,7 +281,7 @@ struct fftconv_plan {
     // ([b][fft_w][fft_h], written by set_image / set_images beside the forward transform), KN the normalised kernels T'' of the
     // chunk whose column spectra are in A -- the column pass reads them instead of the caller's -- NS64 the float64 scratch of both.
     // "norm_store" 1: the specialised output kernel multiplies by D itself ahead of its store (fast_cols.hpp: NORM) where it
-    // can -- norm_direct(): fp32 maps of the window or of a rectangle on a plan that has the kernel.  0, and everything else
+    // can -- OutputRoute::fused: fp32 maps of the window or of a rectangle on a plan that has the kernel.  0, and everything else
     // (16-bit maps, "output_region" 1-4, generic / Bluestein / kernel_path 1 or 2 output kernels, configurations that are not
     // built): STAGED -- the output kernel stores the fp32 window into O as for a cropped region, and the crop / pad kernel
     // multiplies by D at the window coordinate on the way into the maps (kernels_ncc.hip).
@@ -284,9 +293,8 @@ struct fftconv_plan {
     long opt_score = 0, norm_box_h = 0, norm_box_w = 0;
     long opt_norm_store = FC_NORM_STORE_DEFAULT;
     bool score_planes() const { return score_has_plane(opt_score); }
-    bool norm_direct() const {
-        return fast_cols_score_direct((int)opt_score, opt_norm_store != 0, tiled != nullptr, (int)opt_map_format, opt_region, g.M, g.y_tiled());
-    }
+    // read-only option "norm_direct": whether the route of a sink that is not a window combines in the output kernel's store
+    bool norm_direct() const { return plan_output_route(output_route_in(this, SinkKind::Packed)).fused(); }
     DevBuf<float> ND, KN, KC;
     DevBuf<double> NS64;
     DevBuf<float> OC;  // cropped maps staged for the copy-out
@@ -456,11 +464,6 @@ int cols_threads(const Geometry& g);
 int rows_threads(const Geometry& g);
 // the deferred kernel-column pass of fftconv_plan_prepare_kernels_packed, launched by itself on the stream it was recorded for
 int flush_pending_prepare(fftconv_plan* p);
-// the plan's "output_region" of nmaps full-window maps at src, compacted into dst: 4 pads to the pow2 window, the others crop
-// scale: maps of a score with a plane -- the planes of the plan's images (D, Dc: multiplied; Q: added with consts[m % per_image], the
-// constants of the launch's kernels); map m of the launch belongs to image image0 + m / per_image
-int launch_region(const fftconv_plan* p, const float* src, float* dst, int nmaps, hipStream_t s, const float* scale = nullptr, int image0 = 0,
-                  int per_image = 1, const float* consts = nullptr);
 // Core of the per-kernel loop for n kernels of one size, packed on the device at dk ([n][F][kw][kh]); on failure nothing of the
 // host-output ring is still writing into the caller's buffers when the error is returned
 int run_group(fftconv_plan* p, int n, const float* dk, int kh, int kw, const Sink& sink);
@@ -471,13 +474,31 @@ int prepare_kernels(fftconv_plan* p, int n, const float* dk, int kh, int kw, boo
 int plan_create_internal(fftconv_plan** plan, int data_h, int data_w, int feature_dim, int max_kernel_h, int max_kernel_w, int gpu_id,
                          void* hip_stream, const fftconv_plan_options* options, bool cyclic);
 
-// the launch that stores ny maps of the plan's rectangle (fftconv_plan::rect_direct) from the intermediate y, dense from `out` on
-FastColsShape output_rect_shape(const fftconv_plan* p, const c32* y, float* out, int ny, int format);
-// the launch that stores ny normalised maps (fftconv_plan::norm_direct) of the window or of the plan's rectangle: image-major from
-// image image0 on, per_image kernels each
-FastColsShape output_norm_shape(const fftconv_plan* p, const c32* y, float* out, int ny, int image0, int per_image);
-// ... of score 4: consts[0] is the constant of the launch's first kernel
-FastColsShape output_sqdiff_shape(const fftconv_plan* p, const c32* y, float* out, int ny, int image0, int per_image, const float* consts);
+// ---- output side of the plan core (plan_output.cpp) ----
+// How the maps of a group leave the device: the route, decided once per group, and what the loop needs beside it
+struct Delivery {
+    OutputRoute r;
+    DevBuf<float>* stage = nullptr;    // staged routes: where the maps wait for their copy (r.staging)
+    size_t oe = 0;                     // elements per delivered map
+    size_t eb = sizeof(float);         // bytes per element ("map_format")
+    size_t mb() const { return oe * eb; }
+};
+// what one launch of a group adds to the route: its maps are image-major from image image0 on with per_image kernels each, and
+// consts[0] is the constant of the launch's first kernel (score 4: KC at the kernel's place in the chunk)
+struct OutLaunch {
+    int image0 = 0, per_image = 1;
+    const float* consts = nullptr;
+};
+// the route of a group into `sink` and the buffers it names, sized for nbY maps per launch (the ring: started)
+int plan_delivery(fftconv_plan* p, const Sink& sink, int nbY, Delivery& d);
+// output columns of ny maps: Y transformed along h into the maps at obase (win: into the window of an overlap-save block)
+int launch_output_cols(fftconv_plan* p, const OutputRoute& r, const OutWindow* win, float* obase, int ny, const OutLaunch& l);
+// r.after: nmaps full fp32 windows at src cropped (padded) into dst and combined with the route's plane on the way
+int launch_region(const fftconv_plan* p, const OutputRoute& r, const float* src, float* dst, int nmaps, hipStream_t s, const OutLaunch& l = {});
+// the maps [first, first + ny) are queued into `dest` (staging buffer buf of a streamed group): their way to the caller
+int deliver_batch(fftconv_plan* p, const Delivery& d, const Sink& sink, int first, int ny, int buf, const float* dest);
+// the rectangle launch of a route whose store is Rect, RectScale or RectAdd: ny maps from the intermediate y, dense from `out` on
+FastColsShape output_rect_shape(const fftconv_plan* p, const OutputRoute& r, const c32* y, float* out, int ny, const OutLaunch& l = {});
 
 // ---- host-output streaming (host_ring.cpp) ----
 // A streamed group (run_group, host maps of at least host_min_kb) has two staging buffers on the device: batch b is computed into
@@ -493,9 +514,9 @@ int ring_finish(fftconv_plan* p, const Sink& sink);
 
 // ---- placement tuning (placement.cpp) ----
 // before the first launch of a group of n maps into a (re)allocated intermediate: times candidate allocations of it where the plan's
-// tune_placement option (or its automatic default) says so.  direct: the output kernel writes the caller's packed maps, from `out` on
-// format: FC_MAP_* of what the output kernel writes at `out` (fp32 into the full-window staging of a cropped region)
-int tune_intermediate_placement(fftconv_plan* p, const Sink& sink, int n, int nbY, float* out, bool direct, int format);
+// tune_placement option (or its automatic default) says so.  route: the group's (its probe launch, what the output kernel stores and
+// whether `out`, its target, is the caller's packed maps or a staging buffer)
+int tune_intermediate_placement(fftconv_plan* p, const OutputRoute& route, int n, int nbY, float* out);
 
 // ---- block-wise plans (blockwise.cpp) ----
 bool blocks_preferred(const Geometry& g, const fftconv_plan_options* options);

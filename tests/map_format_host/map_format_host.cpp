@@ -126,7 +126,7 @@ void run_fast_cols(const char* what, int H, int W, int kh, int kw, int path_mode
                 for (int i = 0; i < Cfg::LDS_ELEMS; i++) lds[i] = mk(1e30f, -1e30f);
                 HostPhaseCtx<std::conditional_t<tiled.value, ColPairState<Cfg>, ColState<Cfg>>> ctx(Cfg::NT);
                 if (format == FC_MAP_F32) fast_cols_body<Cfg, tiled.value, sliced.value, dyn.value>(ctx, lds.data(), sh.a, wg, sh.grid);
-                else fast_cols_body<Cfg, tiled.value, sliced.value, dyn.value, true>(ctx, lds.data(), sh.a, wg, sh.grid);
+                else fast_cols_body<Cfg, tiled.value, sliced.value, dyn.value, ColStore::PAIRS16>(ctx, lds.data(), sh.a, wg, sh.grid);
             }
         });
         if (format != FC_MAP_F32) compare(what, f32, h16, format, ne);

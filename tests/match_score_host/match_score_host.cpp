@@ -4,9 +4,9 @@
 // here exactly as the kernels of kernels_score.hip call them and are held to the table of include/fftconv.h, brute force in long double.
 //   match_score_host planes    Dc = E^(-1/2) and Q = E, strip by strip; exact zeros exactly where no non-zero pixel lies under the box
 //   match_score_host kernels   the preparations of scores 2, 3 and 4 and the constant c_k
-//   match_score_host shape     fast_cols_sqdiff_launch_shape and through it the ADD body of fast_cols.hpp on the phase context: every
+//   match_score_host shape     fast_cols_rect_launch_shape with an Add plane and through it the ADD body of fast_cols.hpp on the phase context: every
 //                              element is the plain body's element + (Q + c), bit for bit, and nothing else is written or read
-//   match_score_host direct    fast_cols_sqdiff_available and fast_cols_score_direct over every combination; the argument checks
+//   match_score_host direct    fast_cols_sqdiff_available and the fused store of plan_output_route (output_route.hpp) over every combination; the argument checks
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -15,6 +15,7 @@
 
 #include "emu_runners.hpp"
 #include "ncc.hpp"
+#include "output_route.hpp"
 
 using namespace fc;
 using emu::HostPhaseCtx;
@@ -245,22 +246,26 @@ static void shape_config(const char* what, int H, int W, int kh, int kw, bool ex
             const FastColsArgs a = fast_cols_args(g, d, Y.data(), base + GUARD, stride, NK, FC_MAP_F32);
             // the product passes (image0, per_image) with the launch's first kernel at consts[0]; a launch that starts inside an image
             // is what `first` not being a multiple of per_image means, set here as the body reads it
-            FastColsShape sh = fast_cols_sqdiff_launch_shape(Cfg::T, a, r.off_h, r.off_w, r.out_h, r.out_w, 1 << 20, Q.data(), consts.data(), g.fft_h, g.fft_w, 1, PER_IMAGE);
+            MapPlane pl;
+            pl.kind = PlaneKind::Add; pl.plane = Q.data(); pl.consts = consts.data(); pl.plane_elems = (size_t)g.fft_h * g.fft_w; pl.pitch = g.fft_h;
+            pl.first = 1 * PER_IMAGE; pl.per_image = PER_IMAGE;
+            FastColsShape sh = fast_cols_rect_launch_shape(Cfg::T, a, r.off_h, r.off_w, r.out_h, r.out_w, 1 << 20, pl);
+            FastColsSqdiffArgs q = fast_cols_sqdiff_args(sh.plane);      // what the launch hands the kernel
             const int w_lo = r.off_w / Cfg::T * Cfg::T, w_hi = (r.off_w + r.out_w + Cfg::T - 1) / Cfg::T * Cfg::T, tiles = (w_hi - w_lo) / Cfg::T * NK;
             const int want_wide = (r.off_h % 2 == 0 && r.out_h % 2 == 0) ? 1 : 0;
             CHECK(sh.variant == (dyn ? FastColsVariant::TILED_DYN : FastColsVariant::TILED), "%s: variant %d", what, (int)sh.variant);
             CHECK(sh.a.h_lo == r.off_h && sh.a.fft_h == r.off_h + r.out_h && sh.a.out_pitch == r.out_h, "%s: rows [%d, %d) pitch %d", what, sh.a.h_lo, sh.a.fft_h, sh.a.out_pitch);
             CHECK(sh.a.w_first == w_lo && sh.a.ntiles == tiles && sh.grid == tiles, "%s: %d tiles from column %d on %d workgroups", what, sh.a.ntiles, sh.a.w_first, sh.grid);
             CHECK(sh.a.rect_w_lo == r.off_w && sh.a.rect_w_n == r.out_w && sh.a.rect_wide == want_wide, "%s: columns [%d, +%d) wide %d", what, sh.a.rect_w_lo, sh.a.rect_w_n, sh.a.rect_wide);
-            CHECK(sh.q.q == Q.data() && sh.q.c == consts.data() && sh.q.plane == ne && sh.q.pitch == g.fft_h && sh.q.first == PER_IMAGE && sh.q.per_image == PER_IMAGE &&
-                  fast_cols_sqdiff_args_ok(sh.q) && !sh.n.d, "%s: planes of %zu elements, pitch %d, first %d, %d per image", what, sh.q.plane, sh.q.pitch, sh.q.first, sh.q.per_image);
+            CHECK(q.q == Q.data() && q.c == consts.data() && q.plane == ne && q.pitch == g.fft_h && q.first == PER_IMAGE && q.per_image == PER_IMAGE &&
+                  fast_cols_sqdiff_args_ok(q) && sh.plane.kind == PlaneKind::Add, "%s: planes of %zu elements, pitch %d, first %d, %d per image", what, q.plane, q.pitch, q.first, q.per_image);
             if (failures != before) continue;
-            sh.q.first = FIRST;
+            q.first = FIRST;
             if (dyn) sh.a.queue_shift = 1;
             sh.grid = sh.a.ntiles < 3 ? sh.a.ntiles : 3;
             run_wgs(sh.grid, [&](auto& ctx, int wg) {
-                if (dyn) fast_cols_body<Cfg, true, false, true, false, true, false, true>(ctx, lds.data(), sh.a, wg, sh.grid, nullptr, &sh.q);
-                else fast_cols_body<Cfg, true, false, false, false, true, false, true>(ctx, lds.data(), sh.a, wg, sh.grid, nullptr, &sh.q);
+                if (dyn) fast_cols_body<Cfg, true, false, true, ColStore::RECT_ADD>(ctx, lds.data(), sh.a, wg, sh.grid, q);
+                else fast_cols_body<Cfg, true, false, false, ColStore::RECT_ADD>(ctx, lds.data(), sh.a, wg, sh.grid, q);
             });
             size_t bad = 0, first = 0, stray = 0, written = 0;
             for (size_t i = 0; i < total; i++) {
@@ -327,10 +332,15 @@ static int run_direct() {
                             for (long region = 0; region <= 5; region++) {
                                 const bool common = store == 1 && !blockwise && format == FC_MAP_F32 && (region == 0 || region == 5) && tiled_y && fast_cols_lookup(M).ok;
                                 const bool want = score == 4 ? common && fast_cols_sqdiff_built(M) : (score == 1 || score == 3) ? common && fast_cols_norm_built(M) : false;
-                                const bool got = fast_cols_score_direct(score, store, blockwise, format, region, M, tiled_y);
+                                OutputRouteIn in;      // (the route of a packed sink: what read-only option "norm_direct" reports)
+                                in.sink = SinkKind::Packed; in.region = region; in.rect_store = true; in.score = score; in.norm_store = store != 0;
+                                in.blockwise = blockwise != 0; in.map_format = format; in.fast_cols = fast_cols_lookup(M).ok; in.y_tiled = tiled_y != 0;
+                                in.rect_built = fast_cols_rect_built(M); in.norm_built = fast_cols_norm_built(M); in.sqdiff_built = fast_cols_sqdiff_built(M);
+                                const OutputRoute route = plan_output_route(in);
+                                const bool got = route.fused();
                                 CHECK(got == want, "score_direct(M %d, tiled %d, score %d, store %d, block-wise %d, format %d, region %ld) = %d", M, tiled_y, score,
                                       store, blockwise, format, region, (int)got);
-                                if (score == 1) CHECK(got == fast_cols_norm_direct(true, store, blockwise, format, region, M, tiled_y), "score 1 is mode 1");
+                                if (score == 1) CHECK(got == (route.store == OutStore::RectScale && route.plane == OutPlane::D), "score 1 is mode 1");
                                 ones[score] += got;
                                 walked++;
                             }

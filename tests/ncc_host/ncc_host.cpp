@@ -6,12 +6,12 @@
 //   ncc_host stats     window statistics, every case
 //   ncc_host kernels   kernel normalisation
 //   ncc_host index     map -> image, strip widths, argument check
-//   ncc_host shape     the launch-shape decision of the fused scale (fast_paths.hpp: fast_cols_norm_launch_shape), whole window
+//   ncc_host shape     the launch-shape decision of the fused scale (fast_paths.hpp: fast_cols_rect_launch_shape with a Scale plane), whole window
 //                      and rectangle, image0 > 0 and per_image > 1, and through it the NORM body of fast_cols.hpp on the phase
 //                      context of tests/emu: every stored element must be the plain body's element times D at its window
 //                      coordinate in the plane of its map's image, bit for bit, and nothing else may be written or read (the
 //                      plane of image 0 is NaN, the planes end with the window: a sanitizer build sees any read beyond them)
-//   ncc_host direct    fast_cols_norm_available over every configuration, and the norm_direct predicate (fast_cols_norm_direct)
+//   ncc_host direct    fast_cols_norm_available over every configuration, and the norm_direct predicate (output_route.hpp: the fused store of plan_output_route)
 //                      over mode x store x block-wise x format x region x configuration x layout of the intermediate
 #include <cmath>
 #include <cstdint>
@@ -21,6 +21,7 @@
 
 #include "emu_runners.hpp"
 #include "ncc.hpp"
+#include "output_route.hpp"
 
 using namespace fc;
 using emu::HostPhaseCtx;
@@ -285,7 +286,10 @@ static void shape_config(const char* what, int H, int W, int kh, int kw, bool ex
             for (size_t i = 0; i < total; i++) memcpy(base + i, &POISON, 4);
             d.queue = dyn ? queue : nullptr;
             const FastColsArgs a = fast_cols_args(g, d, Y.data(), base + GUARD, stride, NK, FC_MAP_F32);
-            FastColsShape sh = fast_cols_norm_launch_shape(Cfg::T, a, r.off_h, r.off_w, r.out_h, r.out_w, 1 << 20, D.data(), g.fft_h, g.fft_w, IMAGE0, PER_IMAGE);
+            MapPlane pl;
+            pl.kind = PlaneKind::Scale; pl.plane = D.data(); pl.plane_elems = (size_t)g.fft_h * g.fft_w; pl.pitch = g.fft_h; pl.first = IMAGE0 * PER_IMAGE; pl.per_image = PER_IMAGE;
+            FastColsShape sh = fast_cols_rect_launch_shape(Cfg::T, a, r.off_h, r.off_w, r.out_h, r.out_w, 1 << 20, pl);
+            const FastColsNormArgs n = fast_cols_norm_args(sh.plane);      // what the launch hands the kernel
             // the decision: the rectangle launch of fast_cols_rect_launch_shape, plus the planes
             const int w_lo = r.off_w / Cfg::T * Cfg::T, w_hi = (r.off_w + r.out_w + Cfg::T - 1) / Cfg::T * Cfg::T, tiles = (w_hi - w_lo) / Cfg::T * NK;
             const bool whole = r.off_h == 0 && r.off_w == 0 && r.out_h == g.fft_h && r.out_w == g.fft_w;
@@ -297,14 +301,14 @@ static void shape_config(const char* what, int H, int W, int kh, int kw, bool ex
             CHECK(sh.a.rect_w_lo == r.off_w && sh.a.rect_w_n == r.out_w && sh.a.rect_wide == want_wide, "%s: columns [%d, +%d) wide %d", what, sh.a.rect_w_lo, sh.a.rect_w_n, sh.a.rect_wide);
             CHECK(!whole || sh.a.rect_wide == 1, "%s: the whole window keeps the pair stores", what);
             CHECK(sh.a.out_format == FC_MAP_F32 && sh.a.tail_tiles == 0 && sh.a.slice_shift == 0, "%s: fp32, unsliced", what);
-            CHECK(sh.n.d == D.data() && sh.n.plane == ne && sh.n.pitch == g.fft_h && sh.n.first == IMAGE0 * PER_IMAGE && sh.n.per_image == PER_IMAGE,
-                  "%s: planes of %zu elements, pitch %d, first %d, %d per image", what, sh.n.plane, sh.n.pitch, sh.n.first, sh.n.per_image);
+            CHECK(sh.plane.kind == PlaneKind::Scale && n.d == D.data() && n.plane == ne && n.pitch == g.fft_h && n.first == IMAGE0 * PER_IMAGE && n.per_image == PER_IMAGE,
+                  "%s: planes of %zu elements, pitch %d, first %d, %d per image", what, n.plane, n.pitch, n.first, n.per_image);
             if (failures != before) continue;
             if (dyn) sh.a.queue_shift = 1;
             sh.grid = sh.a.ntiles < 3 ? sh.a.ntiles : 3;
             run_wgs(sh.grid, [&](auto& ctx, int wg) {
-                if (dyn) fast_cols_body<Cfg, true, false, true, false, true, true>(ctx, lds.data(), sh.a, wg, sh.grid, &sh.n);
-                else fast_cols_body<Cfg, true, false, false, false, true, true>(ctx, lds.data(), sh.a, wg, sh.grid, &sh.n);
+                if (dyn) fast_cols_body<Cfg, true, false, true, ColStore::RECT_SCALE>(ctx, lds.data(), sh.a, wg, sh.grid, n);
+                else fast_cols_body<Cfg, true, false, false, ColStore::RECT_SCALE>(ctx, lds.data(), sh.a, wg, sh.grid, n);
             });
             size_t bad = 0, first = 0, stray = 0, written = 0;
             for (size_t i = 0; i < total; i++) {
@@ -370,7 +374,11 @@ static int run_direct() {
                             for (long region = 0; region <= 5; region++) {
                                 const bool want = mode == 1 && store == 1 && !blockwise && format == FC_MAP_F32 && (region == 0 || region == 5) && tiled_y &&
                                                   fast_cols_lookup(M).ok && M != 544 && M != 2080 && fast_cols_norm_built(M);
-                                const bool got = fast_cols_norm_direct(mode, store, blockwise, format, region, M, tiled_y);
+                                OutputRouteIn in;      // (the route of a packed sink: what read-only option "norm_direct" reports)
+                                in.sink = SinkKind::Packed; in.region = region; in.rect_store = true; in.score = mode; in.norm_store = store != 0;
+                                in.blockwise = blockwise != 0; in.map_format = format; in.fast_cols = fast_cols_lookup(M).ok; in.y_tiled = tiled_y != 0;
+                                in.rect_built = fast_cols_rect_built(M); in.norm_built = fast_cols_norm_built(M); in.sqdiff_built = fast_cols_sqdiff_built(M);
+                                const bool got = plan_output_route(in).fused();
                                 CHECK(got == want, "norm_direct(M %d, tiled %d, mode %d, store %d, block-wise %d, format %d, region %ld) = %d", M, tiled_y, mode,
                                       store, blockwise, format, region, (int)got);
                                 ones += got;

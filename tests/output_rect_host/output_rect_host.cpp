@@ -181,11 +181,11 @@ void run_config(const char* what, int H, int W, int kh, int kw, bool exact, int 
                 sh.grid = sh.a.ntiles < 3 ? sh.a.ntiles : 3;
                 run_wgs(sh.grid, [&](auto& ctx, int wg) {
                     if (format == FC_MAP_F32) {
-                        if (run.dyn) fast_cols_body<Cfg, true, false, true, false, true>(ctx, lds.data(), sh.a, wg, sh.grid);
-                        else fast_cols_body<Cfg, true, false, false, false, true>(ctx, lds.data(), sh.a, wg, sh.grid);
+                        if (run.dyn) fast_cols_body<Cfg, true, false, true, ColStore::RECT>(ctx, lds.data(), sh.a, wg, sh.grid);
+                        else fast_cols_body<Cfg, true, false, false, ColStore::RECT>(ctx, lds.data(), sh.a, wg, sh.grid);
                     } else {
-                        if (run.dyn) fast_cols_body<Cfg, true, false, true, true, true>(ctx, lds.data(), sh.a, wg, sh.grid);
-                        else fast_cols_body<Cfg, true, false, false, true, true>(ctx, lds.data(), sh.a, wg, sh.grid);
+                        if (run.dyn) fast_cols_body<Cfg, true, false, true, ColStore::RECT16>(ctx, lds.data(), sh.a, wg, sh.grid);
+                        else fast_cols_body<Cfg, true, false, false, ColStore::RECT16>(ctx, lds.data(), sh.a, wg, sh.grid);
                     }
                 });
                 // every element of the buffer: inside a map the reference element, everywhere else the poison

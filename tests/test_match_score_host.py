@@ -5,7 +5,7 @@
     own main over the product's headers, runs them strip by strip as the launcher does and holds every element to the table of
     include/fftconv.h, brute force in long double -- exact zeros exactly where no non-zero pixel lies under the box; it also builds
     with -fsanitize=address,undefined and then runs directly;
-  * the launch-shape decision of the fused additive store (fast_paths.hpp: fast_cols_sqdiff_launch_shape) for the whole window and
+  * the launch-shape decision of the fused additive store (fast_paths.hpp: fast_cols_rect_launch_shape with an Add plane) for the whole window and
     odd rectangles, and through it the ADD body of fast_cols.hpp on the host phase context, with a launch that starts and ends
     inside an image: every element the plain body's element + (Q + c), bit for bit;
   * fast_cols_sqdiff_available for every configuration, the direct predicate over every combination of settings, the argument checks;

@@ -5,7 +5,7 @@
     strip as the launcher does and holds every element to the brute-force definition in long double -- exact zeros exactly where
     the definition floors; it also builds with -fsanitize=address,undefined and then runs directly;
   * the map-to-image index, the strip widths and the argument check of the same header;
-  * the launch-shape decision of the fused scale (fast_paths.hpp: fast_cols_norm_launch_shape) for the whole window and for
+  * the launch-shape decision of the fused scale (fast_paths.hpp: fast_cols_rect_launch_shape with a Scale plane) for the whole window and for
     rectangles, with image0 > 0 and per_image > 1, and through it the NORM body of fast_cols.hpp on the host phase context: every
     element the plain body's element times D of its map's image, bit for bit;
   * fast_cols_norm_available for every configuration and the norm_direct predicate over every combination of settings;
