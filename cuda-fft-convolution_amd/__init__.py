@@ -136,7 +136,7 @@ EXPORTED_SYMBOLS = (
     "fftconv_plan_use_spectrum_buffer", "fftconv_plan_export_spectrum", "fftconv_plan_import_spectrum",
     "fftconv_plan_convolve", "fftconv_plan_convolve_packed", "fftconv_plan_prepare_kernels_packed",
     "fftconv_plan_synchronize", "fftconv_plan_set_stream",
-    "fftconv_plan_set_option", "fftconv_plan_set_output_rect", "fftconv_plan_set_normalisation", "fftconv_plan_set_match_score", "fftconv_plan_set_border", "fftconv_plan_get_option", "fftconv_plan_get_profile",
+    "fftconv_plan_set_option", "fftconv_plan_set_output_rect", "fftconv_plan_set_output_stride", "fftconv_plan_set_normalisation", "fftconv_plan_set_match_score", "fftconv_plan_set_border", "fftconv_plan_get_option", "fftconv_plan_get_profile",
     "fftconv_fft_data", "fftconv_conv_fft_data",
     "fftconv_multi_create", "fftconv_multi_destroy", "fftconv_multi_set_image", "fftconv_multi_import_spectrum",
     "fftconv_multi_convolve", "fftconv_multi_set_option", "fftconv_multi_get_option",
@@ -211,6 +211,7 @@ def load_library():
     lib.fftconv_plan_set_stream.argtypes = [vp, vp]
     lib.fftconv_plan_set_option.argtypes = [vp, ctypes.c_char_p, ctypes.c_long]
     lib.fftconv_plan_set_output_rect.argtypes = [vp, ci, ci, ci, ci]
+    lib.fftconv_plan_set_output_stride.argtypes = [vp, ci, ci]
     lib.fftconv_plan_set_normalisation.argtypes = [vp, ci, ci, ci]
     lib.fftconv_plan_set_match_score.argtypes = [vp, ci, ci, ci]
     lib.fftconv_plan_set_border.argtypes = [vp, ci, ctypes.c_float]
@@ -581,6 +582,15 @@ class Plan:
         """every result map becomes rows [off_h, off_h + out_h) of columns [off_w, off_w + out_w) of the FFT_H x FFT_W window
         (dense, column-major); info.out_h / out_w / out_map_bytes follow, option "output_region" then reads 5"""
         _check(self._lib.fftconv_plan_set_output_rect(self._h, int(off_h), int(off_w), int(out_h), int(out_w)))
+        _check(self._lib.fftconv_plan_get_info(self._h, ctypes.byref(self.info)))
+
+    def set_output_stride(self, stride_h, stride_w):
+        """every result map becomes every stride_h-th row and stride_w-th column of the map the plan would deliver without it (the
+        window, a region, the rectangle), counted from that map's first row and column (fftconv_plan_set_output_stride): dense,
+        column-major, ceil(out_h / stride_h) x ceil(out_w / stride_w); info.out_h / out_w / out_map_bytes follow.  (1, 1) restores
+        the dense maps.  Option "stride_store" (1, the default: the output kernel samples in its store where the plan can; 0:
+        always the staged crop), read-only "stride_direct", "stride_h", "stride_w"."""
+        _check(self._lib.fftconv_plan_set_output_stride(self._h, int(stride_h), int(stride_w)))
         _check(self._lib.fftconv_plan_get_info(self._h, ctypes.byref(self.info)))
 
     def set_normalisation(self, mode, box_h=0, box_w=0):

@@ -193,7 +193,7 @@ static int tiled_deliver(fftconv_plan* p, float* big, int nk, int k0, bool more,
     fftconv_plan* sub = ts->sub;
     const size_t oe = p->out_elems();
     const float* src = big;
-    if (p->opt_region != 0) {
+    if (p->opt_region != 0 || p->strided()) {      // (a stride is treated as a region is: full-window maps first, then the sampling crop -- region 0 included)
         float* dst = out_packed ? out_packed + (size_t)k0 * oe : ts->crop.p;
         // (the route of this plan's region: a block-wise plan never stores it densely itself and has no plane -- a plain crop or pad)
         if (int rc = launch_region(p, plan_output_route(output_route_in(p, SinkKind::Packed)), big, dst, nk, sub->stream)) return rc;
@@ -219,7 +219,7 @@ int tiled_convolve_save(fftconv_plan* p, int n, const float* const* kernels, con
     const size_t budget = (size_t)6 << 30;
     // "output_region" other than the window: the blocks still store into full-window maps (the output kernel's stores are
     // pairs of rows at even offsets: an arbitrary rectangle is not), a crop kernel compacts the region out of them
-    const bool cropped = p->opt_region != 0;
+    const bool cropped = p->opt_region != 0 || p->strided();
     const size_t oe = p->out_elems();
     const bool direct = out_packed && !cropped;       // the blocks store straight into the caller's packed maps
     const int nc = direct ? n : (int)std::max<size_t>(1, std::min<size_t>((size_t)n, budget / (big_map * sizeof(float))));
@@ -302,7 +302,7 @@ int tiled_convolve(fftconv_plan* p, int n, const float* const* kernels, const in
     const size_t big_map = ts->big_map(), blk_map = sub->g.map_elems();
     const size_t budget = (size_t)6 << 30;
     const int nc = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, budget / ((big_map + blk_map) * sizeof(float))));
-    const bool cropped = p->opt_region != 0;          // as in tiled_convolve_save: full-window maps first, the region cropped out of them
+    const bool cropped = p->opt_region != 0 || p->strided();          // as in tiled_convolve_save: full-window maps first, the region cropped out of them
     const bool direct = out_packed && !cropped;
     if (!direct)
         if (int rc = ts->big.ensure(big_map * nc)) return rc;

@@ -216,12 +216,34 @@ struct FastColsSqdiffArgs {
 };
 FC_HD bool fast_cols_sqdiff_args_ok(const FastColsSqdiffArgs& a) { return a.q && a.c && a.plane > 0 && a.pitch > 0 && a.first >= 0 && a.per_image >= 1; }
 
+// STRIDE instantiations only (strided maps, fftconv_plan_set_output_stride): every sh-th row and sw-th column of the rectangle, counted
+// from its first row and column, is stored, densely.  The kernel divides by neither stride: StrideDiv holds a step with what
+// replaces the division, uniform over the launch -- a shift and a mask for a power of two (shift >= 0), else the reciprocal
+// rcp = ceil(2^32 / step), with which (x * rcp) >> 32 == x / step for every x with x * step < 2^32 (the host keeps step at most the
+// extent it samples, and an extent has fewer than 2^16 rows and columns: fast_paths.hpp, fast_cols_stride_launch_shape).
+struct StrideDiv {
+    int step = 1, shift = 0;
+    unsigned mask = 0, rcp = 0;
+};
+FC_HD unsigned stride_quot(const StrideDiv& d, unsigned x) { return d.shift >= 0 ? x >> d.shift : (unsigned)(((unsigned long long)x * d.rcp) >> 32); }
+// (q = stride_quot(d, x): whether x is a multiple of the step)
+FC_HD bool stride_hit(const StrideDiv& d, unsigned x, unsigned q) { return d.shift >= 0 ? (x & d.mask) == 0 : q * (unsigned)d.step == x; }
+// h, w: the strides along the rows and the columns of the rectangle FastColsArgs names (h_lo, fft_h, rect_w_lo, rect_w_n: the
+// UNSAMPLED extent; out_pitch: the sampled rows of a column).  tile_step: 0 -- the launch covers the contiguous range of window tiles
+// from w_first on, as RECT's; sw > T: sw -- one tile per sampled column, tile i of a map is the window tile that holds column
+// rect_w_lo + i * sw.  A kernel argument of its own for the reason given above FastColsNormArgs.
+struct FastColsStrideArgs {
+    StrideDiv h, w;
+    int tile_step = 0;
+};
+
 // What the last phase of fast_cols_body stores (its template parameter STORE, described there), and the argument a store takes
-// beside FastColsArgs: the plane's device struct, or nothing (void)
-enum class ColStore { PAIRS, PAIRS16, RECT, RECT16, RECT_SCALE, RECT_ADD };
+// beside FastColsArgs: the plane's (or the strides') device struct, or nothing (void)
+enum class ColStore { PAIRS, PAIRS16, RECT, RECT16, RECT_SCALE, RECT_ADD, RECT_STRIDE };
 template <ColStore S> struct ColStorePlane { using type = void; };
 template <> struct ColStorePlane<ColStore::RECT_SCALE> { using type = FastColsNormArgs; };
 template <> struct ColStorePlane<ColStore::RECT_ADD> { using type = FastColsSqdiffArgs; };
+template <> struct ColStorePlane<ColStore::RECT_STRIDE> { using type = FastColsStrideArgs; };
 template <class A>
 FC_HD const A* col_store_plane(const A& a) { return &a; }
 
@@ -308,23 +330,31 @@ FC_HD int pair_of_unit(int u) {
 // store (FastColsNormArgs, the body's last argument); the multiply is the only arithmetic added, and the store stays ONE predicated block per pair.
 // ADD (RECT, fp32 maps, never with NORM): matching score 4 -- a value pair becomes v + (q + c), q the pair of the plane Q at its
 // window coordinate and c the constant of the map's kernel (FastColsSqdiffArgs); the load sits where NORM's sits.
-// STORE names what C4 stores, one of the six stores that exist -- the properties above in the combinations that are legal:
+// STRIDE (RECT, fp32 maps, never with NORM or ADD): strided maps -- of the rectangle's columns only those whose offset from its first
+// column is a multiple of the column stride are transformed in stage 1 and stored, side by side; of a column's rows those whose offset
+// from its first row is a multiple of the row stride, one element per store (FastColsStrideArgs; a row stride of 1 keeps RECT's
+// stores, the pair store included).  A column stride above T launches one tile per sampled column (tile_w0 below).
+// STORE names what C4 stores, one of the seven stores that exist -- the properties above in the combinations that are legal:
 //   PAIRS, PAIRS16             the window (or an OutWindow), a pair of rows per store: fp32, 16-bit (OUT16)
 //   RECT, RECT16               the dense rectangle: fp32, 16-bit (RECT, RECT + OUT16)
 //   RECT_SCALE, RECT_ADD       the fp32 rectangle times a scale plane (RECT + NORM), plus Q + c (RECT + ADD)
-// The last two take one more argument, the plane's device struct (FastColsNormArgs, FastColsSqdiffArgs); the others take none.
+//   RECT_STRIDE                every sh-th row and sw-th column of the fp32 rectangle (RECT + STRIDE)
+// The last three take one more argument, their device struct (FastColsNormArgs, FastColsSqdiffArgs, FastColsStrideArgs); the others
+// take none.
 template <class C, bool TILED, bool SLICED = false, bool DYN = false, ColStore STORE = ColStore::PAIRS, class Ctx, class... PlaneArgs>
 FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int nwg, const PlaneArgs&... plane_args) {
     constexpr bool OUT16 = STORE == ColStore::PAIRS16 || STORE == ColStore::RECT16;
     constexpr bool RECT = STORE != ColStore::PAIRS && STORE != ColStore::PAIRS16;
-    constexpr bool NORM = STORE == ColStore::RECT_SCALE, ADD = STORE == ColStore::RECT_ADD;
+    constexpr bool NORM = STORE == ColStore::RECT_SCALE, ADD = STORE == ColStore::RECT_ADD, STRIDE = STORE == ColStore::RECT_STRIDE;
     using Plane = typename ColStorePlane<STORE>::type;
     static_assert(sizeof...(PlaneArgs) == (std::is_void_v<Plane> ? 0 : 1) && (std::is_same_v<Plane, PlaneArgs> && ...),
-                  "RECT_SCALE takes FastColsNormArgs, RECT_ADD FastColsSqdiffArgs, the other stores nothing");
+                  "RECT_SCALE takes FastColsNormArgs, RECT_ADD FastColsSqdiffArgs, RECT_STRIDE FastColsStrideArgs, the other stores nothing");
     [[maybe_unused]] const FastColsNormArgs* nrm = nullptr;
     [[maybe_unused]] const FastColsSqdiffArgs* add = nullptr;
+    [[maybe_unused]] const FastColsStrideArgs* strd = nullptr;
     if constexpr (NORM) nrm = col_store_plane(plane_args...);
     if constexpr (ADD) add = col_store_plane(plane_args...);
+    if constexpr (STRIDE) strd = col_store_plane(plane_args...);
     static_assert(!RECT || (TILED && !SLICED), "the rectangle store exists for unsliced launches on the tiled intermediate");
     static_assert(!SLICED || TILED, "column slices exist for the tiled intermediate only");
     static_assert(!(SLICED && DYN), "the sliced tail round is dealt statically");
@@ -384,6 +414,15 @@ FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int
     const int first_tile = dyn ? FC_UNIFORM(qs[1]) : tile_of(0);
     [[maybe_unused]] int cur_lo = cols_lo(0), cur_hi = cols_hi(0), nxt_lo = 0, nxt_hi = T;
 
+    // first window column of a map's launched tile i: the launch covers a contiguous range of window tiles, or (STRIDE with a column
+    // stride above T) the tiles of the sampled columns alone
+    auto tile_w0 = [&](int i) -> int {
+        if constexpr (STRIDE) {
+            if (strd->tile_step) return (g.rect_w_lo + i * strd->tile_step) / T * T;
+        }
+        return g.w_first + i * T;
+    };
+
     // part: 0 = the whole gather (the first tile; every tile of the row-major intermediate); 1 / 2 / 3 = its first / second / last
     // third of rounds, issued at the start of the tile, after stage 3 and ahead of the last round of stage 2 -- a CU cannot
     // keep a whole tile (135 KB) of loads in flight, so issuing it in one go stalls the waves in the issue itself; each third
@@ -391,7 +430,7 @@ FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int
     auto issue_gather = [&](int t, State& st, int tile, auto part_, [[maybe_unused]] int c_lo, [[maybe_unused]] int c_hi) {
         constexpr int part = decltype(part_)::value;
         const int kernel = tile / g.tiles_per_kernel;
-        const int w0 = g.w_first + (tile - kernel * g.tiles_per_kernel) * T;
+        const int w0 = tile_w0(tile - kernel * g.tiles_per_kernel);
         if constexpr (PLAND) {   // rows 2p, 2p+1 = bins (p, M-p); one thread takes both for two columns
             const int tw = 1 << g.y_tile_shift;
             const c32* Yt = g.Y + (size_t)kernel * g.y_kernel_stride + (size_t)(w0 >> g.y_tile_shift) * g.y_tile_elems + (w0 & (tw - 1));
@@ -507,7 +546,7 @@ FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int
         const int tile = dyn ? dyn_tile : tile_of(it);
         if (tile >= n_total) break;
         const int kernel = tile / g.tiles_per_kernel;
-        const int w0 = g.w_first + (tile - kernel * g.tiles_per_kernel) * T;
+        const int w0 = tile_w0(tile - kernel * g.tiles_per_kernel);
         const int next = dyn ? dyn_next : tile_of(it + 1);
         // dynamic queue: the ticket of the tile after next is requested now (ahead of the gather loads: the memory counter is in
         // order) and read in C4, behind the wait for the gather that is there anyway
@@ -631,6 +670,13 @@ FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int
                 bool mine1 = idx < C::NB1 * T;
                 if constexpr (SLICED) mine1 = mine1 && idx / C::NB1 >= cur_lo && idx / C::NB1 < cur_hi;
                 if constexpr (RECT) mine1 = mine1 && (unsigned)(w0 + idx / C::NB1 - g.rect_w_lo) < (unsigned)g.rect_w_n;
+                // STRIDE: of the rectangle's columns the sampled ones alone; qcol: the column's place in the strided map
+                [[maybe_unused]] unsigned qcol = 0;
+                if constexpr (STRIDE) {
+                    const unsigned cw = (unsigned)(w0 + idx / C::NB1 - g.rect_w_lo);
+                    qcol = stride_quot(strd->w, cw);
+                    mine1 = mine1 && stride_hit(strd->w, cw, qcol);
+                }
                 if (mine1) {
                     const int col = idx / C::NB1, j = idx % C::NB1;
                     const c32* p = lds + col * LP + j;
@@ -640,7 +686,9 @@ FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int
                     inv_stage1_in<R1, C::S1>(p, 0, pw, v);
                     if constexpr (RECT) {
                         // element (h - h_lo) of the column's run of the dense map; hr = row 2n of the pair, relative to h_lo
-                        const size_t cbase = (size_t)(w0 + col - g.rect_w_lo) * g.out_pitch;
+                        size_t cbase;
+                        if constexpr (STRIDE) cbase = (size_t)qcol * g.out_pitch;
+                        else cbase = (size_t)(w0 + col - g.rect_w_lo) * g.out_pitch;
                         // (the two element classes differ in the pointer, the pair store and the conversion: one predicated block)
                         std::conditional_t<OUT16, uint16_t, float>* o;
                         if constexpr (OUT16) o = out16 + cbase;
@@ -652,6 +700,10 @@ FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int
                         [[maybe_unused]] const float* dcol = nullptr;
                         if constexpr (NORM) dcol = dplane + (size_t)(w0 + col) * nrm->pitch;
                         if constexpr (ADD) dcol = dplane + (size_t)(w0 + col) * add->pitch;
+                        // STRIDE with a row stride other than 1 (uniform over the launch): row hr of the rectangle is element hr / sh of
+                        // the column's run if it is a multiple of sh -- one element per store
+                        [[maybe_unused]] bool strided_rows = false;
+                        if constexpr (STRIDE) strided_rows = strd->h.step != 1;
                         static_for<0, R1>([&](auto a_) {
                             constexpr int a = decltype(a_)::value;
                             const int hr = 2 * (j + a * m1) - g.h_lo;
@@ -667,7 +719,13 @@ FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int
                                     v[a].x += sx;
                                     v[a].y += sy;
                                 }
-                                if (g.rect_wide) {
+                                if (strided_rows) {
+                                    if constexpr (STRIDE) {
+                                        const unsigned q0 = stride_quot(strd->h, (unsigned)hr), q1 = stride_quot(strd->h, (unsigned)(hr + 1));
+                                        if (hr >= 0 && stride_hit(strd->h, (unsigned)hr, q0)) FC_STREAM_STORE_ELEM(o + q0, v[a].x);
+                                        if ((unsigned)(hr + 1) < nrows && stride_hit(strd->h, (unsigned)(hr + 1), q1)) FC_STREAM_STORE_ELEM(o + q1, v[a].y);
+                                    }
+                                } else if (g.rect_wide) {
                                     if constexpr (OUT16) FC_STREAM_STORE4(o + hr, fc_pack_map16(v[a].x, v[a].y, out_bf16));
                                     else FC_STREAM_STORE(reinterpret_cast<c32*>(o + hr), v[a]);
                                 } else {

@@ -603,6 +603,8 @@ struct FastColsShape {
     FastColsArgs a;
     int grid;
     MapPlane plane{};          // the rectangle family's fused scale / additive store only (fast_cols_rect_launch_shape below)
+    bool strided = false;      // the strided store (fast_cols_stride_launch_shape below): the launch is k_fast_cols_stride's, with `stride`
+    FastColsStrideArgs stride{};
 };
 inline FastColsShape fast_cols_launch_shape(int M, int T, const FastColsArgs& a, int want) {
     FastColsShape r{FastColsVariant::TILED_SLICED, a, 0};
@@ -657,6 +659,62 @@ inline FastColsShape fast_cols_rect_launch_shape(int T, const FastColsArgs& a, i
     if (r.variant == FastColsVariant::TILED_DYN) {
         r.a.queue_shift = 0;
         while ((16 << r.a.queue_shift) <= r.grid) r.a.queue_shift++;
+    }
+    return r;
+}
+
+// Strided store (fast_cols.hpp: STRIDE; plan entry fftconv_plan_set_output_stride): the fp32 rectangle kernel stores every sh-th row
+// and sw-th column of the extent, counted from its first row and column.  Built by the family's rule: a configuration whose kernel
+// spills a vector register, uses scratch or drops below 3 waves per SIMD in the build's reports (csrc/kernels_cols_stride_g*.rpt) is
+// NOT built and listed here; its plans sample while the staged window is cropped.  M = 544 and 2080 started here: their rectangle
+// kernels are not built either.
+constexpr int FC_COLS_STRIDE_NOT_BUILT[] = {544, 2080};
+constexpr bool fast_cols_stride_built(int M) {
+    for (int x : FC_COLS_STRIDE_NOT_BUILT)
+        if (x == M) return false;
+    return true;
+}
+inline bool fast_cols_stride_available(int M, bool y_tiled) { return y_tiled && fast_cols_lookup(M).ok && fast_cols_stride_built(M); }
+// rows or columns of an extent of n sampled at `step` from its first one
+constexpr int strided_count(int n, int step) { return (n + step - 1) / step; }
+// a step with what replaces the division by it in the kernel (fast_cols.hpp: StrideDiv); n: what it samples -- a step beyond n
+// samples the first element alone, as n does, and n < 2^16 keeps the reciprocal exact
+inline StrideDiv stride_div(int step, int n) {
+    StrideDiv d;
+    d.step = step < n ? step : n;
+    if ((d.step & (d.step - 1)) == 0) {
+        d.shift = 0;
+        while ((1 << d.shift) < d.step) d.shift++;
+        d.mask = (unsigned)d.step - 1u;
+    } else {
+        d.shift = -1;
+        d.rcp = (unsigned)((((unsigned long long)1 << 32) + (unsigned)d.step - 1u) / (unsigned)d.step);
+    }
+    return d;
+}
+// The launch of nk strided maps: `a` as for fast_cols_rect_launch_shape, with `out` the first dense strided map and out_kernel_stride
+// the elements between two of them (>= ceil(out_h / sh) * ceil(out_w / sw)); the extent (off_h, off_w, out_h, out_w) is the
+// UNSAMPLED one.  Only tiles that hold a sampled column are launched: for sw <= T RECT's contiguous range, ending at the tile of the
+// last sampled column; for sw > T one tile per sampled column (FastColsStrideArgs::tile_step).  sh == 1 keeps RECT's stores, the
+// pair store under RECT's conditions; sh >= 2 stores elements.  fp32 maps only (launch_fast_cols_rect refuses the others), extents
+// of fewer than 2^16 rows and columns (every one-pass window).
+inline FastColsShape fast_cols_stride_launch_shape(int T, const FastColsArgs& a, int off_h, int off_w, int out_h, int out_w, int sh, int sw, int want) {
+    const int nw = strided_count(out_w, sw), last_w = off_w + (nw - 1) * (sw < out_w ? sw : out_w);
+    FastColsShape r = fast_cols_rect_launch_shape(T, a, off_h, off_w, out_h, last_w - off_w + 1, want);
+    r.strided = true;
+    r.stride.h = stride_div(sh, out_h);
+    r.stride.w = stride_div(sw, out_w);
+    r.a.out_pitch = strided_count(out_h, sh);
+    if (r.stride.h.step != 1) r.a.rect_wide = 0;
+    if (r.stride.w.step > T) {
+        const int nk = a.tiles_per_kernel > 0 ? a.ntiles / a.tiles_per_kernel : 0;
+        r.stride.tile_step = r.stride.w.step;
+        r.a.tiles_per_kernel = nw; r.a.ntiles = nw * nk;
+        r.grid = r.a.ntiles < want ? r.a.ntiles : want;
+        if (r.variant == FastColsVariant::TILED_DYN) {
+            r.a.queue_shift = 0;
+            while ((16 << r.a.queue_shift) <= r.grid) r.a.queue_shift++;
+        }
     }
     return r;
 }

@@ -301,6 +301,7 @@ const LongOption kLongOptions[] = {
     {"tuned_best", &fftconv_plan::tuned_best, 0, 0, OPT_GET_ONLY},
     {"output_region", &fftconv_plan::opt_region, 0, 0, OPT_GET_ONLY},
     {"rect_store", &fftconv_plan::opt_rect_store, 0, 1, OPT_BOOL},
+    {"stride_store", &fftconv_plan::opt_stride_store, 0, 1, OPT_BOOL},   // (it only chooses the route of the next group: nothing cached depends on it)
     {"dynamic_tiles", &fftconv_plan::opt_dynamic_tiles, 0, 0, OPT_GET_ONLY},
     {"defer_prepare", &fftconv_plan::opt_defer_prepare, 0, 0, OPT_GET_ONLY},
     {"image_walk", &fftconv_plan::opt_image_walk, 0, 1, OPT_BOOL},      // (nothing cached depends on it: no OPT_FORGETS)
@@ -545,8 +546,8 @@ int fftconv_plan_get_info(const fftconv_plan* plan, fftconv_plan_info* info) {
     info->exact_window = g.exact_window ? 1 : 0;
     info->spectrum_bytes = g.spectrum_elems() * sizeof(c32);
     info->map_bytes = g.map_elems() * plan->elem_bytes();
-    info->out_h = plan->opt_region ? plan->out_h : g.fft_h;
-    info->out_w = plan->opt_region ? plan->out_w : g.fft_w;
+    info->out_h = plan->map_h();      // (of the delivered map: the extent, sampled at the plan's strides)
+    info->out_w = plan->map_w();
     info->out_map_bytes = plan->out_map_bytes();
     info->workspace_bytes = plan->A.bytes() + plan->Y.bytes() + plan->K.bytes() + plan->O.bytes() + plan->I.bytes() + plan->IT.bytes() + plan->IE.bytes() +
                             plan->ND.bytes() + plan->KN.bytes() + plan->KC.bytes() + plan->NS64.bytes();      // (matching scores: all 0 until one is on)
@@ -678,7 +679,7 @@ int fftconv_plan_set_option(fftconv_plan* plan, const char* name, long value) {
     if (!plan || !name) return api_fail(FFTCONV_ERR_INVALID_ARG, "NULL argument");
     if (!strcmp(name, "map_format"))
         if (const char* why = map_format_error(value, plan->tiled != nullptr)) return api_fail(FFTCONV_ERR_INVALID_ARG, "%s", why);
-    if (plan->tiled && strcmp(name, "output_region") && strcmp(name, "rect_store")) {      // block-wise: options act on the block plan ("output_region", "rect_store": on this one, below)
+    if (plan->tiled && strcmp(name, "output_region") && strcmp(name, "rect_store") && strcmp(name, "stride_store")) {      // block-wise: options act on the block plan ("output_region", "rect_store", "stride_store": on this one, below)
         if (!strcmp(name, "verbose")) plan->opt_verbose = value != 0;
         return fftconv_plan_set_option(plan->tiled->sub, name, value);
     }
@@ -742,6 +743,7 @@ int fftconv_plan_set_option(fftconv_plan* plan, const char* name, long value) {
         else if (value == 4) { oh = fft_size_pow2(g.H + g.max_kh - 1); ow = fft_size_pow2(g.W + g.max_kw - 1); }
         else if (value == 5) return api_fail(FFTCONV_ERR_INVALID_ARG, "output_region 5 (a rectangle of the window) is set with fftconv_plan_set_output_rect");
         else if (value != 0) return api_fail(FFTCONV_ERR_INVALID_ARG, "output_region is 0 (window), 1 (full), 2 (same), 3 (valid) or 4 (pow2 window)");
+        if (const char* why = output_stride_error(plan->stride_h, plan->stride_w, value)) return api_fail(FFTCONV_ERR_INVALID_ARG, "%s", why);
         if (oh < 1 || ow < 1) return api_fail(FFTCONV_ERR_INVALID_ARG, "output_region %ld is empty for %dx%d data and %dx%d kernels", value, g.H, g.W, g.max_kh, g.max_kw);
         if (int rc = use_device(plan)) return rc;
         HIP_TRY(hipStreamSynchronize(plan->stream));
@@ -764,6 +766,19 @@ int fftconv_plan_set_output_rect(fftconv_plan* plan, int off_h, int off_w, int o
     HIP_TRY(hipStreamSynchronize(plan->stream));
     plan->release_ring();          // sized for the map bytes
     plan->opt_region = 5; plan->out_h = out_h; plan->out_w = out_w; plan->off_h = off_h; plan->off_w = off_w;
+    return 0;
+}
+
+int fftconv_plan_set_output_stride(fftconv_plan* plan, int stride_h, int stride_w) {
+    if (!plan) return api_fail(FFTCONV_ERR_INVALID_ARG, "plan is NULL");
+    if (const char* why = output_stride_error(stride_h, stride_w, plan->opt_region))
+        return api_fail(FFTCONV_ERR_INVALID_ARG, "%s (strides (%d, %d) asked of a plan with output_region %ld)", why, stride_h, stride_w, plan->opt_region);
+    if (plan->stride_h == stride_h && plan->stride_w == stride_w) return 0;
+    if (int rc = use_device(plan)) return rc;
+    HIP_TRY(hipStreamSynchronize(plan->stream));
+    plan->release_ring();          // sized for the map bytes
+    // (output-side state alone: the image, the prepared kernels and the extent stay)
+    plan->stride_h = stride_h; plan->stride_w = stride_w;
     return 0;
 }
 
@@ -844,6 +859,12 @@ int fftconv_plan_get_option(fftconv_plan* plan, const char* name, long* value) {
     if (!strcmp(name, "rect_off_w")) { *value = plan->opt_region == 5 ? plan->off_w : 0; return 0; }
     if (!strcmp(name, "rect_direct")) { *value = plan->rect_direct() ? 1 : 0; return 0; }
     if (!strcmp(name, "rect_store")) { *value = plan->opt_rect_store; return 0; }
+    // strided maps (fftconv_plan_set_output_stride), read-only: the strides, and whether the output kernel samples in its store with
+    // the plan's current settings (else the staged crop does); "stride_store": the plan's own (a block-wise plan always crops)
+    if (!strcmp(name, "stride_h")) { *value = plan->stride_h; return 0; }
+    if (!strcmp(name, "stride_w")) { *value = plan->stride_w; return 0; }
+    if (!strcmp(name, "stride_direct")) { *value = plan->stride_direct() ? 1 : 0; return 0; }
+    if (!strcmp(name, "stride_store")) { *value = plan->opt_stride_store; return 0; }
     // read-only: 1 if, with the plan's current settings, the output kernel itself scales normalised maps (else the staged crop does)
     if (!strcmp(name, "normalise")) { *value = plan->opt_score == FC_SCORE_CCOEFF_NORMED ? 1 : 0; return 0; }      // (mode 1 is score 1)
     if (!strcmp(name, "norm_direct")) { *value = plan->norm_direct() ? 1 : 0; return 0; }

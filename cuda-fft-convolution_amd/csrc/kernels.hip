@@ -73,23 +73,24 @@ __global__ void __launch_bounds__(256) k_add_window(float* __restrict__ dst, int
 }
 
 // dst map (dst_h x dst_w, contiguous) = the window [off_h, off_h + dst_h) x [off_w, off_w + dst_w) of the
-// src map (src_h rows per column): the "full" / "same" / "valid" regions of the padded window
+// src map (src_h rows per column): the "full" / "same" / "valid" regions of the padded window; sampled at the strides (sh, sw)
+// from the window's first row and column (strided maps; 1, 1: the plain crop)
 __global__ void __launch_bounds__(256) k_crop_maps(const float* __restrict__ src, int src_h, size_t src_map_stride, float* __restrict__ dst,
-                                                   int dst_h, int dst_w, size_t dst_map_stride, int off_h, int off_w) {
+                                                   int dst_h, int dst_w, size_t dst_map_stride, int off_h, int off_w, int sh, int sw) {
     const int x = (int)blockIdx.x, map = (int)blockIdx.y;
-    const float* s = src + (size_t)map * src_map_stride + (size_t)(off_w + x) * src_h + off_h;
+    const float* s = src + (size_t)map * src_map_stride + (size_t)(off_w + x * sw) * src_h + off_h;
     float* d = dst + (size_t)map * dst_map_stride + (size_t)x * dst_h;
-    for (int y = (int)threadIdx.x; y < dst_h; y += (int)blockDim.x) d[y] = s[y];
+    for (int y = (int)threadIdx.x; y < dst_h; y += (int)blockDim.x) d[y] = s[(size_t)y * sh];
 }
 
 // the same into 16-bit maps (fp16 / bf16: fc_map16): the source is the fp32 full-window staging.  Region maps can have an odd
 // out_h and an odd element count, so the destination is only 2-byte aligned: one element per store.
 __global__ void __launch_bounds__(256) k_crop_maps16(const float* __restrict__ src, int src_h, size_t src_map_stride, uint16_t* __restrict__ dst,
-                                                     int dst_h, int dst_w, size_t dst_map_stride, int off_h, int off_w, int bf16) {
+                                                     int dst_h, int dst_w, size_t dst_map_stride, int off_h, int off_w, int sh, int sw, int bf16) {
     const int x = (int)blockIdx.x, map = (int)blockIdx.y;
-    const float* s = src + (size_t)map * src_map_stride + (size_t)(off_w + x) * src_h + off_h;
+    const float* s = src + (size_t)map * src_map_stride + (size_t)(off_w + x * sw) * src_h + off_h;
     uint16_t* d = dst + (size_t)map * dst_map_stride + (size_t)x * dst_h;
-    for (int y = (int)threadIdx.x; y < dst_h; y += (int)blockDim.x) d[y] = fc_map16(s[y], bf16 != 0);
+    for (int y = (int)threadIdx.x; y < dst_h; y += (int)blockDim.x) d[y] = fc_map16(s[(size_t)y * sh], bf16 != 0);
 }
 
 // Image spectrum between the engine's internal order and the reference's natural order
@@ -174,14 +175,15 @@ hipError_t launch_add_window(float* dst, int dst_h, int dst_w, size_t dst_map_st
 }
 
 hipError_t launch_crop_maps(const float* src, int src_h, size_t src_map_stride, float* dst, int dst_h, int dst_w, size_t dst_map_stride,
-                            int off_h, int off_w, int nmaps, hipStream_t s, int format, const MapPlane& plane) {
+                            int off_h, int off_w, int nmaps, hipStream_t s, int format, const MapPlane& plane, int stride_h, int stride_w) {
     if (nmaps <= 0 || dst_h <= 0 || dst_w <= 0) return hipSuccess;
-    if (!maps_plane_ok(plane)) return hipErrorInvalidValue;
-    const MapsLaunch l{src, src_h, 0, src_map_stride, dst, dst_h, dst_w, dst_map_stride, off_h, off_w, nmaps, format, s};
+    if (!maps_plane_ok(plane) || stride_h < 1 || stride_w < 1) return hipErrorInvalidValue;
+    const MapsLaunch l{src, src_h, 0, src_map_stride, dst, dst_h, dst_w, dst_map_stride, off_h, off_w, nmaps, format, s, stride_h, stride_w};
+    const int sh = stride_h, sw = stride_w;
     if (plane.kind == PlaneKind::Scale) return crop_maps_scaled(l, plane);
     if (plane.kind == PlaneKind::Add) return crop_maps_added(l, plane);
-    return l.run([&](dim3 g, dim3 b, uint16_t* d, int bf16) { hipLaunchKernelGGL(k_crop_maps16, g, b, 0, s, src, src_h, src_map_stride, d, dst_h, dst_w, dst_map_stride, off_h, off_w, bf16); },
-                 [&](dim3 g, dim3 b, float* d, int) { hipLaunchKernelGGL(k_crop_maps, g, b, 0, s, src, src_h, src_map_stride, d, dst_h, dst_w, dst_map_stride, off_h, off_w); });
+    return l.run([&](dim3 g, dim3 b, uint16_t* d, int bf16) { hipLaunchKernelGGL(k_crop_maps16, g, b, 0, s, src, src_h, src_map_stride, d, dst_h, dst_w, dst_map_stride, off_h, off_w, sh, sw, bf16); },
+                 [&](dim3 g, dim3 b, float* d, int) { hipLaunchKernelGGL(k_crop_maps, g, b, 0, s, src, src_h, src_map_stride, d, dst_h, dst_w, dst_map_stride, off_h, off_w, sh, sw); });
 }
 
 // ---- the specialised kernels: their translation units (kernels_*_g<G>.hip) hold one group of configurations each; the
@@ -225,6 +227,11 @@ hipError_t launch_fast_cols_rect(int M, int T, const FastColsShape& shape, hipSt
     if (!shape.a.y_tiled || (shape.variant != FastColsVariant::TILED && shape.variant != FastColsVariant::TILED_DYN)) return hipErrorInvalidValue;
     const bool f32 = shape.a.out_format == FC_MAP_F32;
     const MapPlane& pl = shape.plane;
+    if (shape.strided) {
+        // (fp32, no plane; the reciprocals of the strides are exact for extents below 2^16: fast_cols.hpp, StrideDiv)
+        if (!f32 || pl.kind != PlaneKind::None || shape.a.fft_h - shape.a.h_lo >= 65536 || shape.a.rect_w_n >= 65536) return hipErrorInvalidValue;
+        return in_first_group<FC_COL_GROUPS>([&](auto g) { return launch_fast_cols_rect_stride_group<g.value>(M, T, shape, s); });
+    }
     if (pl.kind == PlaneKind::Scale) {
         if (!f32 || !pl.plane || pl.per_image < 1) return hipErrorInvalidValue;
         return in_first_group<FC_COL_GROUPS>([&](auto g) { return launch_fast_cols_rect_scale_group<g.value>(M, T, shape, s); });

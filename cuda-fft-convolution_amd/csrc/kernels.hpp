@@ -22,8 +22,11 @@ hipError_t launch_add_window(float* dst, int dst_h, int dst_w, size_t dst_map_st
 // (plane: every element is combined with the plane at its WINDOW coordinate on the way -- Scale: times D; Add: s + (Q + c), c =
 //  consts[m % per_image] for map m of the launch -- the planes [image][src_w][src_h], src_map_stride apart; map m belongs to image
 //  first / per_image + m / per_image, first a multiple of per_image.  The kernels: kernels_ncc.hip (Scale), kernels_score.hip (Add))
+// (stride_h, stride_w: strided maps, fftconv_plan_set_output_stride -- dst element (y, x) is the window's (off_h + y * stride_h,
+//  off_w + x * stride_w), dst_h and dst_w counting the SAMPLED rows and columns; the plane is read at that window coordinate)
 hipError_t launch_crop_maps(const float* src, int src_h, size_t src_map_stride, float* dst, int dst_h, int dst_w, size_t dst_map_stride,
-                            int off_h, int off_w, int nmaps, hipStream_t s, int format = FC_MAP_F32, const MapPlane& plane = {});
+                            int off_h, int off_w, int nmaps, hipStream_t s, int format = FC_MAP_F32, const MapPlane& plane = {},
+                            int stride_h = 1, int stride_w = 1);
 // natural [f][fw][ch] <-> internal image-spectrum order (see kernels.hip: k_spectrum_reorder)
 hipError_t launch_spectrum_reorder(bool to_natural, c32* S, size_t s_plane, int s_pitch, c32* nat, int fw, int ch, int planes,
                                    const int* row_of, const int* col_of, float scale, hipStream_t s);
@@ -42,6 +45,7 @@ struct MapsLaunch {
     size_t dst_map_stride;
     int off_h, off_w, nmaps, format;
     hipStream_t s;
+    int stride_h = 1, stride_w = 1;      // crops only
     // k16 / k32(grid, block, dst as the kernel takes it, bf16): the fp32 and the 16-bit launch of a crop or pad kernel, written once
     template <class K16, class K32>
     hipError_t run(K16&& k16, K32&& k32) const {
@@ -95,8 +99,9 @@ hipError_t launch_fast_rows_images(int L, const FastRowsArgs& a, int rows, int i
 hipError_t launch_fast_cols(int M, int T, const FastColsArgs& a, int num_cus, hipStream_t s);
 // the rectangle family of the output kernel (fast_cols.hpp: RECT, and on it NORM and ADD): `shape` from fast_cols_rect_launch_shape
 // (fast_paths.hpp) -- shape.plane picks the fused scale of normalised maps (Scale) or the fused additive store of score 4 (Add), both
-// fp32 only; without a plane the rectangle store in shape.a.out_format.  hipErrorInvalidValue for a launch the family does not have
-// (row-major or sliced), for a plane that is not filled in, and for a configuration whose kernel is not built (fast_cols_*_built)
+// fp32 only; without a plane the rectangle store in shape.a.out_format.  A shape from fast_cols_stride_launch_shape (shape.strided) runs
+// the strided store: fp32 maps, no plane.  hipErrorInvalidValue for a launch the family does not have (row-major or sliced), for a
+// plane that is not filled in, and for a configuration whose kernel is not built (fast_cols_*_built)
 hipError_t launch_fast_cols_rect(int M, int T, const FastColsShape& shape, hipStream_t s);
 hipError_t launch_fast_cols_fwd(int M, int T, bool pruned, const FastColsFwdArgs& a, int num_cus, hipStream_t s);
 // image columns of typed pixels (kernels_cols_fwd_px_g<G>.hip; pixel_format.hpp): a.in holds elements of px.format, px from
@@ -134,6 +139,8 @@ template <int G> GroupResult launch_fast_cols_rect_group(int M, int T, const Fas
 template <int G> GroupResult launch_fast_cols_rect16_group(int M, int T, const FastColsShape& shape, hipStream_t s);
 template <int G> GroupResult launch_fast_cols_rect_scale_group(int M, int T, const FastColsShape& shape, hipStream_t s);
 template <int G> GroupResult launch_fast_cols_rect_add_group(int M, int T, const FastColsShape& shape, hipStream_t s);
+// (the strided store: kernels_cols_stride_g<G>.hip)
+template <int G> GroupResult launch_fast_cols_rect_stride_group(int M, int T, const FastColsShape& shape, hipStream_t s);
 template <int G> GroupResult launch_fast_cols_fwd_group(int M, int T, bool pruned, const FastColsFwdArgs& a, int num_cus, hipStream_t s);
 // (typed image pixels: kernels_cols_fwd_px_g<G>.hip)
 template <int G> GroupResult launch_fast_cols_fwd_px_group(int M, int T, const FastColsFwdArgs& a, const PixelLoad& px, int num_cus, hipStream_t s);

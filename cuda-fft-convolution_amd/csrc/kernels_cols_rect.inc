@@ -1,12 +1,14 @@
 // kernels_cols_rect.inc -- the rectangle family of the output-column kernel (fast_cols.hpp: the RECT stores; plan entry
 // fftconv_plan_set_output_rect): the maps are a dense rectangle of the window, written by the output kernel itself.  Included with
-// FC_TU_GROUP = G, as kernels_cols.inc is, by four kinds of translation unit, one kernel each:
+// FC_TU_GROUP = G, as kernels_cols.inc is, by five kinds of translation unit, one kernel each:
 //   kernels_cols_rect_g<G>.hip                       k_fast_cols_rect     fp32 maps
 //   kernels_cols_rect16_g<G>.hip    FC_TU_OUT16 = 1  k_fast_cols_rect16   16-bit maps
 //   kernels_cols_norm_g<G>.hip      FC_TU_NORM = 1   k_fast_cols_norm     fp32 maps times the scale plane of normalised maps (NORM;
 //                                                                         fftconv_plan_set_normalisation, scores 1 and 3)
 //   kernels_cols_sqdiff_g<G>.hip    FC_TU_SQDIFF = 1 k_fast_cols_sqdiff   fp32 maps plus Q + c of matching score 4 (ADD;
 //                                                                         fftconv_plan_set_match_score)
+//   kernels_cols_stride_g<G>.hip    FC_TU_STRIDE = 1 k_fast_cols_stride   fp32 maps, every sh-th row and sw-th column (STRIDE;
+//                                                                         fftconv_plan_set_output_stride)
 // Translation units of their own, so that every other kernel compiles exactly what it compiled before, and kernel names of their
 // own, so that no report filter of one family picks up another.  Tiled intermediate and unsliced launches only: two instantiations
 // (static deal, dynamic tile queue) per configuration and kernel.  A plan without a rectangle launches the NORM / ADD kernels with
@@ -22,13 +24,26 @@
 #ifndef FC_TU_SQDIFF
 #define FC_TU_SQDIFF 0
 #endif
+#ifndef FC_TU_STRIDE
+#define FC_TU_STRIDE 0
+#endif
 
 namespace fc {
 namespace {
 
 // FC_RECT_KERNEL: the unit's kernel; FC_RECT_GROUP / FC_RECT_BUILT: its group entry (kernels.hpp) and its list of built configurations
 // (fast_paths.hpp); FC_RECT_ARGS(sh): the kernel's arguments from the launch shape -- the plane's device struct is filled here
-#if FC_TU_SQDIFF
+#if FC_TU_STRIDE
+#define FC_RECT_KERNEL k_fast_cols_stride
+#define FC_RECT_GROUP launch_fast_cols_rect_stride_group
+#define FC_RECT_BUILT fast_cols_stride_built
+#define FC_RECT_ARGS(sh) (sh).a, (sh).stride
+template <class Cfg, bool DYN>
+__global__ void __launch_bounds__(Cfg::NT, 3) k_fast_cols_stride(FastColsArgs a, FastColsStrideArgs st) {
+    DevPhaseCtx<ColPairState<Cfg>> ctx;
+    fast_cols_body<Cfg, true, false, DYN, ColStore::RECT_STRIDE>(ctx, reinterpret_cast<c32*>(fc_smem), a, (int)blockIdx.x, (int)gridDim.x, st);
+}
+#elif FC_TU_SQDIFF
 #define FC_RECT_KERNEL k_fast_cols_sqdiff
 #define FC_RECT_GROUP launch_fast_cols_rect_add_group
 #define FC_RECT_BUILT fast_cols_sqdiff_built

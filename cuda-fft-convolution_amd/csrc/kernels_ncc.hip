@@ -56,17 +56,17 @@ __global__ void __launch_bounds__(256) k_ncc_unit_kernels(const float* __restric
 }
 
 // NORM siblings of k_crop_maps / k_crop_maps16 (kernels.hip): the element is scaled by D at its WINDOW coordinate while it is
-// cropped and converted.  Map `map` of the launch belongs to image image0 + map / per_image (ncc_image_of); D: [image][src_w][src_h]
+// cropped (sampled at the strides sh, sw: strided maps) and converted.  Map `map` of the launch belongs to image image0 + map / per_image (ncc_image_of); D: [image][src_w][src_h]
 template <bool OUT16>
 __global__ void __launch_bounds__(256) k_crop_maps_norm(const float* __restrict__ src, int src_h, size_t src_map_stride,
                                                         std::conditional_t<OUT16, uint16_t, float>* __restrict__ dst, int dst_h, size_t dst_map_stride,
-                                                        int off_h, int off_w, const float* __restrict__ D, int image0, int per_image, int bf16) {
+                                                        int off_h, int off_w, int sh, int sw, const float* __restrict__ D, int image0, int per_image, int bf16) {
     const int x = (int)blockIdx.x, map = (int)blockIdx.y;
-    const size_t at = (size_t)(off_w + x) * src_h + off_h;
+    const size_t at = (size_t)(off_w + x * sw) * src_h + off_h;
     const float* s = src + (size_t)map * src_map_stride + at;
     const float* sc = D + (size_t)ncc_image_of(image0, map, per_image) * src_map_stride + at;
     auto* d = dst + (size_t)map * dst_map_stride + (size_t)x * dst_h;
-    for (int y = (int)threadIdx.x; y < dst_h; y += (int)blockDim.x) put<OUT16>(d + y, s[y] * sc[y], bf16);
+    for (int y = (int)threadIdx.x; y < dst_h; y += (int)blockDim.x) put<OUT16>(d + y, s[(size_t)y * sh] * sc[(size_t)y * sh], bf16);
 }
 
 // ... and of k_pad_maps / k_pad_maps16
@@ -136,7 +136,7 @@ void launch_ncc_plane_stats(const float* src, int planes, int plane_elems, doubl
 hipError_t crop_maps_scaled(const MapsLaunch& l, const MapPlane& pl) {
     const int image0 = pl.first / pl.per_image;
     auto launch = [&](auto kernel, dim3 g, dim3 b, auto* d, int bf16) {
-        hipLaunchKernelGGL(kernel, g, b, 0, l.s, l.src, l.src_h, l.src_map_stride, d, l.dst_h, l.dst_map_stride, l.off_h, l.off_w, pl.plane, image0, pl.per_image, bf16);
+        hipLaunchKernelGGL(kernel, g, b, 0, l.s, l.src, l.src_h, l.src_map_stride, d, l.dst_h, l.dst_map_stride, l.off_h, l.off_w, l.stride_h, l.stride_w, pl.plane, image0, pl.per_image, bf16);
     };
     return l.run([&](dim3 g, dim3 b, uint16_t* d, int bf16) { launch(k_crop_maps_norm<true>, g, b, d, bf16); },
                  [&](dim3 g, dim3 b, float* d, int bf16) { launch(k_crop_maps_norm<false>, g, b, d, bf16); });

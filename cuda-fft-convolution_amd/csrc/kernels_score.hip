@@ -36,15 +36,15 @@ __global__ void __launch_bounds__(FC_NCC_LANES) k_score_kernels(const float* __r
 template <bool OUT16>
 __global__ void __launch_bounds__(256) k_crop_maps_sqdiff(const float* __restrict__ src, int src_h, size_t src_map_stride,
                                                           std::conditional_t<OUT16, uint16_t, float>* __restrict__ dst, int dst_h, size_t dst_map_stride,
-                                                          int off_h, int off_w, const float* __restrict__ Q, const float* __restrict__ consts, int image0,
-                                                          int per_image, int bf16) {
+                                                          int off_h, int off_w, int sh, int sw, const float* __restrict__ Q, const float* __restrict__ consts,
+                                                          int image0, int per_image, int bf16) {
     const int x = (int)blockIdx.x, map = (int)blockIdx.y;
-    const size_t at = (size_t)(off_w + x) * src_h + off_h;
+    const size_t at = (size_t)(off_w + x * sw) * src_h + off_h;
     const float* s = src + (size_t)map * src_map_stride + at;
     const float* q = Q + (size_t)ncc_image_of(image0, map, per_image) * src_map_stride + at;
     const float c = consts[map % per_image];
     auto* d = dst + (size_t)map * dst_map_stride + (size_t)x * dst_h;
-    for (int y = (int)threadIdx.x; y < dst_h; y += (int)blockDim.x) put<OUT16>(d + y, score_sqdiff(s[y], q[y], c), bf16);
+    for (int y = (int)threadIdx.x; y < dst_h; y += (int)blockDim.x) put<OUT16>(d + y, score_sqdiff(s[(size_t)y * sh], q[(size_t)y * sh], c), bf16);
 }
 template <bool OUT16>
 __global__ void __launch_bounds__(256) k_pad_maps_sqdiff(const float* __restrict__ src, int src_h, int src_w, size_t src_map_stride,
@@ -80,7 +80,7 @@ hipError_t launch_score_kernels(int score, const float* src, float* dst, int n, 
 hipError_t crop_maps_added(const MapsLaunch& l, const MapPlane& pl) {
     const int image0 = pl.first / pl.per_image;
     auto launch = [&](auto kernel, dim3 g, dim3 b, auto* d, int bf16) {
-        hipLaunchKernelGGL(kernel, g, b, 0, l.s, l.src, l.src_h, l.src_map_stride, d, l.dst_h, l.dst_map_stride, l.off_h, l.off_w, pl.plane, pl.consts, image0,
+        hipLaunchKernelGGL(kernel, g, b, 0, l.s, l.src, l.src_h, l.src_map_stride, d, l.dst_h, l.dst_map_stride, l.off_h, l.off_w, l.stride_h, l.stride_w, pl.plane, pl.consts, image0,
                            pl.per_image, bf16);
     };
     return l.run([&](dim3 g, dim3 b, uint16_t* d, int bf16) { launch(k_crop_maps_sqdiff<true>, g, b, d, bf16); },

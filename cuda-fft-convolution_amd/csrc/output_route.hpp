@@ -13,16 +13,20 @@
 //             Rect -- region 5 with "rect_store" on a one-pass plan whose rectangle kernel is built, no plane; RectScale (D, Dc) /
 //             RectAdd (Q + c) -- a plane with "norm_store", fp32 maps, region 0 or 5, a one-pass plan whose NORM / ADD kernel is
 //             built: the rectangle is the plan's (extent Rect) or the whole window standing in for one (extent Window).
+//             RectStride -- strided maps (fftconv_plan_set_output_stride: a stride other than (1, 1)) with "stride_store" on, fp32
+//             maps, no plane, region 0 or 5, a one-pass plan on the tiled intermediate whose STRIDE kernel is built: the kernel stores
+//             the sampled rows and columns of the extent densely.  Every other strided group is sampled by the crop (after).
 //   after     what follows the kernel: a region other than the window that the kernel did not store itself, and every plane it did not
 //             combine itself (region 0 included: the crop of the whole window), go through the fp32 window in O and are cropped --
-//             region 4: padded -- into the maps, times or plus the plane on the way.
+//             region 4: padded -- into the maps, times or plus the plane on the way.  A stride the kernel did not sample itself is
+//             the crop's too, region 0 included (region 4 takes no stride: fftconv_plan_set_output_stride refuses it).
 //   format    kernel_format: what the output kernel stores -- fp32 whenever a crop follows, else "map_format"; map_format: the maps'.
 //   target    where the kernel writes: O when a crop follows, else the staging buffer of a staged route, else the caller's memory.
 //   buffers   O for the crop (need_O), and the staging of Copies / Pinned / Ring (staging, twice for the ring: staging_copies): OC
 //             for everything the kernel or the crop stores densely -- region maps, rectangles, every fused plane, region 0 included --
 //             else O.
 //   tuning    a score with a plane is never tuned and leaves the intermediate marked fresh (Skip); a window is never probed (None);
-//             else the probes are the group's own launch, Rect or Plain, into `target` -- every batch's destination when that is the
+//             else the probes are the group's own launch, Rect (the strided launch of RectStride included) or Plain, into `target` -- every batch's destination when that is the
 //             caller's memory, else the one staging buffer.
 //   error     an output window on a plan without the specialised output kernel, or with any score on: refused.
 #pragma once
@@ -44,7 +48,7 @@ enum class Route {
     Ring,     // host maps of at least host_min_kb: two staging buffers, the copy-out of batch b overlaps the compute of batch b + 1
 };
 enum class SinkKind { Window, Packed, DevicePtrs, Host };
-enum class OutStore { Generic, Plain, Rect, RectScale, RectAdd };
+enum class OutStore { Generic, Plain, Rect, RectScale, RectAdd, RectStride };
 enum class OutPlane { None, D, Dc, Q };           // D, Dc: multiplied; Q: added with the constant of the map's kernel
 enum class OutBuffer { Caller, O, OC };
 enum class OutExtent { Window, Region, Rect };    // what a delivered map holds: "output_region" 0, 1-4, 5
@@ -64,6 +68,10 @@ struct OutputRouteIn {
     int map_format = FC_MAP_F32;
     bool fast_cols = false, y_tiled = false;   // the plan has the specialised output kernel; its intermediate is tiled
     bool rect_built = false, norm_built = false, sqdiff_built = false;      // fast_paths.hpp: fast_cols_*_built of the plan's M
+    // strided maps (fftconv_plan_set_output_stride); the defaults are "no stride"
+    int stride_h = 1, stride_w = 1;
+    bool stride_store = true, stride_built = false;
+    bool strided() const { return stride_h != 1 || stride_w != 1; }
 };
 
 struct OutputRoute {
@@ -95,12 +103,14 @@ inline OutputRoute plan_output_route(const OutputRouteIn& in) {
     const bool one_pass_tiled = !window && !in.blockwise && in.fast_cols && in.y_tiled;      // (a tiled intermediate implies the kernel)
     if (r.plane != OutPlane::None) {
         const bool built = r.plane == OutPlane::Q ? in.sqdiff_built : in.norm_built;
-        if (one_pass_tiled && in.norm_store && in.map_format == FC_MAP_F32 && r.extent != OutExtent::Region && built)
+        if (one_pass_tiled && in.norm_store && in.map_format == FC_MAP_F32 && r.extent != OutExtent::Region && built && !in.strided())      // (no fused plane + stride)
             r.store = r.plane == OutPlane::Q ? OutStore::RectAdd : OutStore::RectScale;
+    } else if (in.strided()) {
+        if (one_pass_tiled && in.stride_store && in.stride_built && in.map_format == FC_MAP_F32 && r.extent != OutExtent::Region) r.store = OutStore::RectStride;
     } else if (one_pass_tiled && r.extent == OutExtent::Rect && in.rect_store && in.rect_built) r.store = OutStore::Rect;
     if (r.store == OutStore::Generic && in.fast_cols) r.store = OutStore::Plain;
-    const bool dense = r.store == OutStore::Rect || r.fused();      // the kernel stores the delivered maps itself
-    if (!dense && (r.extent != OutExtent::Window || r.plane != OutPlane::None)) r.after = in.region == 4 ? OutAfter::Pad : OutAfter::Crop;
+    const bool dense = r.store == OutStore::Rect || r.store == OutStore::RectStride || r.fused();      // the kernel stores the delivered maps itself
+    if (!dense && (r.extent != OutExtent::Window || r.plane != OutPlane::None || in.strided())) r.after = in.region == 4 ? OutAfter::Pad : OutAfter::Crop;
     const bool cropped = r.after != OutAfter::None;
     r.map_format = in.map_format;
     r.kernel_format = cropped ? FC_MAP_F32 : in.map_format;
@@ -117,7 +127,8 @@ inline OutputRoute plan_output_route(const OutputRouteIn& in) {
         r.staging_copies = r.route == Route::Ring ? 2 : 1;
     }
     r.target = cropped ? OutBuffer::O : r.staging;
-    r.probe = r.plane != OutPlane::None ? TuneProbe::Skip : window ? TuneProbe::None : r.store == OutStore::Rect ? TuneProbe::Rect : TuneProbe::Plain;
+    r.probe = r.plane != OutPlane::None ? TuneProbe::Skip : window ? TuneProbe::None
+              : r.store == OutStore::Rect || r.store == OutStore::RectStride ? TuneProbe::Rect : TuneProbe::Plain;
     return r;
 }
 

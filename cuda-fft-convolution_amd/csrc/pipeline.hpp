@@ -430,4 +430,15 @@ inline const char* output_rect_error(long off_h, long off_w, long out_h, long ou
     return nullptr;
 }
 
+// fftconv_plan_set_output_stride and "output_region": why a plan cannot have the strides (stride_h, stride_w) and that region at once,
+// or nullptr if it can.  Region 4 is the window PADDED to the next power of two, not a sampling of the window: it takes no stride
+// other than (1, 1), whichever of the two is asked for last.
+inline const char* output_stride_error(long stride_h, long stride_w, long region) {
+    if (stride_h < 1 || stride_w < 1) return "output stride: stride_h and stride_w must be at least 1";
+    if ((stride_h != 1 || stride_w != 1) && region == 4)
+        return "output stride: output_region 4 (the pow2-padded window) is not a sampling of the window and takes no stride; "
+               "set the stride back to (1, 1) or choose another region";
+    return nullptr;
+}
+
 }  // namespace fc

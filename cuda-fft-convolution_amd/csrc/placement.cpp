@@ -33,8 +33,8 @@ int tune_intermediate_placement(fftconv_plan* p, const OutputRoute& route, int n
     int k = route.probe == TuneProbe::None ? 0 : (int)p->opt_tune_placement;
     const int format = route.kernel_format;           // of what the output kernel writes at `out` (fp32 into the full-window staging of a cropped region)
     const size_t eb = fc_map_elem_bytes(format);
-    // (a route whose output kernel stores the caller's rectangle itself is probed with exactly that launch: `out` is sized for
-    // the dense rectangles, full-window probes would overrun it)
+    // (a route whose output kernel stores the caller's rectangle itself -- or its strided maps -- is probed with exactly that launch:
+    // `out` is sized for the dense rectangles or the strided maps, full-window probes would overrun it)
     const bool rect = route.probe == TuneProbe::Rect;
     const bool direct = route.target == OutBuffer::Caller;      // the output kernel writes the caller's packed maps, from `out` on
     if (k < 0) k = placement_auto_candidates(p, (size_t)std::min(nbY, n) * (rect ? p->out_elems() : g.map_elems()) * eb);

@@ -298,7 +298,25 @@ struct fftconv_plan {
     DevBuf<float> ND, KN, KC;
     DevBuf<double> NS64;
     DevBuf<float> OC;  // cropped maps staged for the copy-out
-    size_t out_elems() const { return opt_region ? (size_t)out_h * out_w : g.map_elems(); }   // (block-wise plans: g holds the whole window)
+    // fftconv_plan_set_output_stride: the delivered map S holds every stride_h-th row and stride_w-th column of the extent U the plan
+    // would deliver without it (the window, a region, the rectangle: ext_h x ext_w at off_h, off_w), counted from U's first row and
+    // column -- map_h x map_w elements, dense.  Output-side state of its own: it keeps the image and the prepared kernels, and it
+    // stays while the extent changes (out_h, out_w, off_h, off_w always describe U).  "stride_store" 1: the specialised output kernel
+    // samples in its store where it can (fast_cols.hpp: STRIDE) -- OutStore::RectStride; 0, and every plan it cannot serve: the fp32
+    // window goes through O and the crop samples it (output_route.hpp).
+    int stride_h = 1, stride_w = 1;
+    long opt_stride_store = 1;
+    bool strided() const { return stride_h != 1 || stride_w != 1; }
+    int ext_h() const { return opt_region ? out_h : g.fft_h; }
+    int ext_w() const { return opt_region ? out_w : g.fft_w; }
+    int map_h() const { return strided_count(ext_h(), stride_h); }
+    int map_w() const { return strided_count(ext_w(), stride_w); }
+    // read-only option "stride_direct": the store of the route of a sink that is not a window
+    bool stride_direct() const { return plan_output_route(output_route_in(this, SinkKind::Packed)).store == OutStore::RectStride; }
+    size_t out_elems() const {      // (block-wise plans: g holds the whole window)
+        if (strided()) return (size_t)map_h() * map_w();
+        return opt_region ? (size_t)out_h * out_w : g.map_elems();
+    }
     // "map_format": element format of every result map (fc_common.hpp: FC_MAP_*; one-pass plans only).  The staging buffers O / OC
     // stay arrays of float that are sized in bytes and addressed through map_at; the full-window buffer a crop reads is always fp32.
     long opt_map_format = 0;
@@ -497,7 +515,7 @@ int launch_output_cols(fftconv_plan* p, const OutputRoute& r, const OutWindow* w
 int launch_region(const fftconv_plan* p, const OutputRoute& r, const float* src, float* dst, int nmaps, hipStream_t s, const OutLaunch& l = {});
 // the maps [first, first + ny) are queued into `dest` (staging buffer buf of a streamed group): their way to the caller
 int deliver_batch(fftconv_plan* p, const Delivery& d, const Sink& sink, int first, int ny, int buf, const float* dest);
-// the rectangle launch of a route whose store is Rect, RectScale or RectAdd: ny maps from the intermediate y, dense from `out` on
+// the rectangle launch of a route whose store is Rect, RectScale, RectAdd or RectStride: ny maps from the intermediate y, dense from `out` on
 FastColsShape output_rect_shape(const fftconv_plan* p, const OutputRoute& r, const c32* y, float* out, int ny, const OutLaunch& l = {});
 
 // ---- host-output streaming (host_ring.cpp) ----

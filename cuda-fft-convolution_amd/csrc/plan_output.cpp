@@ -43,6 +43,7 @@ OutputRouteIn output_route_in(const fftconv_plan* p, SinkKind sink) {
     in.map_format = (int)p->opt_map_format;
     in.fast_cols = g.fast_cols.ok; in.y_tiled = g.y_tiled();
     in.rect_built = fast_cols_rect_built(g.M); in.norm_built = fast_cols_norm_built(g.M); in.sqdiff_built = fast_cols_sqdiff_built(g.M);
+    in.stride_h = p->stride_h; in.stride_w = p->stride_w; in.stride_store = p->opt_stride_store != 0; in.stride_built = fast_cols_stride_built(g.M);
     return in;
 }
 
@@ -67,11 +68,15 @@ int plan_delivery(fftconv_plan* p, const Sink& sink, int nbY, Delivery& d) {
 }
 
 // the launch that stores ny maps of the route's rectangle -- the plan's, or the whole window standing in for one -- from the
-// intermediate y, dense from `out` on; a fused route (RectScale, RectAdd): with the plane of the launch's images and kernels
+// intermediate y, dense from `out` on; a fused route (RectScale, RectAdd): with the plane of the launch's images and kernels; RectStride:
+// the strided launch of that extent
 FastColsShape output_rect_shape(const fftconv_plan* p, const OutputRoute& r, const c32* y, float* out, int ny, const OutLaunch& l) {
     const Geometry& g = p->g;
     const bool whole = r.extent == OutExtent::Window;
     const FastColsArgs fa = fast_cols_args(g, p->d, y, out, p->out_elems(), ny, r.kernel_format);
+    if (r.store == OutStore::RectStride)
+        return fast_cols_stride_launch_shape(g.fast_cols.T, fa, whole ? 0 : p->off_h, whole ? 0 : p->off_w, p->ext_h(), p->ext_w(), p->stride_h, p->stride_w,
+                                             persistent_want(g.fast_cols.lds_bytes, g.fast_cols.NT, p->num_cus));
     return fast_cols_rect_launch_shape(g.fast_cols.T, fa, whole ? 0 : p->off_h, whole ? 0 : p->off_w, whole ? g.fft_h : p->out_h, whole ? g.fft_w : p->out_w,
                                        persistent_want(g.fast_cols.lds_bytes, g.fast_cols.NT, p->num_cus), r.fused() ? output_plane(p, r, l) : MapPlane{});
 }
@@ -101,7 +106,11 @@ int launch_output_cols(fftconv_plan* p, const OutputRoute& r, const OutWindow* w
         static const char* const fused[] = {"", "scaled by D (normalisation: fused)", "scaled by Dc (normalisation: fused CCORR_NORMED)",
                                             "plus Q + c (normalisation: fused SQDIFF)"};      // OutPlane
         const FastColsShape sh = output_rect_shape(p, r, p->Y.p, obase, ny, l);
-        if (r.fused())
+        if (r.store == OutStore::RectStride)
+            FC_VERBOSE(p, "output kernel: tiled rectangle, stride (%d, %d) fused in the store (%s), %d workgroups on %d tiles, fp32 elements, rows [%d, %d) of columns [%d, %d) into %d x %d maps",
+                       p->stride_h, p->stride_w, sh.a.rect_wide ? "pair stores" : "element stores", sh.grid, sh.a.ntiles, sh.a.h_lo, sh.a.fft_h, sh.a.rect_w_lo,
+                       sh.a.rect_w_lo + p->ext_w(), p->map_h(), p->map_w());
+        else if (r.fused())
             FC_VERBOSE(p, "output kernel: tiled rectangle %s, %d workgroups, fp32 elements, rows [%d, %d) of columns [%d, %d), images %d..", fused[(int)r.plane],
                        sh.grid, sh.a.h_lo, sh.a.fft_h, sh.a.rect_w_lo, sh.a.rect_w_lo + sh.a.rect_w_n, l.image0);
         else
@@ -117,7 +126,11 @@ int launch_output_cols(fftconv_plan* p, const OutputRoute& r, const OutWindow* w
 int launch_region(const fftconv_plan* p, const OutputRoute& r, const float* src, float* dst, int nmaps, hipStream_t s, const OutLaunch& l) {
     const Geometry& g = p->g;      // (block-wise plans: g holds the whole window)
     const bool whole = r.extent == OutExtent::Window, pad = r.after == OutAfter::Pad;
-    const int oh = whole ? g.fft_h : p->out_h, ow = whole ? g.fft_w : p->out_w, fh = whole ? 0 : p->off_h, fw = whole ? 0 : p->off_w;
+    const int fh = whole ? 0 : p->off_h, fw = whole ? 0 : p->off_w;
+    const int oh = pad ? p->out_h : p->map_h(), ow = pad ? p->out_w : p->map_w();      // of a delivered map (a stride: the sampled rows and columns; never padded)
+    if (p->strided())
+        FC_VERBOSE(p, "output stride (%d, %d): staged -- sampled by the crop from rows [%d, %d) of columns [%d, %d) of the fp32 window", p->stride_h, p->stride_w, fh,
+                   fh + p->ext_h(), fw, fw + p->ext_w());
     const char* const how = pad ? "padded" : "cropped";
     const char* const format = kMapFormatNames[r.map_format];      // of dst; src is fp32
     if (r.plane != OutPlane::None) {
@@ -126,11 +139,11 @@ int launch_region(const fftconv_plan* p, const OutputRoute& r, const float* src,
         FC_VERBOSE(p, "normalisation: %s -- %d maps of images %d.. %s while %s from the fp32 window into %d x %d %s maps", staged[(int)r.plane], nmaps, l.image0,
                    combined[(int)r.plane], how, oh, ow, format);
     } else if (r.extent == OutExtent::Rect)
-        FC_VERBOSE(p, "output rectangle: %d maps cropped from the fp32 window, rows [%d, %d) of columns [%d, %d), into %s maps", nmaps, fh, fh + oh, fw, fw + ow, format);
+        FC_VERBOSE(p, "output rectangle: %d maps cropped from the fp32 window, rows [%d, %d) of columns [%d, %d), into %s maps", nmaps, fh, fh + p->ext_h(), fw, fw + p->ext_w(), format);
     else FC_VERBOSE(p, "output region %ld: %d maps %s from the fp32 window into %d x %d %s maps", p->opt_region, nmaps, how, oh, ow, format);
     const MapPlane pl = output_plane(p, r, l);
     if (pad) HIP_TRY(launch_pad_maps(src, g.fft_h, g.fft_w, g.map_elems(), dst, oh, ow, p->out_elems(), nmaps, s, r.map_format, pl));
-    else HIP_TRY(launch_crop_maps(src, g.fft_h, g.map_elems(), dst, oh, ow, p->out_elems(), fh, fw, nmaps, s, r.map_format, pl));
+    else HIP_TRY(launch_crop_maps(src, g.fft_h, g.map_elems(), dst, oh, ow, p->out_elems(), fh, fw, nmaps, s, r.map_format, pl, p->stride_h, p->stride_w));
     return 0;
 }
 

@@ -430,6 +430,10 @@ int fftconv_plan_synchronize(fftconv_plan *plan);
  *             plan has the kernel for it; 0: the window goes through the fp32 staging and is cropped like regions 1-3.
  *             Read-only beside it: "rect_direct" (1 if, with the plan's current settings, the output kernel will store the
  *             rectangle itself), "rect_off_h" / "rect_off_w" (the rectangle's offsets; 0 without one)),
+ *          "stride_store" (1 (default): the output kernel samples the strided maps of fftconv_plan_set_output_stride in its store
+ *             where the plan can; 0: always the staged route -- the fp32 window, then the sampling crop.  Read-only beside it:
+ *             "stride_h" / "stride_w" (the strides; 1 without any) and "stride_direct" (1 if, with the plan's current settings,
+ *             the output kernel will sample in its store)),
  *          "image_walk" (image batches, fftconv_plan_set_images.  0 (default): a workgroup of the spectral-row kernel keeps an
  *             image-spectrum row in registers and walks over kernels.  1: where the plan has the kernel for it, a launch of more
  *             than one image keeps the transformed KERNEL row in registers and walks over the images of the launch ("rows_group"
@@ -474,6 +478,27 @@ int fftconv_plan_set_option(fftconv_plan *plan, const char *name, long value);
  * kernel is not built because it would spill registers (1088 and 4160 points along h: exact_window plans of the 1088- / 4160-row
  * windows) -- computes the window and crops it; read-only option "rect_direct" tells which. */
 int fftconv_plan_set_output_rect(fftconv_plan *plan, int off_h, int off_w, int out_h, int out_w);
+/* Strided result maps.  Let U be the out_h x out_w map the plan delivers without this entry -- the window, an "output_region" 1-3,
+ * the rectangle of fftconv_plan_set_output_rect, the "same" map of a border mode.  With strides (stride_h, stride_w) every result
+ * map is S[i, j] = U[i * stride_h, j * stride_w], i < ceil(out_h / stride_h), j < ceil(out_w / stride_w): column-major and dense,
+ * in the plan's "map_format", image-major for image batches, on every delivery route -- the response at the stride of a coarse
+ * search or of a feature map's cells, as conv2d(stride=) gives it.  The sampling grid starts at U's own first row and column
+ * (another phase: fftconv_plan_set_output_rect); a stride larger than the extent gives one row or column.  plan_info.out_h /
+ * out_w / out_map_bytes are those of S.  A stride < 1 is FFTCONV_ERR_INVALID_ARG, and so is a stride other than (1, 1) while
+ * "output_region" is 4 (the pow2-padded window is not a sampling of the window), as is region 4 while a stride is set; the
+ * previous setting stays.  Output-side state of its own: the plan's stream is synchronised, the image and the prepared kernels
+ * stay, and the stride survives fftconv_plan_set_output_rect, "output_region", fftconv_plan_set_border, "map_format",
+ * fftconv_plan_set_images and fftconv_plan_set_stream (the extents are recomputed); (1, 1) restores the dense maps exactly.  On a
+ * one-pass plan with the specialised output kernel and the tiled intermediate (kernel_path 0), fp32 maps of the window or of a
+ * rectangle and no score with a plane (scores 0 and 2), that kernel samples in its store: a column that is not sampled is neither
+ * transformed in the last inverse stage nor stored, only tiles that hold a sampled column are launched, and the map store falls
+ * from 4P to 4P / (stride_h * stride_w) bytes.  Everything else is STAGED -- 16-bit maps, scores 1, 3 and 4,
+ * "output_region" 1-3, generic / Bluestein / kernel_path 1 or 2 output kernels, block-wise plans, the two transforms whose kernel
+ * is not built (1088 and 4160 points along h), option "stride_store" 0: the output kernel stores the fp32 window into the plan's
+ * staging and the crop samples it (a plane is read at the element's window coordinate).  Both routes return the same bits, those
+ * of the dense maps sliced; read-only option "stride_direct" tells which.  The one-shot, two-step, fftconv_multi_*, plan-cache and
+ * MEX entries do not take strides. */
+int fftconv_plan_set_output_stride(fftconv_plan *plan, int stride_h, int stride_w);
 /* Normalised cross-correlation maps.  mode 0 (default): the maps are the raw sums of products, bit for bit what they are
  * without this entry.  mode 1: every map is the zero-mean normalised cross-correlation (MATLAB's normxcorr2, OpenCV's
  * TM_CCOEFF_NORMED) over the box box_h x box_w, n = box_h * box_w: in [-1, 1], 1 at a perfect match, invariant to gain and
