@@ -84,6 +84,8 @@ _PIXEL_OF_DTYPE = {np.dtype(np.uint8): PIXEL_U8, np.dtype(np.uint16): PIXEL_U16,
 # extension: constant, edge, symmetric, reflect, wrap.
 # matching scores (Plan.set_match_score; FFTCONV_SCORE_* of include/fftconv.h)
 SCORE_NONE, SCORE_CCOEFF_NORMED, SCORE_CCOEFF, SCORE_CCORR_NORMED, SCORE_SQDIFF = 0, 1, 2, 3, 4
+# spectral filters (Plan.set_spectral_filter; FFTCONV_FILTER_* of include/fftconv.h)
+FILTER_PRODUCT, FILTER_PHASE, FILTER_WIENER = 0, 1, 2
 BORDER_ZERO, BORDER_CONSTANT, BORDER_REPLICATE, BORDER_SYMMETRIC, BORDER_REFLECT101, BORDER_CIRCULAR = 0, 1, 2, 3, 4, 5
 
 
@@ -136,7 +138,7 @@ EXPORTED_SYMBOLS = (
     "fftconv_plan_use_spectrum_buffer", "fftconv_plan_export_spectrum", "fftconv_plan_import_spectrum",
     "fftconv_plan_convolve", "fftconv_plan_convolve_packed", "fftconv_plan_prepare_kernels_packed",
     "fftconv_plan_synchronize", "fftconv_plan_set_stream",
-    "fftconv_plan_set_option", "fftconv_plan_set_output_rect", "fftconv_plan_set_output_stride", "fftconv_plan_set_normalisation", "fftconv_plan_set_match_score", "fftconv_plan_set_border", "fftconv_plan_get_option", "fftconv_plan_get_profile",
+    "fftconv_plan_set_option", "fftconv_plan_set_output_rect", "fftconv_plan_set_output_stride", "fftconv_plan_set_normalisation", "fftconv_plan_set_match_score", "fftconv_plan_set_border", "fftconv_plan_set_spectral_filter", "fftconv_plan_get_option", "fftconv_plan_get_profile",
     "fftconv_fft_data", "fftconv_conv_fft_data",
     "fftconv_multi_create", "fftconv_multi_destroy", "fftconv_multi_set_image", "fftconv_multi_import_spectrum",
     "fftconv_multi_convolve", "fftconv_multi_set_option", "fftconv_multi_get_option",
@@ -215,6 +217,7 @@ def load_library():
     lib.fftconv_plan_set_normalisation.argtypes = [vp, ci, ci, ci]
     lib.fftconv_plan_set_match_score.argtypes = [vp, ci, ci, ci]
     lib.fftconv_plan_set_border.argtypes = [vp, ci, ctypes.c_float]
+    lib.fftconv_plan_set_spectral_filter.argtypes = [vp, ci, ctypes.c_float]
     lib.fftconv_plan_get_option.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_long)]
     lib.fftconv_plan_get_profile.argtypes = [vp, ctypes.POINTER(Profile), ci]
     lib.fftconv_fft_data.argtypes = [vp, ci, ci, ci, ci, ci, ci, ctypes.POINTER(vp)]
@@ -618,6 +621,15 @@ class Plan:
         "border_direct", "border_mode", "border_lead_h", "border_lead_w"."""
         _check(self._lib.fftconv_plan_set_border(self._h, int(mode), float(value)))
         _check(self._lib.fftconv_plan_get_info(self._h, ctypes.byref(self.info)))
+
+    def set_spectral_filter(self, mode, param=0.0):
+        """the pointwise operation between the forward and the inverse transform (fftconv_plan_set_spectral_filter): FILTER_PRODUCT
+        (the default: I^ K^), FILTER_PHASE (phase correlation, P / |P| with P = I^ K^; param 0) or FILTER_WIENER (I^ conj(K^) /
+        (|K^|^2 + param), param = lambda >= 0 in the units of |K^|^2 of the unnormalised DFT), on the plan's transform lengths
+        (info.transform_h x transform_w; exact_window makes them the window).  feature_dim 1, one-pass plans without a matching
+        score.  It keeps the image, the prepared kernels and the output side.  Read-only options "spectral_filter",
+        "spectral_filter_fast"."""
+        _check(self._lib.fftconv_plan_set_spectral_filter(self._h, int(mode), float(param)))
 
     def get_option(self, name):
         v = ctypes.c_long(0)

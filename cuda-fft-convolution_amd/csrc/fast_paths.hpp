@@ -235,6 +235,32 @@ constexpr bool fast_rows_images_built(int L) {
 }
 inline bool fast_rows_images_available(int L, int max_kw) { return fast_rows_lookup(L, max_kw < 1 ? 1 : max_kw).ok && fast_rows_images_built(L); }
 
+// Spectral filter (fast_rows_multi.hpp: FILTER; spectral_filter.hpp; plan entry fftconv_plan_set_spectral_filter): the F = 1 kernel
+// walk with the filter's pointwise function in place of the product -- one instantiation per (length, NZ2), the mode a uniform of
+// the launch, in kernels of their own name (kernels_rows_filter_g<G>.hip).  The rule for a variant: no spilled register and no
+// scratch in the build's reports (csrc/kernels_rows_filter_g*.rpt); it may hold fewer waves per SIMD than its plain sibling.
+// Compiled as the plain kernels are, seven lengths spilled (4 ... 57 registers at the 168 of three waves per SIMD).  Two of them fit
+// once the walk forms its stage-1 twiddle chain again per map instead of keeping the even powers (RowMultiState: KEEP is off under
+// FILTER -- 4224 and 3520, 9 spilled registers with them kept, 159 and 156 registers without).  Four run on launch bounds of two waves per SIMD
+// (fast_rows_filter_min_waves): 2112 (173 registers), 864 (172), 4608 (169 at NZ2 = 16) and 4160 (185: radix 26).  The last one, 7040
+// = 10.32.22 x2, cannot be relaxed -- its workgroup of 640 threads is ten waves, three per SIMD whatever the bounds say -- and
+// spills 4 registers: it is NOT built and listed here, and the setter refuses modes 1 and 2 on a plan of that length (a caller
+// creates the plan with kernel_path 1).  The built ones and the ones listed here add up to the 32 lengths
+// (tests/test_spectral_filter_host.py holds the reports against it).
+constexpr int FC_ROWS_FILTER_NOT_BUILT[] = {7040};
+constexpr bool fast_rows_filter_built(int L) {
+    for (int x : FC_ROWS_FILTER_NOT_BUILT)
+        if (x == L) return false;
+    return true;
+}
+// minimum waves per SIMD of a filter kernel's launch bounds: the plain kernels' 3, or 2 (up to 256 registers)
+constexpr int FC_ROWS_FILTER_TWO_WAVES[] = {4608, 4160, 2112, 864};
+constexpr int fast_rows_filter_min_waves(int L) {
+    for (int x : FC_ROWS_FILTER_TWO_WAVES)
+        if (x == L) return 2;
+    return 3;
+}
+
 // Host tables of a fast row configuration.
 struct FastRowsTables {
     Plan1D plan;               // radices (R1, R2, R3)

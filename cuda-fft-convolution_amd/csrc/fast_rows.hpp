@@ -25,6 +25,7 @@
 #include "fc_common.hpp"
 #include "fc_instrument.hpp"
 #include "fft_stages.hpp"
+#include "spectral_filter.hpp"
 
 namespace fc {
 
@@ -98,6 +99,10 @@ struct FastRowsArgs {
     size_t s_image_stride;
     int images;
     int kernels_per_image;
+    // Spectral filter (fftconv_plan_set_spectral_filter; spectral_filter.hpp): FC_FILTER_* and the launch's uniform parameter (PHASE:
+    // c = 1 / (Lh * Lw); WIENER: lambda).  Read by the FILTER instantiations of the body only (k_fast_rows_filter); zero elsewhere.
+    int filter_mode;
+    float filter_param;
 };
 
 // Slot u = t + NT * ROUND of a phase with NB butterflies per row: the workgroup's row rr, the butterfly w within that row, and

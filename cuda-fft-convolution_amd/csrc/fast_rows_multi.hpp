@@ -35,9 +35,11 @@ constexpr bool row_multi_keeps_even_powers() {
     return !MULTIF && C::RPW == 1 && C::R1 >= 4 && 2 * (C::R1 / 2 - 1) * C::RND1 <= FC_ROWS_KEEP_REGS && C::R3 >= 14 && C::R3 <= 24;
 }
 
-template <class C, bool MULTIF = false>
+// (FILTER: the registers are not there -- 4224 and 3520 spill 9 with the powers kept beside the filter's temporaries; the chain
+//  formed again is the same bits, power_chain_from_even)
+template <class C, bool MULTIF = false, bool FILTER = false>
 struct RowMultiState {
-    static constexpr bool KEEP = row_multi_keeps_even_powers<C, MULTIF>();
+    static constexpr bool KEEP = !FILTER && row_multi_keeps_even_powers<C, MULTIF>();
     static constexpr int NEVEN = C::R1 / 2 - 1;
     c32 s[C::R3];        // image spectrum of this thread's stage-3 butterfly (F = 1: whole walk; MULTIF: one step)
     c32 acc[MULTIF ? C::R3 : 1];   // feature sum of the current map (MULTIF)
@@ -53,11 +55,14 @@ struct RowMultiState {
 // LINEAR: always true (fast_rows_visit_linear, fast_paths.hpp).  It once chose between two forms of P5; the other one (per-output
 // tile arithmetic, for an m1 that is no whole number of half layout tiles) had no configuration and is gone: RowCfg asserts
 // the condition.  The argument itself is still to be deleted, together with the visitor and the argument of the two kernels.
-template <class C, int NZ2, bool LINEAR, bool MULTIF = false, class Ctx>
+// FILTER (F = 1; k_fast_rows_filter, fftconv_plan_set_spectral_filter): the product of P3 is the pointwise function of
+// spectral_filter.hpp that g.filter_mode names -- one instantiation per configuration for all modes, everything else as it is.
+template <class C, int NZ2, bool LINEAR, bool MULTIF = false, bool FILTER = false, class Ctx>
 FC_HD void fast_rows_multi_body(Ctx& ctx, c32* lds, const FastRowsArgs& g, int group, int kernel0, int nk, int rows) {
     static_assert(LINEAR, "the row kernel has one form of its last phase");
+    static_assert(!(FILTER && MULTIF), "the filter of a feature sum is another formula");
     constexpr int L = C::L, R1 = C::R1, R2 = C::R2, R3 = C::R3, NT = C::NT, m1 = C::m1, RPW = C::RPW, S1 = C::S1, LR = C::LR;
-    using State = RowMultiState<C, MULTIF>;
+    using State = RowMultiState<C, MULTIF, FILTER>;
     const int nF = MULTIF ? g.F : 1;
     c32* tw2 = lds + RPW * LR;
     const int kw = g.kw;
@@ -240,7 +245,26 @@ FC_HD void fast_rows_multi_body(Ctx& ctx, c32* lds, const FastRowsArgs& g, int g
                 }
                 Dft<R3, -1>::run(v);
                 if constexpr (MULTIF && S_EARLY < R3 / 2) load_s(st, f, rr, q, IC<S_EARLY>{}, IC<R3 / 2>{});
-                if constexpr (!MULTIF) {
+                if constexpr (FILTER) {
+                    // one of three unrolled loops, picked by the launch's mode (uniform: a scalar branch around the loop, not in it)
+                    const float fp = g.filter_param;
+                    if (g.filter_mode == FC_FILTER_PHASE) {
+                        static_for<0, R3>([&](auto a_) {
+                            constexpr int a = decltype(a_)::value;
+                            v[a] = spectral_filter_phase(v[a], st.s[a], fp);
+                        });
+                    } else if (g.filter_mode == FC_FILTER_WIENER) {
+                        static_for<0, R3>([&](auto a_) {
+                            constexpr int a = decltype(a_)::value;
+                            v[a] = spectral_filter_wiener(v[a], st.s[a], fp);
+                        });
+                    } else {
+                        static_for<0, R3>([&](auto a_) {
+                            constexpr int a = decltype(a_)::value;
+                            v[a] = cmul(v[a], st.s[a]);
+                        });
+                    }
+                } else if constexpr (!MULTIF) {
                     static_for<0, R3>([&](auto a_) {
                         constexpr int a = decltype(a_)::value;
                         v[a] = cmul(v[a], st.s[a]);

@@ -199,10 +199,15 @@ int launch_spectral_rows_batch(fftconv_plan* p, const c32* a, int kw, int b0, in
     } else if (g.fast_rows.ok) {
         FastRowsArgs fa = fast_rows_args(g, p->d, a, kw, s, p->Y.p);
         rows_args_set_images(fa, g, nb, nk);
+        if (p->opt_filter) {      // (fftconv_plan_set_spectral_filter: the FILTER instantiation, the mode and its parameter uniforms of the launch)
+            fa.filter_mode = (int)p->opt_filter; fa.filter_param = spectral_filter_launch_param(p->opt_filter, p->filter_lambda, g.Lh, g.Lw);
+            HIP_TRY(launch_fast_rows_filter(g.Lw, fast_rows_nz2(g, kw), fa, g.rows, nk, route.per_wg, p->stream));
+        } else
         HIP_TRY(launch_fast_rows_multi(g.Lw, fast_rows_nz2(g, kw), fa, g.rows, nk, route.per_wg, p->stream));
     } else {
         SpectralRowsArgs sa = spectral_rows_args(g, p->t, p->d, a, kw, s, p->Y.p);
         rows_args_set_images(sa, g, nb, nk);
+        sa.filter_mode = (int)p->opt_filter; sa.filter_param = spectral_filter_launch_param(p->opt_filter, p->filter_lambda, g.Lh, g.Lw);
         HIP_TRY(launch_spectral_rows(sa, g.rows, nk, rows_threads(g), p->rows_lds(), p->stream));
     }
     return p->prof_end();
@@ -249,6 +254,9 @@ int run_group_impl(fftconv_plan* p, int n, const float* dk, int kh, int kw, cons
             FC_VERBOSE(p, "maps %d..%d: spectral rows (%s, %d rows x %d points, %s%d %s per workgroup), output columns (%s, %d-point, %d columns per tile)",
                        first, first + ny - 1, g.fast_rows.ok ? "specialised" : "generic", g.rows, g.Lw, route.image_walk ? "image walk: " : "", route.per_wg,
                        route.image_walk ? "images" : "maps", g.fast_cols.ok ? "specialised" : "generic", g.M, g.fast_cols.ok ? g.fast_cols.T : g.T_cols);
+            if (p->opt_filter)
+                FC_VERBOSE(p, "spectral filter %ld (%s, lambda %g) in the product phase of the %s row kernel", p->opt_filter,
+                           p->opt_filter == FC_FILTER_PHASE ? "phase" : "wiener", (double)p->filter_lambda, p->filter_fast() ? "specialised" : "generic");
             if (int rc = launch_spectral_rows_batch(p, p->A.p + (size_t)(l.k0 - l.a0) * bs.per_a, kw, l.b0, l.nb, l.nk, route)) return rc;
             int buf = 0;
             if (d.r.route == Route::Ring)
@@ -790,6 +798,9 @@ static int set_score(fftconv_plan* plan, int score, int box_h, int box_w) {
     if (score != 0 && plan->border_mode)
         return api_fail(FFTCONV_ERR_INVALID_ARG, "a border is on (fftconv_plan_set_border, mode %ld): the window statistics of normalised maps assume zero padding",
                         plan->border_mode);
+    if (score != 0 && plan->opt_filter)
+        return api_fail(FFTCONV_ERR_INVALID_ARG, "spectral filter %ld is on (fftconv_plan_set_spectral_filter): the window statistics of a score belong to the "
+                        "plain product", plan->opt_filter);
     if (score == 0) box_h = box_w = 0;
     if (plan->opt_score == score && plan->norm_box_h == box_h && plan->norm_box_w == box_w) return 0;      // nothing changes: the image stays
     if (int rc = use_device(plan)) return rc;
@@ -845,8 +856,36 @@ int fftconv_plan_set_border(fftconv_plan* plan, int mode, float value) {
     return 0;
 }
 
+int fftconv_plan_set_spectral_filter(fftconv_plan* plan, int mode, float param) {
+    if (!plan) return api_fail(FFTCONV_ERR_INVALID_ARG, "plan is NULL");
+    const Geometry& g = plan->g;
+    if (const char* why = spectral_filter_args_error(mode, param))
+        return api_fail(FFTCONV_ERR_INVALID_ARG, "%s (mode %d, param %g)", why, mode, (double)param);
+    if (mode != FC_FILTER_WIENER) param = 0.f;
+    if (mode != FC_FILTER_PRODUCT) {
+        if (plan->tiled)
+            return api_fail(FFTCONV_ERR_INVALID_ARG, "a spectral filter is not available on a block-wise plan (%d blocks: the filter is defined on one transform of the "
+                            "whole window); create a one-pass plan (fftconv_plan_options.blockwise = 1)", plan->tiled->nblk);
+        if (g.F > 1)
+            return api_fail(FFTCONV_ERR_INVALID_ARG, "a spectral filter needs feature_dim 1 (this plan: %d): the filter of a feature sum is another formula", g.F);
+        if (plan->opt_score)
+            return api_fail(FFTCONV_ERR_INVALID_ARG, "matching score %ld is on (fftconv_plan_set_match_score / _set_normalisation): its window statistics belong to "
+                            "the plain product", plan->opt_score);
+        if (g.fast_rows.ok && !fast_rows_filter_built(g.Lw))
+            return api_fail(FFTCONV_ERR_INVALID_ARG, "the specialised spectral-row kernel of %d points has no filter form (it would spill registers); create the plan "
+                            "with fftconv_plan_options.kernel_path = 1 (generic kernels)", g.Lw);
+    }
+    // (state of the spectral-row launches alone: the image, the prepared kernels, the stream and the output side stay; nothing to wait for)
+    plan->opt_filter = mode; plan->filter_lambda = param;
+    return 0;
+}
+
 int fftconv_plan_get_option(fftconv_plan* plan, const char* name, long* value) {
     if (!plan || !name || !value) return api_fail(FFTCONV_ERR_INVALID_ARG, "null argument");
+    // spectral filter (fftconv_plan_set_spectral_filter), read-only: the mode, and whether the next spectral-row launch under it runs
+    // the specialised filter kernel (0 without a mode, and where the generic kernel's branch serves it)
+    if (!strcmp(name, "spectral_filter")) { *value = plan->opt_filter; return 0; }
+    if (!strcmp(name, "spectral_filter_fast")) { *value = plan->filter_fast() ? 1 : 0; return 0; }
     // border modes (fftconv_plan_set_border), read-only: the mode, where data sample 0 lies in the window, and whether the next
     // image on this plan, with the options as they are, is mapped in the column kernel's load (0 without a border)
     if (!strcmp(name, "border_mode")) { *value = plan->border_mode; return 0; }

@@ -205,6 +205,13 @@ hipError_t launch_fast_rows_multi(int L, int nz2, const FastRowsArgs& a, int row
     return in_first_group<FC_ROW_GROUPS>([&](auto g) { return launch_fast_rows_multi_group<g.value>(L, nz2, a, rows, kernels, kernels_per_wg, s); });
 }
 
+hipError_t launch_fast_rows_filter(int L, int nz2, const FastRowsArgs& a, int rows, int kernels, int kernels_per_wg, hipStream_t s) {
+    if (rows <= 0 || kernels <= 0) return hipSuccess;
+    if (a.F != 1 || kernels_per_wg < 1 || !fc_filter_mode_ok(a.filter_mode)) return hipErrorInvalidValue;
+    if (a.images > 1 && a.kernels_per_image != kernels) return hipErrorInvalidValue;   // (image batches: `kernels` counts per image)
+    return in_first_group<FC_ROW_GROUPS>([&](auto g) { return launch_fast_rows_filter_group<g.value>(L, nz2, a, rows, kernels, kernels_per_wg, s); });
+}
+
 hipError_t launch_fast_rows_images(int L, const FastRowsArgs& a, int rows, int images_per_wg, hipStream_t s) {
     if (rows <= 0) return hipSuccess;
     if (a.F != 1 || images_per_wg < 1 || a.images < 1 || a.kernels_per_image < 1) return hipErrorInvalidValue;

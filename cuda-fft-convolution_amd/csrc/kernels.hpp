@@ -90,6 +90,9 @@ hipError_t launch_spectral_rows(const SpectralRowsArgs& a, int rows, int kernels
 // specialised spectral rows (fast_rows_multi.hpp): kernels_per_wg (>= 1) consecutive kernels share one fetch of the image-spectrum
 // row; hipErrorInvalidValue if no instantiation matches (L, nz2)
 hipError_t launch_fast_rows_multi(int L, int nz2, const FastRowsArgs& a, int rows, int kernels, int kernels_per_wg, hipStream_t s);
+// the same walk with a spectral filter in the product phase (kernels_rows_filter_g<G>.hip; a.filter_mode, a.filter_param): F = 1;
+// hipErrorInvalidValue besides for a length that is not built (fast_paths.hpp: fast_rows_filter_built)
+hipError_t launch_fast_rows_filter(int L, int nz2, const FastRowsArgs& a, int rows, int kernels, int kernels_per_wg, hipStream_t s);
 // how many workgroups of that kernel a CU holds at once (hipOccupancyMaxActiveBlocksPerMultiprocessor)
 hipError_t fast_rows_multi_wgs_per_cu(int L, int nz2, const FastRowsArgs& a, int* wgs_per_cu);
 // image-walk spectral rows (fast_rows_images.hpp; F = 1): the a.images x a.kernels_per_image maps of the launch, a workgroup per
@@ -126,6 +129,8 @@ hipError_t launch_cols_c2r(const ColsC2RArgs& a, int tiles, int kernels, int thr
 using GroupResult = std::optional<hipError_t>;
 template <int G> GroupResult launch_fast_rows_fwd_group(int L, const FastRowsFwdArgs& a, int rows, hipStream_t s);
 template <int G> GroupResult launch_fast_rows_multi_group(int L, int nz2, const FastRowsArgs& a, int rows, int kernels, int kernels_per_wg, hipStream_t s);
+// (with a spectral filter: kernels_rows_filter_g<G>.hip)
+template <int G> GroupResult launch_fast_rows_filter_group(int L, int nz2, const FastRowsArgs& a, int rows, int kernels, int kernels_per_wg, hipStream_t s);
 template <int G> GroupResult fast_rows_multi_wgs_per_cu_group(int L, int nz2, const FastRowsArgs& a, int* wgs_per_cu);
 // (the image walk: kernels_rows_images_g<G>.hip)
 template <int G> GroupResult launch_fast_rows_images_group(int L, const FastRowsArgs& a, int rows, int images_per_wg, hipStream_t s);

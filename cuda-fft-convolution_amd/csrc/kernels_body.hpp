@@ -20,6 +20,7 @@
 #pragma once
 #include "fc_common.hpp"
 #include "fft_lds.hpp"
+#include "spectral_filter.hpp"
 
 namespace fc {
 
@@ -158,6 +159,9 @@ struct SpectralRowsArgs {
     size_t s_image_stride;
     int images;
     int kernels_per_image;
+    // spectral filter, as FastRowsArgs (fast_rows.hpp); F = 1 only.  Zero: the plain product
+    int filter_mode;
+    float filter_param;
 };
 
 // lds: the work buffer (fft_work_length c32: Lw, or the Bluestein work length), for F > 1 followed by an Lw-c32
@@ -181,7 +185,11 @@ FC_HD void spectral_rows_body(const Ctx& ctx, c32* lds, const SpectralRowsArgs& 
         ctx.sync();
         fft_forward<BS>(ctx, buf, L, 1, a.fd, a.tw);
         if (a.F == 1) {
-            for (int x = ctx.tid; x < L; x += ctx.nthreads) buf[x] = cmul(buf[x], srow[x]);
+            if (a.filter_mode != FC_FILTER_PRODUCT) {      // (uniform; fftconv_plan_set_spectral_filter)
+                for (int x = ctx.tid; x < L; x += ctx.nthreads) buf[x] = spectral_filter_apply(a.filter_mode, a.filter_param, buf[x], srow[x]);
+            } else {
+                for (int x = ctx.tid; x < L; x += ctx.nthreads) buf[x] = cmul(buf[x], srow[x]);
+            }
         } else if (f == 0) {
             for (int x = ctx.tid; x < L; x += ctx.nthreads) acc[x] = cmul(buf[x], srow[x]);
         } else if (f < a.F - 1) {

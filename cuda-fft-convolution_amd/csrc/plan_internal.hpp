@@ -274,8 +274,15 @@ struct fftconv_plan {
     // every plan it cannot serve: the walk over kernels.  Nothing cached depends on it.
     long opt_image_walk = 0;
     bool image_walk_active() const {
-        return opt_image_walk && !tiled && g.F == 1 && g.path_mode != 0 && g.fast_rows.ok && fast_rows_images_available(g.Lw, g.max_kw);
+        return opt_image_walk && !opt_filter && !tiled && g.F == 1 && g.path_mode != 0 && g.fast_rows.ok && fast_rows_images_available(g.Lw, g.max_kw);
     }
+    // fftconv_plan_set_spectral_filter (spectral_filter.hpp): FC_FILTER_* of the pointwise operation of the spectral-row launches and
+    // the Wiener filter's lambda.  State of the row launches alone: nothing cached depends on it, and it allocates nothing.  While
+    // a mode is on the launches walk over kernels (the image walk has no filter form) -- on the specialised kernel's FILTER
+    // instantiation (filter_fast(); read-only option "spectral_filter_fast") or behind the generic kernel's branch.
+    long opt_filter = 0;
+    float filter_lambda = 0.f;
+    bool filter_fast() const { return opt_filter && !tiled && g.fast_rows.ok && fast_rows_filter_built(g.Lw); }
     // fftconv_plan_set_normalisation (ncc.hpp): 1 = the maps are zero-mean normalised cross-correlations over the box norm_box_h x
     // norm_box_w, the size of every kernel while it is on.  ND holds the scale plane D of every image the plan holds
     // ([b][fft_w][fft_h], written by set_image / set_images beside the forward transform), KN the normalised kernels T'' of the

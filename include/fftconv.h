@@ -621,6 +621,43 @@ int fftconv_plan_set_match_score(fftconv_plan *plan, int score, int box_h, int b
 enum { FFTCONV_BORDER_ZERO = 0, FFTCONV_BORDER_CONSTANT = 1, FFTCONV_BORDER_REPLICATE = 2, FFTCONV_BORDER_SYMMETRIC = 3,
        FFTCONV_BORDER_REFLECT101 = 4, FFTCONV_BORDER_CIRCULAR = 5 };
 int fftconv_plan_set_border(fftconv_plan *plan, int mode, float value);
+/* Spectral filters: what happens to every bin between the forward and the inverse transform.  Let L_h x L_w be the plan's
+ * transform lengths (fftconv_plan_info.transform_h / transform_w), I^ the unnormalised L_h x L_w DFT of the window the plan
+ * transforms -- the zero-padded image, or the bordered extension while a border is on -- and K^_k the DFT of kernel k as the plan
+ * places it: at the origin, after "flip_kernels".  IDFT is the normalised inverse (numpy's ifft2).  Every map is the
+ * FFT_H x FFT_W window (rows < fft_h, columns < fft_w) of
+ *     mode 0 FFTCONV_FILTER_PRODUCT   IDFT(I^ . K^_k)                           the library as it is, every bit unchanged (default)
+ *     mode 1 FFTCONV_FILTER_PHASE     IDFT(P / |P|),  P = I^ . K^_k             and 0 in a bin where P is zero
+ *     mode 2 FFTCONV_FILTER_WIENER    IDFT(I^ . conj(K^_k) / (|K^_k|^2 + lambda))   and 0 in a bin where the denominator is zero
+ * and everything downstream of it -- "output_region", rectangle, stride, "map_format", delivery -- works as ever.
+ * Mode 1 is phase correlation (skimage's phase_cross_correlation, OpenCV's phaseCorrelate): it ignores illumination and contrast.
+ * `param` must be 0 (reserved for a regulariser).  A pure cyclic shift gives a peak of height 1.  With "flip_kernels" 1 the
+ * zero-shift peak of a template cut from the image at (y0, x0) lies at (y0 + kh - 1, x0 + kw - 1), as the raw correlation's
+ * does; all shifts lie inside the window whatever L is.
+ * Mode 2 is the Wiener / regularised inverse filter (deconvolution with a known point-spread function; the response of a
+ * correlation filter): lambda = param >= 0, finite, in the units of |K^|^2 of the UNNORMALISED DFT.
+ * The arithmetic is fp32 with the hardware's reciprocal and reciprocal square root (1 ulp); "zero" above means below the smallest
+ * normal fp32 number in the kernel's own scaling (|P|^2 / (L_h L_w)^2 for mode 1, |K^|^2 + lambda for mode 2).
+ * Unlike mode 0, modes 1 and 2 depend on the cyclic modulus: a default plan may transform a longer length than its window (1152
+ * points for a 1088 window), and the filter is defined on THAT length.  A caller who needs the window itself as the modulus
+ * creates the plan with fftconv_plan_options.exact_window = 1.
+ * The setter changes spectral-row launches only: it keeps the image or images, the prepared kernels
+ * (fftconv_plan_prepare_kernels_packed, deferred preparation, the column cache), the stream, the rectangle, the stride and the
+ * format, allocates nothing and does not synchronise.  A warm device-resident convolve under a mode never synchronises and can
+ * be captured into a graph.  A call that changes nothing is a no-op.  The filter runs in the product phase of the spectral-row
+ * kernel: the specialised one in an instantiation of its own per (length, kernel width class) that serves all modes, the generic
+ * and Bluestein one (kernel_path 1, exact_window windows that do not factor) behind a uniform branch.  While a mode is on,
+ * "image_walk_active" reads 0 and image batches keep the walk over kernels.
+ * Read-only options: "spectral_filter" (the mode), "spectral_filter_fast" (1 if the next spectral-row launch of this plan under
+ * the mode runs the specialised filter kernel).
+ * FFTCONV_ERR_INVALID_ARG, the plan's state untouched: a mode outside 0..2; a param that is not finite, negative, or non-zero in
+ * mode 1 (mode 0 ignores a valid one); modes 1 and 2 with feature_dim > 1 (the filter of a feature sum is another formula), on a block-wise plan, on a
+ * plan with normalisation or a matching score on -- likewise fftconv_plan_set_normalisation / fftconv_plan_set_match_score with a
+ * non-zero mode while a filter is on -- and on a plan whose specialised row length has no filter kernel because it would spill
+ * registers (7040 points along w: create such a plan with kernel_path 1).
+ * The one-shot and two-step entries, fftconv_multi_*, the plan cache and the MEX gateways do not take the option. */
+enum { FFTCONV_FILTER_PRODUCT = 0, FFTCONV_FILTER_PHASE = 1, FFTCONV_FILTER_WIENER = 2 };
+int fftconv_plan_set_spectral_filter(fftconv_plan *plan, int mode, float param);
 /* Current value of an option, plus read-only ones: "tuned_candidates" (allocations tried by the last placement tuning)
  * and "tuned_best" (index of the one kept), "blockwise" (blocks of a block-wise plan, 0 = one pass), "overlap_save" (1: the blocks are stored by the output kernel),
  * "rows_slots_per_cu" (workgroups of the multi-map row kernel a CU holds at once: what the walk length is chosen for),
