@@ -277,12 +277,11 @@ int run_group_impl(fftconv_plan* p, int n, const float* dk, int kh, int kw, cons
 }
 
 // Options that are a `long` member of the plan and nothing else: fftconv_plan_set_option and fftconv_plan_get_option are both
-// served from this table.  Options with logic of their own are code in those two functions.
+// served from this table.  Options with logic of their own are code in fftconv_plan_set_option and rows of kComputedOptions.
 enum : unsigned {
     OPT_BOOL = 1,       // stored as value != 0
     OPT_REJECT = 2,     // a value outside [lo, hi] is an error (otherwise it is clamped)
-    OPT_FORGETS = 4,    // the kernel column spectra in A depend on it: ColumnCache::forget
-    OPT_RING = 8,       // the host-output ring is sized by it: torn down, rebuilt by the next host-output call
+    OPT_OWN = 4,        // a block-wise plan answers it itself, set and get (every other name acts on its block plan)
     OPT_GET_ONLY = 16,  // get_option only: read-only, or set_option handles the name in code
     OPT_SET_ONLY = 32,
 };
@@ -291,39 +290,110 @@ struct LongOption {
     long fftconv_plan::*member;
     long lo, hi;
     unsigned flags;
+    unsigned effects = 0;      // FX_* of plan_rules.hpp: what setting it invalidates
 };
 const LongOption kLongOptions[] = {
     {"tune_placement", &fftconv_plan::opt_tune_placement, -1, 8, 0},
-    {"kernel_chunk_mb", &fftconv_plan::opt_kernel_chunk_mb, 0, LONG_MAX, OPT_FORGETS},
-    {"batch_maps", &fftconv_plan::opt_batch_maps, 0, LONG_MAX, OPT_FORGETS},
+    {"kernel_chunk_mb", &fftconv_plan::opt_kernel_chunk_mb, 0, LONG_MAX, 0, FX_COLUMNS},
+    {"batch_maps", &fftconv_plan::opt_batch_maps, 0, LONG_MAX, 0, FX_COLUMNS},
     {"verbose", &fftconv_plan::opt_verbose, 0, 1, OPT_BOOL},
-    {"flip_kernels", &fftconv_plan::opt_flip_kernels, 0, 1, OPT_BOOL | OPT_FORGETS},
-    {"map_format", &fftconv_plan::opt_map_format, FC_MAP_F32, FC_MAP_BF16, OPT_REJECT | OPT_FORGETS | OPT_RING},   // (the ring is sized for the map bytes)
+    {"flip_kernels", &fftconv_plan::opt_flip_kernels, 0, 1, OPT_BOOL, FX_COLUMNS},
+    {"map_format", &fftconv_plan::opt_map_format, FC_MAP_F32, FC_MAP_BF16, OPT_REJECT, FX_WAIT | FX_RING | FX_COLUMNS},   // (the ring is sized for the map bytes)
     {"host_pinned", &fftconv_plan::opt_host_pinned, 0, 1, OPT_BOOL},
     {"host_min_kb", &fftconv_plan::opt_host_min_kb, 0, 1 << 30, OPT_REJECT},
-    {"host_stream", &fftconv_plan::opt_host_stream, 0, 1 << 20, OPT_REJECT | OPT_RING},   // (0, 1 or 2: checked once the ring is down)
-    {"host_threads", &fftconv_plan::opt_host_threads, 0, 1 << 20, OPT_REJECT | OPT_RING | OPT_SET_ONLY},
-    {"host_chunk_kb", &fftconv_plan::opt_host_chunk_kb, 0, 1 << 20, OPT_REJECT | OPT_RING | OPT_SET_ONLY},
-    {"host_slots", &fftconv_plan::opt_host_slots, 0, 1 << 20, OPT_REJECT | OPT_RING | OPT_SET_ONLY},
+    {"host_stream", &fftconv_plan::opt_host_stream, 0, 1 << 20, OPT_REJECT, FX_WAIT | FX_RING},   // (0, 1 or 2: checked once the ring is down)
+    {"host_threads", &fftconv_plan::opt_host_threads, 0, 1 << 20, OPT_REJECT | OPT_SET_ONLY, FX_WAIT | FX_RING},
+    {"host_chunk_kb", &fftconv_plan::opt_host_chunk_kb, 0, 1 << 20, OPT_REJECT | OPT_SET_ONLY, FX_WAIT | FX_RING},
+    {"host_slots", &fftconv_plan::opt_host_slots, 0, 1 << 20, OPT_REJECT | OPT_SET_ONLY, FX_WAIT | FX_RING},
     {"tuned_candidates", &fftconv_plan::tuned_candidates, 0, 0, OPT_GET_ONLY},
     {"tuned_best", &fftconv_plan::tuned_best, 0, 0, OPT_GET_ONLY},
-    {"output_region", &fftconv_plan::opt_region, 0, 0, OPT_GET_ONLY},
-    {"rect_store", &fftconv_plan::opt_rect_store, 0, 1, OPT_BOOL},
-    {"stride_store", &fftconv_plan::opt_stride_store, 0, 1, OPT_BOOL},   // (it only chooses the route of the next group: nothing cached depends on it)
+    {"output_region", &fftconv_plan::opt_region, 0, 0, OPT_GET_ONLY | OPT_OWN},      // (block-wise: cropped on delivery)
+    {"rect_store", &fftconv_plan::opt_rect_store, 0, 1, OPT_BOOL | OPT_OWN},
+    {"stride_store", &fftconv_plan::opt_stride_store, 0, 1, OPT_BOOL | OPT_OWN},   // (it only chooses the route of the next group: nothing cached depends on it)
     {"dynamic_tiles", &fftconv_plan::opt_dynamic_tiles, 0, 0, OPT_GET_ONLY},
     {"defer_prepare", &fftconv_plan::opt_defer_prepare, 0, 0, OPT_GET_ONLY},
-    {"image_walk", &fftconv_plan::opt_image_walk, 0, 1, OPT_BOOL},      // (nothing cached depends on it: no OPT_FORGETS)
-    {"norm_store", &fftconv_plan::opt_norm_store, 0, 1, OPT_BOOL},       // (the kernel column spectra are the same either way: no OPT_FORGETS)
-    {"pixel_store", &fftconv_plan::opt_pixel_store, 0, 1, OPT_BOOL},     // (it only chooses the route of the next typed call: no OPT_FORGETS)
-    {"border_store", &fftconv_plan::opt_border_store, 0, 1, OPT_BOOL},   // (it only chooses the route of the next image: no OPT_FORGETS)
+    {"image_walk", &fftconv_plan::opt_image_walk, 0, 1, OPT_BOOL},      // (nothing cached depends on it: no FX_COLUMNS)
+    {"norm_store", &fftconv_plan::opt_norm_store, 0, 1, OPT_BOOL},       // (the kernel column spectra are the same either way: no FX_COLUMNS)
+    {"pixel_store", &fftconv_plan::opt_pixel_store, 0, 1, OPT_BOOL},     // (it only chooses the route of the next typed call: no FX_COLUMNS)
+    {"border_store", &fftconv_plan::opt_border_store, 0, 1, OPT_BOOL},   // (it only chooses the route of the next image: no FX_COLUMNS)
     {"match_score", &fftconv_plan::opt_score, 0, 0, OPT_GET_ONLY},       // (fftconv_plan_set_match_score / _set_normalisation set the three; "normalise": get_option)
     {"norm_box_h", &fftconv_plan::norm_box_h, 0, 0, OPT_GET_ONLY},
     {"norm_box_w", &fftconv_plan::norm_box_w, 0, 0, OPT_GET_ONLY},
 };
-const LongOption* find_option(const char* name, unsigned not_flag) {
+const LongOption* find_option(const char* name) {
     for (const LongOption& o : kLongOptions)
-        if (!strcmp(name, o.name)) return (o.flags & not_flag) ? nullptr : &o;
+        if (!strcmp(name, o.name)) return &o;
     return nullptr;
+}
+
+// Read-only options that are computed from the plan: fftconv_plan_get_option looks here first.  own: as OPT_OWN -- a block-wise plan
+// answers from its own state (the setters act on it; its routes are its own), every other name is its block plan's.
+struct ComputedOption {
+    const char* name;
+    long (*get)(const fftconv_plan*);
+    bool own;
+};
+const ComputedOption kComputedOptions[] = {
+    // spectral filter (fftconv_plan_set_spectral_filter): the mode, and whether the next spectral-row launch under it runs the
+    // specialised filter kernel (0 without a mode, and where the generic kernel's branch serves it)
+    {"spectral_filter", [](const fftconv_plan* p) { return p->opt_filter; }, true},
+    {"spectral_filter_fast", [](const fftconv_plan* p) { return (long)p->filter_fast(); }, true},
+    // border modes (fftconv_plan_set_border): the mode, where data sample 0 lies in the window, and whether the next image on this
+    // plan, with the options as they are, is mapped in the column kernel's load (0 without a border)
+    {"border_mode", [](const fftconv_plan* p) { return p->border_mode; }, true},
+    {"border_lead_h", [](const fftconv_plan* p) { return (long)(p->border_mode ? border_lead(p->g.max_kh) : 0); }, true},
+    {"border_lead_w", [](const fftconv_plan* p) { return (long)(p->border_mode ? border_lead(p->g.max_kw) : 0); }, true},
+    {"border_direct", [](const fftconv_plan* p) { return (long)p->border_direct(); }, true},
+    // the caller's rectangle (fftconv_plan_set_output_rect): its offsets (0 without one), and whether the output kernel stores it
+    // itself with the plan's current settings
+    {"rect_off_h", [](const fftconv_plan* p) { return (long)(p->opt_region == 5 ? p->off_h : 0); }, true},
+    {"rect_off_w", [](const fftconv_plan* p) { return (long)(p->opt_region == 5 ? p->off_w : 0); }, true},
+    {"rect_direct", [](const fftconv_plan* p) { return (long)p->rect_direct(); }, true},
+    // strided maps (fftconv_plan_set_output_stride): the strides, and whether the output kernel samples in its store with the plan's
+    // current settings (else the staged crop does; a block-wise plan always crops)
+    {"stride_h", [](const fftconv_plan* p) { return (long)p->stride_h; }, true},
+    {"stride_w", [](const fftconv_plan* p) { return (long)p->stride_w; }, true},
+    {"stride_direct", [](const fftconv_plan* p) { return (long)p->stride_direct(); }, true},
+    // 1 if, with the plan's current settings, the output kernel itself scales normalised maps (else the staged crop does)
+    {"normalise", [](const fftconv_plan* p) { return (long)(p->opt_score == FC_SCORE_CCOEFF_NORMED); }, true},      // (mode 1 is score 1)
+    {"norm_direct", [](const fftconv_plan* p) { return (long)p->norm_direct(); }, true},
+    // 1 if, with the plan's current settings, a spectral-row launch of more than one image walks over images
+    {"image_walk_active", [](const fftconv_plan* p) { return (long)p->image_walk_active(); }, true},
+    // typed image pixels (fftconv_plan_set_images_typed): 1 if a typed call on this plan, with the options as they are, converts in
+    // the column kernel's load; the format of the images the plan holds (0: fp32, an imported spectrum, or none)
+    {"pixel_direct", [](const fftconv_plan* p) { return (long)p->pixel_direct(); }, true},
+    {"pixel_format", [](const fftconv_plan* p) { return (p->tiled ? p->tiled->have_image : p->have_image()) ? p->pixel_format : 0; }, true},
+    {"blockwise", [](const fftconv_plan* p) { return (long)(p->tiled ? p->tiled->nblk : 0); }, true},      // number of blocks (0 = one pass)
+    {"overlap_save", [](const fftconv_plan* p) { return (long)(p->tiled && p->tiled->save); }, true},      // blocks stored by the output kernel (1) or summed (0)
+    // the images the plan holds -- fftconv_plan_set_images' count, 1 after fftconv_plan_set_image, 0 before any image
+    {"images", [](const fftconv_plan* p) { return (long)(p->tiled ? p->tiled->have_image : p->n_images); }, true},
+    {"rows_group", [](const fftconv_plan* p) { return (long)p->g.rows_group; }, false},
+    // which passes of this plan run on specialised (compile-time) kernels: bit 0 the spectral rows (w), bit 1 the column passes
+    // (h: image / kernel columns forwards, output columns); 3 = no generic kernel runs
+    {"specialised_kernels", [](const fftconv_plan* p) { return (long)((p->g.fast_rows.ok ? 1 : 0) | (p->g.fast_cols.ok ? 2 : 0)); }, false},
+    {"rows_slots_per_cu", [](const fftconv_plan* p) { return (long)p->g.rows_slots_per_cu; }, false},      // resident row workgroups per CU
+    {"profile", [](const fftconv_plan* p) { return (long)p->profile; }, false},
+    {"prepare_pending", [](const fftconv_plan* p) { return (long)p->a_holds.pending(); }, false},      // a recorded, not yet launched preparation
+};
+
+// the effects of a changed value (plan_rules.hpp: FX_*), in the order every setter performed them
+int apply_effects(fftconv_plan* plan, unsigned effects) {
+    if (effects & FX_WAIT) {
+        if (int rc = use_device(plan)) return rc;
+        HIP_TRY(hipStreamSynchronize(plan->stream));
+    }
+    if (effects & FX_RING) plan->release_ring();
+    if (effects & FX_COLUMNS) plan->a_holds.forget();
+    if (effects & FX_IMAGES) plan->n_images = 0;
+    return 0;
+}
+// a setter behind its argument check and its rule lookup, ahead of its assignments: kSetterEffects' row for it.  True if the call
+// ends here with rc -- a value that does not change where the row says so (0), or an effect that failed
+bool setter_done(fftconv_plan* plan, Setter s, bool unchanged, int& rc) {
+    const SetterEffects& e = setter_effects(s);
+    const bool early = e.unchanged_returns && unchanged;
+    rc = early ? 0 : apply_effects(plan, e.changed);
+    return early || rc != 0;
 }
 
 }  // namespace
@@ -687,20 +757,16 @@ int fftconv_plan_set_option(fftconv_plan* plan, const char* name, long value) {
     if (!plan || !name) return api_fail(FFTCONV_ERR_INVALID_ARG, "NULL argument");
     if (!strcmp(name, "map_format"))
         if (const char* why = map_format_error(value, plan->tiled != nullptr)) return api_fail(FFTCONV_ERR_INVALID_ARG, "%s", why);
-    if (plan->tiled && strcmp(name, "output_region") && strcmp(name, "rect_store") && strcmp(name, "stride_store")) {      // block-wise: options act on the block plan ("output_region", "rect_store", "stride_store": on this one, below)
+    const LongOption* o = find_option(name);
+    if (plan->tiled && !(o && (o->flags & OPT_OWN))) {      // block-wise: options act on the block plan (OPT_OWN: on this one, below)
         if (!strcmp(name, "verbose")) plan->opt_verbose = value != 0;
         return fftconv_plan_set_option(plan->tiled->sub, name, value);
     }
-    if (const LongOption* o = find_option(name, OPT_GET_ONLY)) {
+    if (o && !(o->flags & OPT_GET_ONLY)) {
         if ((o->flags & OPT_REJECT) && (value < o->lo || value > o->hi)) return api_fail(FFTCONV_ERR_INVALID_ARG, "option '%s' out of range", name);
-        if (o->flags & OPT_RING) {
-            if (int rc = use_device(plan)) return rc;
-            HIP_TRY(hipStreamSynchronize(plan->stream));
-            plan->release_ring();
-            if (o->member == &fftconv_plan::opt_host_stream && value > 2) return api_fail(FFTCONV_ERR_INVALID_ARG, "host_stream is 0, 1 or 2");
-        }
+        if (int rc = apply_effects(plan, o->effects)) return rc;
+        if (o->member == &fftconv_plan::opt_host_stream && value > 2) return api_fail(FFTCONV_ERR_INVALID_ARG, "host_stream is 0, 1 or 2");
         plan->*(o->member) = (o->flags & OPT_BOOL) ? (value != 0) : std::min(std::max(value, o->lo), o->hi);
-        if (o->flags & OPT_FORGETS) plan->a_holds.forget();
         return 0;
     }
     if (!strcmp(name, "profile")) {
@@ -753,9 +819,8 @@ int fftconv_plan_set_option(fftconv_plan* plan, const char* name, long value) {
         else if (value != 0) return api_fail(FFTCONV_ERR_INVALID_ARG, "output_region is 0 (window), 1 (full), 2 (same), 3 (valid) or 4 (pow2 window)");
         if (const char* why = output_stride_error(plan->stride_h, plan->stride_w, value)) return api_fail(FFTCONV_ERR_INVALID_ARG, "%s", why);
         if (oh < 1 || ow < 1) return api_fail(FFTCONV_ERR_INVALID_ARG, "output_region %ld is empty for %dx%d data and %dx%d kernels", value, g.H, g.W, g.max_kh, g.max_kw);
-        if (int rc = use_device(plan)) return rc;
-        HIP_TRY(hipStreamSynchronize(plan->stream));
-        plan->release_ring();          // sized for the map bytes
+        int rc;
+        if (setter_done(plan, Setter::OutputRegion, plan->opt_region == value, rc)) return rc;
         // (block-wise plans: g is the whole image's geometry; the blocks keep storing full-window maps and the region is cropped
         //  out of them on delivery, blockwise.cpp: tiled_deliver)
         plan->opt_region = value; plan->out_h = oh; plan->out_w = ow; plan->off_h = fh; plan->off_w = fw;
@@ -770,9 +835,9 @@ int fftconv_plan_set_output_rect(fftconv_plan* plan, int off_h, int off_w, int o
     if (const char* why = output_rect_error(off_h, off_w, out_h, out_w, g.fft_h, g.fft_w))
         return api_fail(FFTCONV_ERR_INVALID_ARG, "%s (rows [%d, %d) of columns [%d, %d) asked of the %d x %d window)", why, off_h, off_h + out_h, off_w,
                         off_w + out_w, g.fft_h, g.fft_w);
-    if (int rc = use_device(plan)) return rc;
-    HIP_TRY(hipStreamSynchronize(plan->stream));
-    plan->release_ring();          // sized for the map bytes
+    const bool same = plan->opt_region == 5 && plan->out_h == out_h && plan->out_w == out_w && plan->off_h == off_h && plan->off_w == off_w;
+    int rc;
+    if (setter_done(plan, Setter::OutputRect, same, rc)) return rc;
     plan->opt_region = 5; plan->out_h = out_h; plan->out_w = out_w; plan->off_h = off_h; plan->off_w = off_w;
     return 0;
 }
@@ -781,10 +846,8 @@ int fftconv_plan_set_output_stride(fftconv_plan* plan, int stride_h, int stride_
     if (!plan) return api_fail(FFTCONV_ERR_INVALID_ARG, "plan is NULL");
     if (const char* why = output_stride_error(stride_h, stride_w, plan->opt_region))
         return api_fail(FFTCONV_ERR_INVALID_ARG, "%s (strides (%d, %d) asked of a plan with output_region %ld)", why, stride_h, stride_w, plan->opt_region);
-    if (plan->stride_h == stride_h && plan->stride_w == stride_w) return 0;
-    if (int rc = use_device(plan)) return rc;
-    HIP_TRY(hipStreamSynchronize(plan->stream));
-    plan->release_ring();          // sized for the map bytes
+    int rc;
+    if (setter_done(plan, Setter::OutputStride, plan->stride_h == stride_h && plan->stride_w == stride_w, rc)) return rc;
     // (output-side state alone: the image, the prepared kernels and the extent stay)
     plan->stride_h = stride_h; plan->stride_w = stride_w;
     return 0;
@@ -792,22 +855,11 @@ int fftconv_plan_set_output_stride(fftconv_plan* plan, int stride_h, int stride_
 
 // fftconv_plan_set_normalisation and fftconv_plan_set_match_score behind their argument checks: one state, one set of rules
 static int set_score(fftconv_plan* plan, int score, int box_h, int box_w) {
-    if (plan->tiled)
-        return api_fail(FFTCONV_ERR_INVALID_ARG, "normalisation is not available on a block-wise plan (%d blocks: the window statistics span blocks); "
-                        "create a one-pass plan (fftconv_plan_options.blockwise = 1)", plan->tiled->nblk);
-    if (score != 0 && plan->border_mode)
-        return api_fail(FFTCONV_ERR_INVALID_ARG, "a border is on (fftconv_plan_set_border, mode %ld): the window statistics of normalised maps assume zero padding",
-                        plan->border_mode);
-    if (score != 0 && plan->opt_filter)
-        return api_fail(FFTCONV_ERR_INVALID_ARG, "spectral filter %ld is on (fftconv_plan_set_spectral_filter): the window statistics of a score belong to the "
-                        "plain product", plan->opt_filter);
+    if (int rc = plan_refused(plan, Ask::Score, score)) return rc;
     if (score == 0) box_h = box_w = 0;
-    if (plan->opt_score == score && plan->norm_box_h == box_h && plan->norm_box_w == box_w) return 0;      // nothing changes: the image stays
-    if (int rc = use_device(plan)) return rc;
-    HIP_TRY(hipStreamSynchronize(plan->stream));
-    // the kernel column spectra are those of the prepared kernels, or not; the plane belongs to (image, score, box) and the pixels are gone
-    plan->a_holds.forget();
-    plan->n_images = 0;
+    // (a change: the kernel column spectra are those of the prepared kernels, or not; the plane belongs to (image, score, box) and the pixels are gone)
+    int rc;
+    if (setter_done(plan, Setter::Score, plan->opt_score == score && plan->norm_box_h == box_h && plan->norm_box_w == box_w, rc)) return rc;
     plan->opt_score = score; plan->norm_box_h = box_h; plan->norm_box_w = box_w;
     return 0;
 }
@@ -834,19 +886,11 @@ int fftconv_plan_set_border(fftconv_plan* plan, int mode, float value) {
     if (const char* why = border_args_error(mode, value, g.H, g.W, g.max_kh, g.max_kw))
         return api_fail(FFTCONV_ERR_INVALID_ARG, "%s (mode %d, value %g asked of a plan with DATA %d x %d and MAX_KERNEL %d x %d)", why, mode, (double)value, g.H,
                         g.W, g.max_kh, g.max_kw);
-    if (plan->tiled)
-        return api_fail(FFTCONV_ERR_INVALID_ARG, "a border is not available on a block-wise plan (%d blocks: the blocks' own rims lie inside the image); "
-                        "create a one-pass plan (fftconv_plan_options.blockwise = 1)", plan->tiled->nblk);
-    if (mode != 0 && plan->opt_score)
-        return api_fail(FFTCONV_ERR_INVALID_ARG, "normalisation is on (fftconv_plan_set_normalisation): the window statistics of normalised maps assume zero padding");
+    if (int rc = plan_refused(plan, Ask::Border, mode)) return rc;
     if (mode != FC_BORDER_CONSTANT) value = 0.f;
-    if (plan->border_mode == mode && plan->border_value == value) return 0;      // nothing changes: the image and the rectangle stay
-    if (int rc = use_device(plan)) return rc;
-    HIP_TRY(hipStreamSynchronize(plan->stream));
-    plan->release_ring();          // sized for the map bytes
-    // as fftconv_plan_set_output_rect: prepared kernels are forgotten; and the spectrum belongs to (image, border)
-    plan->a_holds.forget();
-    plan->n_images = 0;
+    // (nothing changes: the image and the rectangle stay; a change: the spectrum belongs to (image, border))
+    int rc;
+    if (setter_done(plan, Setter::Border, plan->border_mode == mode && plan->border_value == value, rc)) return rc;
     plan->border_mode = mode; plan->border_value = value;
     if (mode) {      // the H x W "same" map anchored on the MAX_KERNEL box: the part of the window the cyclic wrap does not reach
         plan->opt_region = 5; plan->out_h = g.H; plan->out_w = g.W; plan->off_h = g.max_kh - 1; plan->off_w = g.max_kw - 1;
@@ -858,78 +902,26 @@ int fftconv_plan_set_border(fftconv_plan* plan, int mode, float value) {
 
 int fftconv_plan_set_spectral_filter(fftconv_plan* plan, int mode, float param) {
     if (!plan) return api_fail(FFTCONV_ERR_INVALID_ARG, "plan is NULL");
-    const Geometry& g = plan->g;
     if (const char* why = spectral_filter_args_error(mode, param))
         return api_fail(FFTCONV_ERR_INVALID_ARG, "%s (mode %d, param %g)", why, mode, (double)param);
+    if (int rc = plan_refused(plan, Ask::Filter, mode)) return rc;
     if (mode != FC_FILTER_WIENER) param = 0.f;
-    if (mode != FC_FILTER_PRODUCT) {
-        if (plan->tiled)
-            return api_fail(FFTCONV_ERR_INVALID_ARG, "a spectral filter is not available on a block-wise plan (%d blocks: the filter is defined on one transform of the "
-                            "whole window); create a one-pass plan (fftconv_plan_options.blockwise = 1)", plan->tiled->nblk);
-        if (g.F > 1)
-            return api_fail(FFTCONV_ERR_INVALID_ARG, "a spectral filter needs feature_dim 1 (this plan: %d): the filter of a feature sum is another formula", g.F);
-        if (plan->opt_score)
-            return api_fail(FFTCONV_ERR_INVALID_ARG, "matching score %ld is on (fftconv_plan_set_match_score / _set_normalisation): its window statistics belong to "
-                            "the plain product", plan->opt_score);
-        if (g.fast_rows.ok && !fast_rows_filter_built(g.Lw))
-            return api_fail(FFTCONV_ERR_INVALID_ARG, "the specialised spectral-row kernel of %d points has no filter form (it would spill registers); create the plan "
-                            "with fftconv_plan_options.kernel_path = 1 (generic kernels)", g.Lw);
-    }
     // (state of the spectral-row launches alone: the image, the prepared kernels, the stream and the output side stay; nothing to wait for)
+    int rc;
+    if (setter_done(plan, Setter::Filter, plan->opt_filter == mode && plan->filter_lambda == param, rc)) return rc;
     plan->opt_filter = mode; plan->filter_lambda = param;
     return 0;
 }
 
 int fftconv_plan_get_option(fftconv_plan* plan, const char* name, long* value) {
     if (!plan || !name || !value) return api_fail(FFTCONV_ERR_INVALID_ARG, "null argument");
-    // spectral filter (fftconv_plan_set_spectral_filter), read-only: the mode, and whether the next spectral-row launch under it runs
-    // the specialised filter kernel (0 without a mode, and where the generic kernel's branch serves it)
-    if (!strcmp(name, "spectral_filter")) { *value = plan->opt_filter; return 0; }
-    if (!strcmp(name, "spectral_filter_fast")) { *value = plan->filter_fast() ? 1 : 0; return 0; }
-    // border modes (fftconv_plan_set_border), read-only: the mode, where data sample 0 lies in the window, and whether the next
-    // image on this plan, with the options as they are, is mapped in the column kernel's load (0 without a border)
-    if (!strcmp(name, "border_mode")) { *value = plan->border_mode; return 0; }
-    if (!strcmp(name, "border_lead_h")) { *value = plan->border_mode ? border_lead(plan->g.max_kh) : 0; return 0; }
-    if (!strcmp(name, "border_lead_w")) { *value = plan->border_mode ? border_lead(plan->g.max_kw) : 0; return 0; }
-    if (!strcmp(name, "border_direct")) { *value = plan->border_direct() ? 1 : 0; return 0; }
-    // the caller's rectangle (fftconv_plan_set_output_rect), read-only: its offsets (0 without one), and whether the output
-    // kernel stores it itself with the plan's current settings
-    if (!strcmp(name, "rect_off_h")) { *value = plan->opt_region == 5 ? plan->off_h : 0; return 0; }
-    if (!strcmp(name, "rect_off_w")) { *value = plan->opt_region == 5 ? plan->off_w : 0; return 0; }
-    if (!strcmp(name, "rect_direct")) { *value = plan->rect_direct() ? 1 : 0; return 0; }
-    if (!strcmp(name, "rect_store")) { *value = plan->opt_rect_store; return 0; }
-    // strided maps (fftconv_plan_set_output_stride), read-only: the strides, and whether the output kernel samples in its store with
-    // the plan's current settings (else the staged crop does); "stride_store": the plan's own (a block-wise plan always crops)
-    if (!strcmp(name, "stride_h")) { *value = plan->stride_h; return 0; }
-    if (!strcmp(name, "stride_w")) { *value = plan->stride_w; return 0; }
-    if (!strcmp(name, "stride_direct")) { *value = plan->stride_direct() ? 1 : 0; return 0; }
-    if (!strcmp(name, "stride_store")) { *value = plan->opt_stride_store; return 0; }
-    // read-only: 1 if, with the plan's current settings, the output kernel itself scales normalised maps (else the staged crop does)
-    if (!strcmp(name, "normalise")) { *value = plan->opt_score == FC_SCORE_CCOEFF_NORMED ? 1 : 0; return 0; }      // (mode 1 is score 1)
-    if (!strcmp(name, "norm_direct")) { *value = plan->norm_direct() ? 1 : 0; return 0; }
-    // read-only: 1 if, with the plan's current settings, a spectral-row launch of more than one image walks over images
-    if (!strcmp(name, "image_walk_active")) { *value = plan->image_walk_active() ? 1 : 0; return 0; }
-    // typed image pixels (fftconv_plan_set_images_typed), read-only: 1 if a typed call on this plan, with the options as they are,
-    // converts in the column kernel's load; the format of the images the plan holds (0: fp32, an imported spectrum, or none)
-    if (!strcmp(name, "pixel_direct")) { *value = plan->pixel_direct() ? 1 : 0; return 0; }
-    if (!strcmp(name, "pixel_format")) {
-        const bool have = plan->tiled ? plan->tiled->have_image : plan->have_image();
-        *value = have ? plan->pixel_format : 0;
-        return 0;
-    }
-    if (!strcmp(name, "blockwise")) { *value = plan->tiled ? plan->tiled->nblk : 0; return 0; }   // read-only: number of blocks (0 = one pass)
-    if (!strcmp(name, "overlap_save")) { *value = plan->tiled && plan->tiled->save ? 1 : 0; return 0; }   // read-only: blocks stored by the output kernel (1) or summed (0)
-    // read-only: the images the plan holds -- fftconv_plan_set_images' count, 1 after fftconv_plan_set_image, 0 before any image
-    if (!strcmp(name, "images")) { *value = plan->tiled ? (plan->tiled->have_image ? 1 : 0) : plan->n_images; return 0; }
-    if (plan->tiled && strcmp(name, "output_region")) return fftconv_plan_get_option(plan->tiled->sub, name, value);
-    if (const LongOption* o = find_option(name, OPT_SET_ONLY)) { *value = plan->*(o->member); return 0; }
-    if (!strcmp(name, "rows_group")) { *value = plan->g.rows_group; return 0; }
-    // read-only: which passes of this plan run on specialised (compile-time) kernels: bit 0 the spectral rows (w), bit 1 the
-    // column passes (h: image / kernel columns forwards, output columns); 3 = no generic kernel runs
-    if (!strcmp(name, "specialised_kernels")) { *value = (plan->g.fast_rows.ok ? 1 : 0) | (plan->g.fast_cols.ok ? 2 : 0); return 0; }
-    if (!strcmp(name, "rows_slots_per_cu")) { *value = plan->g.rows_slots_per_cu; return 0; }   // read-only: resident row workgroups per CU
-    if (!strcmp(name, "profile")) { *value = plan->profile ? 1 : 0; return 0; }
-    if (!strcmp(name, "prepare_pending")) { *value = plan->a_holds.pending() ? 1 : 0; return 0; }   // read-only: a recorded, not yet launched preparation
+    const ComputedOption* c = nullptr;
+    for (const ComputedOption& k : kComputedOptions)
+        if (!strcmp(name, k.name)) { c = &k; break; }
+    const LongOption* o = c ? nullptr : find_option(name);
+    if (plan->tiled && !(c ? c->own : o && (o->flags & OPT_OWN))) return fftconv_plan_get_option(plan->tiled->sub, name, value);
+    if (c) { *value = c->get(plan); return 0; }
+    if (o && !(o->flags & OPT_SET_ONLY)) { *value = plan->*(o->member); return 0; }
     return api_fail(FFTCONV_ERR_INVALID_ARG, "unknown option '%s'", name);
 }
 

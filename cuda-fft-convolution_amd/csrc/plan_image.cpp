@@ -264,10 +264,8 @@ int fftconv_plan_spectrum(fftconv_plan* plan, void** device_ptr, size_t* bytes) 
 
 static int spectrum_exchange(fftconv_plan* p, float* spectrum, int location, bool to_natural) {
     if (!p || !spectrum) return api_fail(FFTCONV_ERR_INVALID_ARG, "NULL argument");
-    if (!to_natural && p->score_planes())
-        return api_fail(FFTCONV_ERR_INVALID_ARG, "normalisation is on (fftconv_plan_set_normalisation): an imported spectrum carries no window statistics");
-    if (!to_natural && p->border_mode)
-        return api_fail(FFTCONV_ERR_INVALID_ARG, "a border is on (fftconv_plan_set_border, mode %ld): an imported spectrum carries no border", p->border_mode);
+    if (!to_natural)
+        if (int rc = plan_refused(p, Ask::ImportSpectrum)) return rc;
     if (location != FFTCONV_HOST && location != FFTCONV_DEVICE) return api_fail(FFTCONV_ERR_INVALID_ARG, "bad location");
     if (p->tiled) return tiled_unsupported("the spectrum in the reference's order");
     const Geometry& g = p->g;
@@ -330,10 +328,7 @@ int fftconv_plan_use_spectrum_buffer(fftconv_plan* plan, void* device_ptr, size_
 
 int fftconv_plan_mark_spectrum_valid(fftconv_plan* plan) {
     if (!plan) return api_fail(FFTCONV_ERR_INVALID_ARG, "plan is NULL");
-    if (plan->score_planes())
-        return api_fail(FFTCONV_ERR_INVALID_ARG, "normalisation is on (fftconv_plan_set_normalisation): a spectrum written by the caller carries no window statistics");
-    if (plan->border_mode)
-        return api_fail(FFTCONV_ERR_INVALID_ARG, "a border is on (fftconv_plan_set_border, mode %ld): a spectrum written by the caller carries no border", plan->border_mode);
+    if (int rc = plan_refused(plan, Ask::MarkSpectrumValid)) return rc;
     if (plan->tiled) {
         if (!plan->tiled->spec_base()) return api_fail(FFTCONV_ERR_NO_IMAGE, "the plan has no spectrum buffer yet (fftconv_plan_spectrum / fftconv_plan_use_spectrum_buffer)");
         if (!plan->tiled->have_image) plan->pixel_format = FC_PIXEL_F32;

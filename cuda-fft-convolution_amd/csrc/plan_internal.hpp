@@ -3,6 +3,7 @@
 //   column_cache.hpp   what the column-spectrum buffer A holds between calls (KernelSet, ColumnCache): the one owner of that record
 //   image_route.hpp    the way of an image into a one-pass plan, decided once per call (ImageRoute, plan_image_route)
 //   output_route.hpp   the way of a group's maps out of a plan, decided once per group (OutputRoute, plan_output_route)
+//   plan_rules.hpp     which setter is refused while which state holds, and what a changed value invalidates (kPlanRules, kSetterEffects)
 //   fftconv_api.cpp    plan core: creation (plan_device_setup), the per-kernel loop (run_group: launch_kernel_cols,
 //                      launch_spectral_rows_batch, then the output stages), kernel preparation (prepare_kernels),
 //                      options (kLongOptions), two-step pair
@@ -34,6 +35,7 @@
 #include "ncc.hpp"
 #include "output_route.hpp"
 #include "pipeline.hpp"
+#include "plan_rules.hpp"
 
 // default of plan option "norm_store": fused -- it beat the staged route beyond the spread of alternating runs at both geometries
 // measured (cfg3's with 64 maps: 3.90 against 4.98 ms per convolve; cfg2's with 16: 107 against 125 us; profiles/ncc_ab.txt)
@@ -271,7 +273,8 @@ struct fftconv_plan {
     bool rect_direct() const { return plan_output_route(output_route_in(this, SinkKind::Packed)).store == OutStore::Rect; }
     // "image_walk" 1: a spectral-row launch of more than one image runs the kernel that keeps the transformed KERNEL row in
     // registers and walks over images (fast_rows_images.hpp) where the plan has it -- image_walk_active(); 0 (default), and
-    // every plan it cannot serve: the walk over kernels.  Nothing cached depends on it.
+    // every plan it cannot serve: the walk over kernels.  Nothing cached depends on it.  (It gives way to a spectral filter without
+    // a refusal: one of the two silent interactions plan_rules.hpp lists beside its table.)
     long opt_image_walk = 0;
     bool image_walk_active() const {
         return opt_image_walk && !opt_filter && !tiled && g.F == 1 && g.path_mode != 0 && g.fast_rows.ok && fast_rows_images_available(g.Lw, g.max_kw);
@@ -339,7 +342,8 @@ struct fftconv_plan {
     // pixel_format: FC_PIXEL_* of the images the plan holds (0 after every other way an image gets in; read with have_image()).
     long opt_pixel_store = FC_PIXEL_STORE_DEFAULT;
     long pixel_format = 0;
-    // (a typed image while a border is on is converted into I first and takes the fp32 border route from there: never direct)
+    // (a typed image while a border is on is converted into I first and takes the fp32 border route from there: never direct --
+    //  the other silent interaction plan_rules.hpp lists beside its table)
     bool pixel_direct() const { return !border_mode && fast_cols_fwd_px_direct(opt_pixel_store != 0, tiled != nullptr, g.fast_fwd, g.M); }
     DevBuf<float> IT;  // typed pixels on the device: the H2D copy of a typed host image (sized in bytes: floats_for)
     // Border modes (fftconv_plan_set_border; border.hpp): FC_BORDER_* of what the image is beyond its data (0: zeros, the library
@@ -578,3 +582,16 @@ struct TiledState {
         specs.release(); big.release(); tmp.release(); blk.release(); kstage.release(); crop.release();
     }
 };
+
+namespace fc {
+// plan_rules.hpp on this plan: 0 if asking `ask` for `value` passes, else the first rule's code, with its message recorded
+inline int plan_refused(const fftconv_plan* p, Ask ask, long value = 1) {
+    PlanRuleState s;
+    s.blocks = p->tiled ? p->tiled->nblk : 0;
+    s.F = p->g.F;
+    s.score = p->opt_score; s.border = p->border_mode; s.filter = p->opt_filter;
+    s.rows_fast = p->g.fast_rows.ok; s.filter_built = fast_rows_filter_built(p->g.Lw); s.Lw = p->g.Lw;
+    const Refusal r = plan_refusal(s, ask, value);
+    return r ? api_fail(r.rule->code, r.rule->fmt, r.arg) : 0;
+}
+}  // namespace fc

@@ -2,7 +2,8 @@
 
 A plan is a large mutable object (prepared / deferred kernel column spectra, the host-output ring, pinned buffers read in
 place, tile-queue counters, the tuned placement, region / rectangle, map format, stream, batch sizes, flip) whose consistency
-rests on hand-placed invalidations in csrc/fftconv_api.cpp.  A missed one faults nothing: it returns 0 and a wrong map.  The
+rests on the invalidations that csrc/plan_rules.hpp tabulates (kSetterEffects, and the FX_* column of kLongOptions in
+csrc/fftconv_api.cpp; the refusals: kPlanRules).  A missed one faults nothing: it returns 0 and a wrong map.  The
 walk draws a sequence of calls on one plan (draw_walk), a pure-Python model of include/fftconv.h says what every convolve must
 return and which calls must be refused (Model), and run_walk drives the plan on the GPU and compares.
 
