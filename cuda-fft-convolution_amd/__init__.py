@@ -127,6 +127,9 @@ class Profile(ctypes.Structure):
                 for i, n in enumerate(self.NAMES)}
 
 
+# fftconv_extrema (include/fftconv.h): one record of Plan.extrema()
+EXTREMA_DTYPE = [("max_value", "<f4"), ("max_row", "<i4"), ("max_col", "<i4"), ("min_value", "<f4"), ("min_row", "<i4"), ("min_col", "<i4")]
+
 # every symbol include/fftconv.h declares
 EXPORTED_SYMBOLS = (
     "fftconv_fft_size16", "fftconv_fft_size_pow2", "fftconv_last_error", "fftconv_version", "fftconv_device_count",
@@ -138,7 +141,7 @@ EXPORTED_SYMBOLS = (
     "fftconv_plan_use_spectrum_buffer", "fftconv_plan_export_spectrum", "fftconv_plan_import_spectrum",
     "fftconv_plan_convolve", "fftconv_plan_convolve_packed", "fftconv_plan_prepare_kernels_packed",
     "fftconv_plan_synchronize", "fftconv_plan_set_stream",
-    "fftconv_plan_set_option", "fftconv_plan_set_output_rect", "fftconv_plan_set_output_stride", "fftconv_plan_set_normalisation", "fftconv_plan_set_match_score", "fftconv_plan_set_border", "fftconv_plan_set_spectral_filter", "fftconv_plan_get_option", "fftconv_plan_get_profile",
+    "fftconv_plan_set_option", "fftconv_plan_set_output_rect", "fftconv_plan_set_output_stride", "fftconv_plan_set_extrema", "fftconv_plan_get_extrema", "fftconv_plan_extrema_device", "fftconv_plan_set_normalisation", "fftconv_plan_set_match_score", "fftconv_plan_set_border", "fftconv_plan_set_spectral_filter", "fftconv_plan_get_option", "fftconv_plan_get_profile",
     "fftconv_fft_data", "fftconv_conv_fft_data",
     "fftconv_multi_create", "fftconv_multi_destroy", "fftconv_multi_set_image", "fftconv_multi_import_spectrum",
     "fftconv_multi_convolve", "fftconv_multi_set_option", "fftconv_multi_get_option",
@@ -214,6 +217,9 @@ def load_library():
     lib.fftconv_plan_set_option.argtypes = [vp, ctypes.c_char_p, ctypes.c_long]
     lib.fftconv_plan_set_output_rect.argtypes = [vp, ci, ci, ci, ci]
     lib.fftconv_plan_set_output_stride.argtypes = [vp, ci, ci]
+    lib.fftconv_plan_set_extrema.argtypes = [vp, ci, ci]
+    lib.fftconv_plan_get_extrema.argtypes = [vp, ci, ci, vp]
+    lib.fftconv_plan_extrema_device.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(cs)]
     lib.fftconv_plan_set_normalisation.argtypes = [vp, ci, ci, ci]
     lib.fftconv_plan_set_match_score.argtypes = [vp, ci, ci, ci]
     lib.fftconv_plan_set_border.argtypes = [vp, ci, ctypes.c_float]
@@ -595,6 +601,34 @@ class Plan:
         always the staged crop), read-only "stride_direct", "stride_h", "stride_w"."""
         _check(self._lib.fftconv_plan_set_output_stride(self._h, int(stride_h), int(stride_w)))
         _check(self._lib.fftconv_plan_get_info(self._h, ctypes.byref(self.info)))
+
+    def set_extrema(self, on, max_maps=0):
+        """per-map extrema (fftconv_plan_set_extrema): while on, every convolve of up to max_maps maps also leaves one record per
+        delivered map on the device -- its largest and its smallest element and where they lie -- found while the maps are
+        written; the maps themselves are unchanged.  Read them with extrema() or extrema_device().  Option "extrema_store" (1, the
+        default: the output kernel finds them in its store where the plan can; 0: always the scan of the delivered maps),
+        read-only "extrema", "extrema_direct", "extrema_max_maps"."""
+        _check(self._lib.fftconv_plan_set_extrema(self._h, 1 if on else 0, int(max_maps)))
+        _check(self._lib.fftconv_plan_get_info(self._h, ctypes.byref(self.info)))
+
+    def extrema(self, first=0, n=None):
+        """the records [first, first + n) of the last convolve under set_extrema (n None: up to its last map), as a structured
+        NumPy array of EXTREMA_DTYPE: max_value, max_row, max_col, min_value, min_row, min_col -- row the fast index and col the
+        slow one of the delivered map (the element lies at col * out_h + row); ties go to the smallest col * out_h + row, a map
+        without an element that compares reports NaN and -1.  Waits for the plan's stream."""
+        import numpy as np
+        if n is None:      # ("extrema_maps": the maps of the last convolve under it; -1 before any -- the library then refuses the read)
+            n = max(self.get_option("extrema_maps"), 0) - int(first)
+        out = np.zeros(max(int(n), 0), dtype=EXTREMA_DTYPE)
+        _check(self._lib.fftconv_plan_get_extrema(self._h, int(first), int(n), out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def extrema_device(self):
+        """(device pointer, bytes) of the plan's record array (max_maps records of EXTREMA_DTYPE): stable until the next set_extrema
+        or the plan's end; its content is ordered on the plan's stream"""
+        ptr, nbytes = ctypes.c_void_p(), ctypes.c_size_t(0)
+        _check(self._lib.fftconv_plan_extrema_device(self._h, ctypes.byref(ptr), ctypes.byref(nbytes)))
+        return int(ptr.value or 0), int(nbytes.value)
 
     def set_normalisation(self, mode, box_h=0, box_w=0):
         """mode 1: every map becomes the zero-mean normalised cross-correlation over the box box_h x box_w -- the size every

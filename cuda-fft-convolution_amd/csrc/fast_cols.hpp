@@ -14,6 +14,7 @@
 // radix sequence the producers use.
 #pragma once
 #include "butterflies.hpp"
+#include "extrema.hpp"
 #include "fast_rows.hpp"  // power_chain, c32x2
 #include "fc_common.hpp"
 #include "fc_instrument.hpp"
@@ -244,8 +245,37 @@ template <ColStore S> struct ColStorePlane { using type = void; };
 template <> struct ColStorePlane<ColStore::RECT_SCALE> { using type = FastColsNormArgs; };
 template <> struct ColStorePlane<ColStore::RECT_ADD> { using type = FastColsSqdiffArgs; };
 template <> struct ColStorePlane<ColStore::RECT_STRIDE> { using type = FastColsStrideArgs; };
+template <class A, class... Rest>
+FC_HD const A* col_store_plane(const A& a, const Rest&...) { return &a; }
+
+// EXT instantiations only (per-map extrema found in the store, fftconv_plan_set_extrema; extrema.hpp): every wave of every launched
+// tile writes ONE partial -- the extrema of the elements it stored in that tile, or the empty sentinel -- to
+// partials[tile of the launch * waves of a workgroup + wave]: the slot depends on (map, tile, wave) and not on the workgroup that
+// ran the tile, so the static deal and the dynamic queue fill the same slots with the same values, nothing is cleared beforehand
+// and nothing stale is read.  The fold kernel (kernels_extrema.hip) reduces the tiles_per_kernel * waves slots of a map.  A kernel
+// argument of its own, the LAST one, for the reason given above FastColsNormArgs.
+struct FastColsExtremaArgs {
+    ExtremaPartial* partials = nullptr;
+};
 template <class A>
-FC_HD const A* col_store_plane(const A& a) { return &a; }
+FC_HD const A* col_store_last(const A& a) { return &a; }
+template <class A, class B>
+FC_HD const B* col_store_last(const A&, const B& b) { return &b; }
+// the wave's partial from its 64 lanes' -- cross-lane exchanges alone (the tile owns the LDS, and a wave needs no barrier); every
+// lane ends up with the result.  (Host builds run a workgroup's threads one after the other: the EXT stores exist on the device only.)
+FC_HD ExtremaPartial extrema_wave_reduce(ExtremaPartial p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    for (int s = 1; s < 64; s <<= 1) {
+        ExtremaPartial o;
+        o.max_value = __shfl_xor(p.max_value, s, 64);
+        o.max_index = __shfl_xor(p.max_index, s, 64);
+        o.min_value = __shfl_xor(p.min_value, s, 64);
+        o.min_index = __shfl_xor(p.min_index, s, 64);
+        p = extrema_merge(p, o);
+    }
+#endif
+    return p;
+}
 
 template <class C>
 struct ColState {
@@ -341,14 +371,21 @@ FC_HD int pair_of_unit(int u) {
 //   RECT_STRIDE                every sh-th row and sw-th column of the fp32 rectangle (RECT + STRIDE)
 // The last three take one more argument, their device struct (FastColsNormArgs, FastColsSqdiffArgs, FastColsStrideArgs); the others
 // take none.
-template <class C, bool TILED, bool SLICED = false, bool DYN = false, ColStore STORE = ColStore::PAIRS, class Ctx, class... PlaneArgs>
+// EXT (RECT, RECT_SCALE, RECT_ADD only; FastColsExtremaArgs, the last argument): per-map extrema -- beside its stores a thread keeps a
+// running (max, index) and (min, index) of the elements it actually stores, taken after the plane has been combined, the index that
+// of the delivered map; at the end of the tile the wave's 64 lanes are reduced across lanes and one lane writes the wave's partial.
+template <class C, bool TILED, bool SLICED = false, bool DYN = false, ColStore STORE = ColStore::PAIRS, bool EXT = false, class Ctx, class... PlaneArgs>
 FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int nwg, const PlaneArgs&... plane_args) {
     constexpr bool OUT16 = STORE == ColStore::PAIRS16 || STORE == ColStore::RECT16;
     constexpr bool RECT = STORE != ColStore::PAIRS && STORE != ColStore::PAIRS16;
     constexpr bool NORM = STORE == ColStore::RECT_SCALE, ADD = STORE == ColStore::RECT_ADD, STRIDE = STORE == ColStore::RECT_STRIDE;
     using Plane = typename ColStorePlane<STORE>::type;
-    static_assert(sizeof...(PlaneArgs) == (std::is_void_v<Plane> ? 0 : 1) && (std::is_same_v<Plane, PlaneArgs> && ...),
-                  "RECT_SCALE takes FastColsNormArgs, RECT_ADD FastColsSqdiffArgs, RECT_STRIDE FastColsStrideArgs, the other stores nothing");
+    static_assert(sizeof...(PlaneArgs) == (std::is_void_v<Plane> ? 0 : 1) + (EXT ? 1 : 0) && (EXT || (std::is_same_v<Plane, PlaneArgs> && ...)),
+                  "RECT_SCALE takes FastColsNormArgs, RECT_ADD FastColsSqdiffArgs, RECT_STRIDE FastColsStrideArgs, the other stores nothing; EXT adds FastColsExtremaArgs");
+    static_assert(!EXT || ((STORE == ColStore::RECT || STORE == ColStore::RECT_SCALE || STORE == ColStore::RECT_ADD) && C::NT % 64 == 0),
+                  "extrema are found in the fp32 rectangle stores, by whole waves");
+    [[maybe_unused]] const FastColsExtremaArgs* ext = nullptr;
+    if constexpr (EXT) ext = col_store_last(plane_args...);
     [[maybe_unused]] const FastColsNormArgs* nrm = nullptr;
     [[maybe_unused]] const FastColsSqdiffArgs* add = nullptr;
     [[maybe_unused]] const FastColsStrideArgs* strd = nullptr;
@@ -664,6 +701,7 @@ FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int
                     qs[0] = tl;
                 }
             }
+            [[maybe_unused]] ExtremaPartial ex = extrema_empty();      // EXT: of the elements this thread stores in this tile
             FC_NOUNROLL
             for (int r = 0; r < C::RND1; r++) {   // one butterfly at a time: the prefetched tile stays in registers
                 const int idx = t + NT * r;
@@ -719,6 +757,11 @@ FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int
                                     v[a].x += sx;
                                     v[a].y += sy;
                                 }
+                                if constexpr (EXT) {               // (the elements the stores below write: row hr if it is >= 0, row hr + 1 if it is < nrows)
+                                    const int e0 = extrema_rect_index(w0 + col, 2 * (j + a * m1), g.rect_w_lo, g.h_lo, g.out_pitch);
+                                    if (hr >= 0) extrema_take(ex, v[a].x, e0);
+                                    if ((unsigned)(hr + 1) < nrows) extrema_take(ex, v[a].y, e0 + 1);
+                                }
                                 if (strided_rows) {
                                     if constexpr (STRIDE) {
                                         const unsigned q0 = stride_quot(strd->h, (unsigned)hr), q1 = stride_quot(strd->h, (unsigned)(hr + 1));
@@ -749,6 +792,10 @@ FC_HD void fast_cols_body(Ctx& ctx, c32* lds, const FastColsArgs& g, int wg, int
                     });
                     }
                 }
+            }
+            if constexpr (EXT) {      // (every wave of the tile, whatever it stored: the fold reads every slot)
+                ex = extrema_wave_reduce(ex);
+                if ((t & 63) == 0) ext->partials[(size_t)tile * (NT / 64) + (t >> 6)] = ex;
             }
         });
         if constexpr (dyn) { dyn_tile = next; dyn_next = next < n_total ? FC_UNIFORM(qs[0]) : n_total; }

@@ -631,6 +631,7 @@ struct FastColsShape {
     MapPlane plane{};          // the rectangle family's fused scale / additive store only (fast_cols_rect_launch_shape below)
     bool strided = false;      // the strided store (fast_cols_stride_launch_shape below): the launch is k_fast_cols_stride's, with `stride`
     FastColsStrideArgs stride{};
+    FastColsExtremaArgs extrema{};      // per-map extrema found in the store (launch_fast_cols_rect_extrema, kernels.hpp): where the waves' partials go
 };
 inline FastColsShape fast_cols_launch_shape(int M, int T, const FastColsArgs& a, int want) {
     FastColsShape r{FastColsVariant::TILED_SLICED, a, 0};
@@ -770,6 +771,43 @@ constexpr bool fast_cols_sqdiff_built(int M) {
 }
 inline bool fast_cols_sqdiff_available(int M, bool y_tiled) { return y_tiled && fast_cols_lookup(M).ok && fast_cols_sqdiff_built(M); }
 // (whether a group's maps take the fused store or the staged combination: output_route.hpp)
+
+// Per-map extrema found in the store (fast_cols.hpp: EXT; plan entry fftconv_plan_set_extrema): the three fp32 rectangle stores -- RECT
+// (raw maps and score 2; the whole window too), RECT_SCALE (scores 1 and 3), RECT_ADD (score 4) -- with a running (max, index) and (min,
+// index) per thread and a cross-lane reduction per wave and tile.  Built by the family's rule, against the sibling of the same
+// store: a configuration whose kernel spills a vector register, uses scratch or holds a wave per SIMD less than its sibling in the
+// build's reports (csrc/kernels_cols_*ext_g*.rpt) is NOT built and listed here; its plans find the extrema with the scan kernel
+// (kernels_extrema.hip), as every route the fused store does not serve.  M = 544 and 2080 started here: their siblings are not built.
+// The running pairs cost 2 ... 11 registers; what that did at the register steps of a wave per SIMD (VGPRs and waves per SIMD of the EXT
+// kernel against its sibling's, static deal / dynamic queue where they differ):
+//   RECT    640 static 84 / 5 against 78 / 6; 480 dynamic 83 / 5 against 79 / 6; 240 dynamic 83 / 5 against 79 / 6
+//   SCALE   3072 static spills 1 register (8 bytes of scratch) at 128; 1152 dynamic 100 / 4 against 89 / 5; 768 dynamic 98 / 4 against
+//           91 / 5; 480 and 240 dynamic 83 / 5 against 79 / 6
+//   ADD     3072 static spills 1 register at 128; 1536 dynamic 98 / 4 against 95 / 5; 1152 101 / 4 and 97 / 4 against 91 / 5 and 88 / 5;
+//           768 101 / 4 and 98 / 4 against 91 / 5 and 88 / 5; 480 84 / 5 and 81 / 5 against 79 / 6 and 76 / 6; 240 dynamic 83 / 5
+//           against 79 / 6; 144 static 65 / 7 against 56 / 8
+// Every other configuration keeps its sibling's waves without a spill (+2 ... +11 registers: 154 at M = 4224, 157 / 159 at 2112, 92 / 95
+// at 576).  (tests/test_extrema_host.py holds the reports against the lists.)
+constexpr int FC_COLS_RECT_EXT_NOT_BUILT[] = {544, 2080, 640, 480, 240};
+constexpr int FC_COLS_NORM_EXT_NOT_BUILT[] = {544, 2080, 3072, 1152, 768, 480, 240};
+constexpr int FC_COLS_SQDIFF_EXT_NOT_BUILT[] = {544, 2080, 3072, 1536, 1152, 768, 480, 240, 144};
+constexpr bool fast_cols_rect_ext_built(int M) {
+    for (int x : FC_COLS_RECT_EXT_NOT_BUILT)
+        if (x == M) return false;
+    return fast_cols_rect_built(M);
+}
+constexpr bool fast_cols_norm_ext_built(int M) {
+    for (int x : FC_COLS_NORM_EXT_NOT_BUILT)
+        if (x == M) return false;
+    return fast_cols_norm_built(M);
+}
+constexpr bool fast_cols_sqdiff_ext_built(int M) {
+    for (int x : FC_COLS_SQDIFF_EXT_NOT_BUILT)
+        if (x == M) return false;
+    return fast_cols_sqdiff_built(M);
+}
+// slots of the partials one map of a fused launch fills: the tiles that hold a column of it x the waves of a workgroup
+inline int fast_cols_extrema_slots(const FastColsShape& sh, int NT) { return sh.a.tiles_per_kernel * (NT / 64); }
 
 struct FastColsTables {
     Plan1D plan;                   // radices (R1, R2, R3)

@@ -225,6 +225,12 @@ int run_group_impl(fftconv_plan* p, int n, const float* dk, int kh, int kw, cons
     // (a plan holding B images: the maps are the (image, kernel) grid, image-major, and nbY bounds the maps of a launch over it)
     const int B = p->images_held(), image_stride = sink.image_stride > 0 ? sink.image_stride : n;
     const int nbY = bs.nbM, nbA = bs.nbA;
+    if (p->extrema_on()) {      // (refused ahead of any launch: the plan stays as it was)
+        if (int rc = plan_refused(p, AskOutput::ExtremaGroup, 1, sink.window != nullptr)) return rc;
+        if (nbY > p->extrema_launch_maps)
+            return api_fail(FFTCONV_ERR_INVALID_ARG, "per-map extrema: a launch of %d maps, the partials were sized for %d (call fftconv_plan_set_extrema after \"batch_maps\")",
+                            nbY, p->extrema_launch_maps);
+    }
     FC_VERBOSE(p, "Kernel size: h=%d, w=%d", kh, kw);                 // src/cudaConvolutionFFT.cu:240
     FC_VERBOSE(p, "N Kernel: %d (maps per launch %d, kernels per column-spectrum chunk %d, %s)", n, nbY, nbA,
                (sink.packed || sink.window) ? "packed device output" : sink.location == FFTCONV_HOST ? "host output" : "device output");   // :68
@@ -263,10 +269,11 @@ int run_group_impl(fftconv_plan* p, int n, const float* dk, int kh, int kw, cons
                 if (int rc = ring_claim_staging(p, &buf)) return rc;
             float* dest = sink.window ? sink.window->base + (size_t)first * sink.window->map_stride            // where the maps of this batch go
                           : d.stage ? map_at(d.stage->p, (size_t)buf * nbY * d.oe, d.eb) : map_at(sink.packed, (size_t)first * d.oe, d.eb);
-            const OutLaunch ol{l.b0, l.nk, p->KC.p ? p->KC.p + (l.k0 - l.a0) : nullptr};      // (KC holds the chunk's kernels, as A does)
+            const OutLaunch ol{l.b0, l.nk, p->KC.p ? p->KC.p + (l.k0 - l.a0) : nullptr, sink.map0 + first};      // (KC holds the chunk's kernels, as A does)
             if (int rc = launch_output_cols(p, d.r, sink.window, d.r.need_O ? p->O.p : dest, ny, ol)) return rc;
             if (d.r.after != OutAfter::None)
                 if (int rc = launch_region(p, d.r, p->O.p, dest, ny, p->stream, ol)) return rc;
+            if (int rc = launch_extrema(p, d.r, dest, ny, ol)) return rc;      // (behind the last kernel that writes the maps, ahead of their copy-out)
             if (int rc = deliver_batch(p, d, sink, first, ny, buf, dest)) return rc;
         }
     }
@@ -312,6 +319,7 @@ const LongOption kLongOptions[] = {
     {"stride_store", &fftconv_plan::opt_stride_store, 0, 1, OPT_BOOL | OPT_OWN},   // (it only chooses the route of the next group: nothing cached depends on it)
     {"dynamic_tiles", &fftconv_plan::opt_dynamic_tiles, 0, 0, OPT_GET_ONLY},
     {"defer_prepare", &fftconv_plan::opt_defer_prepare, 0, 0, OPT_GET_ONLY},
+    {"extrema_store", &fftconv_plan::opt_extrema_store, 0, 1, OPT_BOOL | OPT_OWN},   // (it only chooses the route of the next group: nothing cached depends on it)
     {"image_walk", &fftconv_plan::opt_image_walk, 0, 1, OPT_BOOL},      // (nothing cached depends on it: no FX_COLUMNS)
     {"norm_store", &fftconv_plan::opt_norm_store, 0, 1, OPT_BOOL},       // (the kernel column spectra are the same either way: no FX_COLUMNS)
     {"pixel_store", &fftconv_plan::opt_pixel_store, 0, 1, OPT_BOOL},     // (it only chooses the route of the next typed call: no FX_COLUMNS)
@@ -354,6 +362,12 @@ const ComputedOption kComputedOptions[] = {
     {"stride_h", [](const fftconv_plan* p) { return (long)p->stride_h; }, true},
     {"stride_w", [](const fftconv_plan* p) { return (long)p->stride_w; }, true},
     {"stride_direct", [](const fftconv_plan* p) { return (long)p->stride_direct(); }, true},
+    // per-map extrema (fftconv_plan_set_extrema): the mode, the maps the records were sized for, and whether the output kernel finds them
+    // in its store with the plan's current settings (else the scan kernel reads the delivered maps; 0 while it is off)
+    {"extrema", [](const fftconv_plan* p) { return (long)p->extrema_on(); }, true},
+    {"extrema_max_maps", [](const fftconv_plan* p) { return (long)p->extrema_max_maps; }, true},
+    {"extrema_maps", [](const fftconv_plan* p) { return (long)p->extrema_maps; }, true},      // the maps of the last convolve under it (-1: none yet)
+    {"extrema_direct", [](const fftconv_plan* p) { return (long)p->extrema_direct(); }, true},
     // 1 if, with the plan's current settings, the output kernel itself scales normalised maps (else the staged crop does)
     {"normalise", [](const fftconv_plan* p) { return (long)(p->opt_score == FC_SCORE_CCOEFF_NORMED); }, true},      // (mode 1 is score 1)
     {"norm_direct", [](const fftconv_plan* p) { return (long)p->norm_direct(); }, true},
@@ -389,8 +403,9 @@ int apply_effects(fftconv_plan* plan, unsigned effects) {
 }
 // a setter behind its argument check and its rule lookup, ahead of its assignments: kSetterEffects' row for it.  True if the call
 // ends here with rc -- a value that does not change where the row says so (0), or an effect that failed
-bool setter_done(fftconv_plan* plan, Setter s, bool unchanged, int& rc) {
-    const SetterEffects& e = setter_effects(s);
+template <class SetterId>      // (Setter, or SetterAdded: the rows plan_rules.hpp lists beside the first table)
+bool setter_done(fftconv_plan* plan, SetterId s, bool unchanged, int& rc) {
+    const auto& e = setter_effects(s);
     const bool early = e.unchanged_returns && unchanged;
     rc = early ? 0 : apply_effects(plan, e.changed);
     return early || rc != 0;
@@ -592,6 +607,21 @@ int fc::plan_create_internal(fftconv_plan** plan, int data_h, int data_w, int fe
     return 0;
 }
 
+// per-map extrema around a convolve of n_kernel kernels on a one-pass plan: more maps than the records hold are refused ahead of any
+// launch; the records count once every group has been queued
+static int extrema_begin(fftconv_plan* p, int n_kernel) {
+    if (!p->extrema_on()) return 0;
+    const long maps = (long)n_kernel * p->images_held();
+    if (maps > p->extrema_max_maps)
+        return api_fail(FFTCONV_ERR_INVALID_ARG, "per-map extrema: a convolve of %ld maps on a plan whose records hold %d (fftconv_plan_set_extrema: max_maps)", maps,
+                        p->extrema_max_maps);
+    p->extrema_maps = -1;      // (a call that fails half-way leaves no records to read)
+    return 0;
+}
+static void extrema_end(fftconv_plan* p, int n_kernel) {
+    if (p->extrema_on()) p->extrema_maps = n_kernel * p->images_held();
+}
+
 extern "C" {
 
 int fftconv_plan_destroy(fftconv_plan* plan) {
@@ -628,7 +658,8 @@ int fftconv_plan_get_info(const fftconv_plan* plan, fftconv_plan_info* info) {
     info->out_w = plan->map_w();
     info->out_map_bytes = plan->out_map_bytes();
     info->workspace_bytes = plan->A.bytes() + plan->Y.bytes() + plan->K.bytes() + plan->O.bytes() + plan->I.bytes() + plan->IT.bytes() + plan->IE.bytes() +
-                            plan->ND.bytes() + plan->KN.bytes() + plan->KC.bytes() + plan->NS64.bytes();      // (matching scores: all 0 until one is on)
+                            plan->ND.bytes() + plan->KN.bytes() + plan->KC.bytes() + plan->NS64.bytes() +      // (matching scores: all 0 until one is on)
+                            plan->EXR.bytes() + plan->EXP.bytes();                                             // (per-map extrema: likewise)
     if (const TiledState* ts = plan->tiled) {     // block-wise: the window of the whole image; the spectrum is every block's
         info->spectrum_bytes = ts->spec_total() * sizeof(c32);
         info->map_bytes = ts->big_map() * sizeof(float);
@@ -655,9 +686,12 @@ int fftconv_plan_convolve_packed(fftconv_plan* plan, int n_kernel, const float* 
         if (rc) (void)keep_error([&] { return hipStreamSynchronize(plan->tiled->sub->stream); });
         return rc;
     }
+    if (int rc = extrema_begin(plan, n_kernel)) return rc;
     Sink sink;
     sink.packed = out_device;
-    return run_group(plan, n_kernel, kernels_device, kernel_h, kernel_w, sink);
+    const int rc = run_group(plan, n_kernel, kernels_device, kernel_h, kernel_w, sink);
+    if (!rc) extrema_end(plan, n_kernel);
+    return rc;
 }
 
 int fftconv_plan_prepare_kernels_packed(fftconv_plan* plan, int n_kernel, const float* kernels_device, int kernel_h,
@@ -692,6 +726,7 @@ int fftconv_plan_convolve(fftconv_plan* plan, int n_kernel, const float* const* 
     // (a plan holding B images: out[] has B * n_kernel entries, image-major -- out[b * n_kernel + k] is image b (x) kernel k)
     for (long m = n_kernel; m < (long)n_kernel * p->images_held(); m++)
         if (!out[m]) return api_fail(FFTCONV_ERR_INVALID_ARG, "output %ld is NULL (the plan holds %d images: %ld maps)", m, p->n_images, (long)n_kernel * p->n_images);
+    if (int rc = extrema_begin(p, n_kernel)) return rc;
     // groups of consecutive kernels of equal size
     for (int k0 = 0, k1; k0 < n_kernel; k0 = k1) {
         k1 = same_size_run_end(kernel_h, kernel_w, k0, n_kernel);
@@ -717,6 +752,7 @@ int fftconv_plan_convolve(fftconv_plan* plan, int n_kernel, const float* const* 
         sink.ptrs = out + k0;
         sink.location = out_location;
         sink.image_stride = n_kernel;
+        sink.map0 = k0;
         const int rcg = run_group(p, n, dk, kh, kw, sink);
         if (kernels_pinned) {      // (whatever the group's outcome: the launches that read the buffer are in the stream)
             if (rcg) (void)keep_error([&] { return p->pin_k.mark(p->stream); });
@@ -725,6 +761,7 @@ int fftconv_plan_convolve(fftconv_plan* plan, int n_kernel, const float* const* 
         if (rcg) return rcg;
     }
     if (out_location == FFTCONV_HOST) HIP_TRY(hipStreamSynchronize(p->stream));
+    extrema_end(p, n_kernel);
     return 0;
 }
 
@@ -850,6 +887,53 @@ int fftconv_plan_set_output_stride(fftconv_plan* plan, int stride_h, int stride_
     if (setter_done(plan, Setter::OutputStride, plan->stride_h == stride_h && plan->stride_w == stride_w, rc)) return rc;
     // (output-side state alone: the image, the prepared kernels and the extent stay)
     plan->stride_h = stride_h; plan->stride_w = stride_w;
+    return 0;
+}
+
+int fftconv_plan_set_extrema(fftconv_plan* plan, int mode, int max_maps) {
+    if (!plan) return api_fail(FFTCONV_ERR_INVALID_ARG, "plan is NULL");
+    if (mode != 0 && mode != 1) return api_fail(FFTCONV_ERR_INVALID_ARG, "per-map extrema: mode is 0 (off) or 1 (on), not %d", mode);
+    if (mode == 1 && max_maps < 1) return api_fail(FFTCONV_ERR_INVALID_ARG, "per-map extrema: max_maps must be at least 1 (%d asked)", max_maps);
+    if (int rc = plan_refused(plan, AskOutput::Extrema, mode)) return rc;
+    if (mode == 0) max_maps = 0;
+    int rc;
+    if (setter_done(plan, SetterAdded::Extrema, plan->extrema_max_maps == max_maps, rc)) return rc;
+    // (output-side state alone: the image, the prepared kernels, the stream and the extent stay)
+    plan->EXR.release(); plan->EXP.release();
+    plan->extrema_max_maps = plan->extrema_slots = plan->extrema_launch_maps = 0;
+    plan->extrema_maps = -1;
+    if (mode == 0) return 0;
+    // the partials of one launch: per map the fused store's slots for the whole window (a rectangle has fewer tiles) or the scan's
+    // blocks, whichever is more; the maps of a launch as batch_sizes bounds them
+    const Geometry& g = plan->g;
+    int slots = FC_EXTREMA_SCAN_MAX_BLOCKS;
+    if (g.fast_cols.ok) slots = std::max(slots, tiles_for(g.fft_w, g.fast_cols.T) * (g.fast_cols.NT / 64));
+    const int launch_maps = (int)std::min<long>(max_maps, plan->opt_batch_maps > 0 ? plan->opt_batch_maps : 64);
+    if (int rce = plan->EXR.ensure((size_t)max_maps)) return rce;
+    if (int rce = plan->EXP.ensure((size_t)slots * launch_maps)) { plan->EXR.release(); return rce; }
+    plan->extrema_max_maps = max_maps; plan->extrema_slots = slots; plan->extrema_launch_maps = launch_maps;
+    return 0;
+}
+
+int fftconv_plan_get_extrema(fftconv_plan* plan, int first_map, int n_maps, fftconv_extrema* out_host) {
+    if (!plan || !out_host) return api_fail(FFTCONV_ERR_INVALID_ARG, "NULL argument");
+    if (!plan->extrema_on()) return api_fail(FFTCONV_ERR_INVALID_ARG, "per-map extrema are off (fftconv_plan_set_extrema)");
+    if (plan->extrema_maps < 0) return api_fail(FFTCONV_ERR_INVALID_ARG, "per-map extrema: no convolve has run since fftconv_plan_set_extrema");
+    if (first_map < 0 || n_maps < 0 || (long)first_map + n_maps > plan->extrema_maps)
+        return api_fail(FFTCONV_ERR_INVALID_ARG, "per-map extrema: records [%d, %d) asked, the last convolve wrote %d", first_map, first_map + n_maps, plan->extrema_maps);
+    if (n_maps == 0) return 0;
+    if (int rc = use_device(plan)) return rc;
+    static_assert(sizeof(fftconv_extrema) == sizeof(ExtremaRecord), "the record the kernels write is the caller's");
+    HIP_TRY(hipMemcpyAsync(out_host, plan->EXR.p + first_map, (size_t)n_maps * sizeof(ExtremaRecord), hipMemcpyDeviceToHost, plan->stream));
+    HIP_TRY(hipStreamSynchronize(plan->stream));
+    return 0;
+}
+
+int fftconv_plan_extrema_device(fftconv_plan* plan, void** device_ptr, size_t* bytes) {
+    if (!plan || !device_ptr || !bytes) return api_fail(FFTCONV_ERR_INVALID_ARG, "NULL argument");
+    if (!plan->extrema_on()) return api_fail(FFTCONV_ERR_INVALID_ARG, "per-map extrema are off (fftconv_plan_set_extrema)");
+    *device_ptr = plan->EXR.p;
+    *bytes = (size_t)plan->extrema_max_maps * sizeof(ExtremaRecord);
     return 0;
 }
 

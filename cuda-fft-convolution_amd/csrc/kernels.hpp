@@ -106,6 +106,16 @@ hipError_t launch_fast_cols(int M, int T, const FastColsArgs& a, int num_cus, hi
 // the strided store: fp32 maps, no plane.  hipErrorInvalidValue for a launch the family does not have (row-major or sliced), for a
 // plane that is not filled in, and for a configuration whose kernel is not built (fast_cols_*_built)
 hipError_t launch_fast_cols_rect(int M, int T, const FastColsShape& shape, hipStream_t s);
+// the same family with the per-map extrema found in the store (kernels_cols_*ext_g<G>.hip; fast_cols.hpp: EXT): fp32 maps, no stride;
+// shape.extrema.partials takes fast_cols_extrema_slots partials per map of the launch.  hipErrorInvalidValue as above, and for a
+// configuration whose EXT kernel is not built (fast_cols_*_ext_built)
+hipError_t launch_fast_cols_rect_extrema(int M, int T, const FastColsShape& shape, hipStream_t s);
+// ---- per-map extrema (kernels_extrema.hip; extrema.hpp)
+// the scan: nmaps dense maps of map_elems elements of `format` (FC_MAP_*) from maps on, map_stride elements apart, where they lie on
+// the device; extrema_scan_blocks(map bytes) partials per map, from partials on
+hipError_t launch_extrema_scan(const void* maps, size_t map_elems, size_t map_stride, int format, int nmaps, ExtremaPartial* partials, hipStream_t s);
+// the fold: records[m] = the record of the per_map partials of map m (maps of out_h rows per column), m < nmaps
+hipError_t launch_extrema_fold(const ExtremaPartial* partials, int per_map, int nmaps, int out_h, ExtremaRecord* records, hipStream_t s);
 hipError_t launch_fast_cols_fwd(int M, int T, bool pruned, const FastColsFwdArgs& a, int num_cus, hipStream_t s);
 // image columns of typed pixels (kernels_cols_fwd_px_g<G>.hip; pixel_format.hpp): a.in holds elements of px.format, px from
 // fast_cols_fwd_pixel_load; hipErrorInvalidValue for fp32 pixels and for a configuration that is not built (fast_cols_fwd_px_built)
@@ -144,6 +154,11 @@ template <int G> GroupResult launch_fast_cols_rect_group(int M, int T, const Fas
 template <int G> GroupResult launch_fast_cols_rect16_group(int M, int T, const FastColsShape& shape, hipStream_t s);
 template <int G> GroupResult launch_fast_cols_rect_scale_group(int M, int T, const FastColsShape& shape, hipStream_t s);
 template <int G> GroupResult launch_fast_cols_rect_add_group(int M, int T, const FastColsShape& shape, hipStream_t s);
+// (the fp32 stores with the per-map extrema found in the store: kernels_cols_ext_g<G>.hip, kernels_cols_norm_ext_g<G>.hip,
+//  kernels_cols_sqdiff_ext_g<G>.hip; launch_fast_cols_rect_extrema picks among them)
+template <int G> GroupResult launch_fast_cols_rect_ext_group(int M, int T, const FastColsShape& shape, hipStream_t s);
+template <int G> GroupResult launch_fast_cols_rect_scale_ext_group(int M, int T, const FastColsShape& shape, hipStream_t s);
+template <int G> GroupResult launch_fast_cols_rect_add_ext_group(int M, int T, const FastColsShape& shape, hipStream_t s);
 // (the strided store: kernels_cols_stride_g<G>.hip)
 template <int G> GroupResult launch_fast_cols_rect_stride_group(int M, int T, const FastColsShape& shape, hipStream_t s);
 template <int G> GroupResult launch_fast_cols_fwd_group(int M, int T, bool pruned, const FastColsFwdArgs& a, int num_cus, hipStream_t s);

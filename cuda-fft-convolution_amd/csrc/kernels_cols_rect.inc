@@ -9,6 +9,10 @@
 //                                                                         fftconv_plan_set_match_score)
 //   kernels_cols_stride_g<G>.hip    FC_TU_STRIDE = 1 k_fast_cols_stride   fp32 maps, every sh-th row and sw-th column (STRIDE;
 //                                                                         fftconv_plan_set_output_stride)
+// With FC_TU_EXTREMA = 1 beside none of the others, FC_TU_NORM or FC_TU_SQDIFF: the same three fp32 stores with the per-map extrema found
+// in the store (EXT; fftconv_plan_set_extrema), under names of their own again --
+//   kernels_cols_ext_g<G>.hip         k_fast_cols_rect_ext     kernels_cols_norm_ext_g<G>.hip    k_fast_cols_norm_ext
+//   kernels_cols_sqdiff_ext_g<G>.hip  k_fast_cols_sqdiff_ext
 // Translation units of their own, so that every other kernel compiles exactly what it compiled before, and kernel names of their
 // own, so that no report filter of one family picks up another.  Tiled intermediate and unsliced launches only: two instantiations
 // (static deal, dynamic tile queue) per configuration and kernel.  A plan without a rectangle launches the NORM / ADD kernels with
@@ -27,13 +31,46 @@
 #ifndef FC_TU_STRIDE
 #define FC_TU_STRIDE 0
 #endif
+#ifndef FC_TU_EXTREMA
+#define FC_TU_EXTREMA 0
+#endif
 
 namespace fc {
 namespace {
 
 // FC_RECT_KERNEL: the unit's kernel; FC_RECT_GROUP / FC_RECT_BUILT: its group entry (kernels.hpp) and its list of built configurations
 // (fast_paths.hpp); FC_RECT_ARGS(sh): the kernel's arguments from the launch shape -- the plane's device struct is filled here
-#if FC_TU_STRIDE
+#if FC_TU_EXTREMA && FC_TU_SQDIFF
+#define FC_RECT_KERNEL k_fast_cols_sqdiff_ext
+#define FC_RECT_GROUP launch_fast_cols_rect_add_ext_group
+#define FC_RECT_BUILT fast_cols_sqdiff_ext_built
+#define FC_RECT_ARGS(sh) (sh).a, fast_cols_sqdiff_args((sh).plane), (sh).extrema
+template <class Cfg, bool DYN>
+__global__ void __launch_bounds__(Cfg::NT, 3) k_fast_cols_sqdiff_ext(FastColsArgs a, FastColsSqdiffArgs q, FastColsExtremaArgs x) {
+    DevPhaseCtx<ColPairState<Cfg>> ctx;
+    fast_cols_body<Cfg, true, false, DYN, ColStore::RECT_ADD, true>(ctx, reinterpret_cast<c32*>(fc_smem), a, (int)blockIdx.x, (int)gridDim.x, q, x);
+}
+#elif FC_TU_EXTREMA && FC_TU_NORM
+#define FC_RECT_KERNEL k_fast_cols_norm_ext
+#define FC_RECT_GROUP launch_fast_cols_rect_scale_ext_group
+#define FC_RECT_BUILT fast_cols_norm_ext_built
+#define FC_RECT_ARGS(sh) (sh).a, fast_cols_norm_args((sh).plane), (sh).extrema
+template <class Cfg, bool DYN>
+__global__ void __launch_bounds__(Cfg::NT, 3) k_fast_cols_norm_ext(FastColsArgs a, FastColsNormArgs n, FastColsExtremaArgs x) {
+    DevPhaseCtx<ColPairState<Cfg>> ctx;
+    fast_cols_body<Cfg, true, false, DYN, ColStore::RECT_SCALE, true>(ctx, reinterpret_cast<c32*>(fc_smem), a, (int)blockIdx.x, (int)gridDim.x, n, x);
+}
+#elif FC_TU_EXTREMA
+#define FC_RECT_KERNEL k_fast_cols_rect_ext
+#define FC_RECT_GROUP launch_fast_cols_rect_ext_group
+#define FC_RECT_BUILT fast_cols_rect_ext_built
+#define FC_RECT_ARGS(sh) (sh).a, (sh).extrema
+template <class Cfg, bool DYN>
+__global__ void __launch_bounds__(Cfg::NT, 3) k_fast_cols_rect_ext(FastColsArgs a, FastColsExtremaArgs x) {
+    DevPhaseCtx<ColPairState<Cfg>> ctx;
+    fast_cols_body<Cfg, true, false, DYN, ColStore::RECT, true>(ctx, reinterpret_cast<c32*>(fc_smem), a, (int)blockIdx.x, (int)gridDim.x, x);
+}
+#elif FC_TU_STRIDE
 #define FC_RECT_KERNEL k_fast_cols_stride
 #define FC_RECT_GROUP launch_fast_cols_rect_stride_group
 #define FC_RECT_BUILT fast_cols_stride_built

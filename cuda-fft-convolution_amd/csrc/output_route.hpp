@@ -28,6 +28,14 @@
 //   tuning    a score with a plane is never tuned and leaves the intermediate marked fresh (Skip); a window is never probed (None);
 //             else the probes are the group's own launch, Rect (the strided launch of RectStride included) or Plain, into `target` -- every batch's destination when that is the
 //             caller's memory, else the one staging buffer.
+//   extrema   per-map extrema (fftconv_plan_set_extrema) while they are on: Fused -- found by the output kernel in its store (fast_cols.hpp:
+//             EXT) -- where "extrema_store" is on and the group's store is one of the three fp32 rectangle stores whose EXT kernel is built:
+//             Rect, RectScale, RectAdd as decided above, or the Plain store of the whole fp32 window of a one-pass plan on the tiled
+//             intermediate, which then becomes Rect with the window standing in for the rectangle (as it does for RectScale / RectAdd).
+//             Scan -- everything else (16-bit maps, named regions, strides, every crop / pad, generic and Bluestein output kernels, the
+//             row-major intermediate, configurations that are not built, "extrema_store" 0): the scan kernel reads the delivered maps
+//             where they lie on the device -- the caller's packed buffer or the staging -- before any copy-out.  The probes stay those of
+//             the store without extrema (the Plain launch writes the same whole windows).
 //   error     an output window on a plan without the specialised output kernel, or with any score on: refused.
 #pragma once
 #include <cstddef>
@@ -54,6 +62,7 @@ enum class OutBuffer { Caller, O, OC };
 enum class OutExtent { Window, Region, Rect };    // what a delivered map holds: "output_region" 0, 1-4, 5
 enum class OutAfter { None, Crop, Pad };
 enum class TuneProbe { Skip, None, Plain, Rect };
+enum class OutExtrema { Off, Fused, Scan };
 
 struct OutputRouteIn {
     SinkKind sink = SinkKind::Packed;
@@ -72,6 +81,9 @@ struct OutputRouteIn {
     int stride_h = 1, stride_w = 1;
     bool stride_store = true, stride_built = false;
     bool strided() const { return stride_h != 1 || stride_w != 1; }
+    // per-map extrema (fftconv_plan_set_extrema); the defaults are "off"
+    bool extrema = false, extrema_store = true;
+    bool extrema_rect_built = false, extrema_norm_built = false, extrema_sqdiff_built = false;      // fast_paths.hpp: fast_cols_*_ext_built of the plan's M
 };
 
 struct OutputRoute {
@@ -88,6 +100,7 @@ struct OutputRoute {
     int staging_copies = 0;
     bool pinned_one_map = false;               // Pinned: a launch of ONE map goes through the pinned buffer too
     TuneProbe probe = TuneProbe::Skip;
+    OutExtrema extrema = OutExtrema::Off;
     bool staged() const { return route == Route::Copies || route == Route::Pinned || route == Route::Ring; }
     bool fused() const { return store == OutStore::RectScale || store == OutStore::RectAdd; }
 };
@@ -109,6 +122,21 @@ inline OutputRoute plan_output_route(const OutputRouteIn& in) {
         if (one_pass_tiled && in.stride_store && in.stride_built && in.map_format == FC_MAP_F32 && r.extent != OutExtent::Region) r.store = OutStore::RectStride;
     } else if (one_pass_tiled && r.extent == OutExtent::Rect && in.rect_store && in.rect_built) r.store = OutStore::Rect;
     if (r.store == OutStore::Generic && in.fast_cols) r.store = OutStore::Plain;
+    const OutStore probe_store = r.store;
+    if (in.extrema && !window) {
+        r.extrema = OutExtrema::Scan;
+        if (in.extrema_store && in.map_format == FC_MAP_F32) {
+            if (r.fused()) {
+                if (r.plane == OutPlane::Q ? in.extrema_sqdiff_built : in.extrema_norm_built) r.extrema = OutExtrema::Fused;
+            } else if (r.store == OutStore::Rect) {
+                if (in.extrema_rect_built) r.extrema = OutExtrema::Fused;
+            } else if (r.store == OutStore::Plain && one_pass_tiled && r.plane == OutPlane::None && !in.strided() && r.extent == OutExtent::Window &&
+                       in.rect_built && in.extrema_rect_built) {
+                r.store = OutStore::Rect;
+                r.extrema = OutExtrema::Fused;
+            }
+        }
+    }
     const bool dense = r.store == OutStore::Rect || r.store == OutStore::RectStride || r.fused();      // the kernel stores the delivered maps itself
     if (!dense && (r.extent != OutExtent::Window || r.plane != OutPlane::None || in.strided())) r.after = in.region == 4 ? OutAfter::Pad : OutAfter::Crop;
     const bool cropped = r.after != OutAfter::None;
@@ -128,7 +156,7 @@ inline OutputRoute plan_output_route(const OutputRouteIn& in) {
     }
     r.target = cropped ? OutBuffer::O : r.staging;
     r.probe = r.plane != OutPlane::None ? TuneProbe::Skip : window ? TuneProbe::None
-              : r.store == OutStore::Rect || r.store == OutStore::RectStride ? TuneProbe::Rect : TuneProbe::Plain;
+              : probe_store == OutStore::Rect || probe_store == OutStore::RectStride ? TuneProbe::Rect : TuneProbe::Plain;
     return r;
 }
 

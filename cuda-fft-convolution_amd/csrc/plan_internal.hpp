@@ -48,6 +48,11 @@ constexpr long FC_PIXEL_STORE_DEFAULT = 1;
 // load beat the staged extension beyond the spread of alternating runs at every shape measured (the device-resident set_images
 // step: cfg5's 35.3 against 44.8 us, cfg3's 91.3 against 124.7, cfg1's x 64 32.4 against 44.2; profiles/border_ab.txt)
 constexpr long FC_BORDER_STORE_DEFAULT = 1;
+// default of plan option "extrema_store" (per-map extrema, fftconv_plan_set_extrema): fused -- the output kernel finds them in its store.
+// It beat the scan beyond the spread of alternating runs at cfg3's geometry with 64 maps (raw maps 3.57 against 3.76 ms per convolve,
+// score 1 4.42 against 4.59, score 4 4.40 against 4.59); at cfg2's with 16 it is level for raw maps (100 against 99 us) and ahead under
+// a score (123 against 128, 116 against 123; profiles/extrema_ab.txt)
+constexpr long FC_EXTREMA_STORE_DEFAULT = 1;
 constexpr long FC_HOST_MIN_KB = 1024;   // default of plan option "host_min_kb" (0 reproduces the threaded path for small maps: tests)
 
 #define HIP_TRY(call)                                                                              \
@@ -332,6 +337,20 @@ struct fftconv_plan {
     long opt_map_format = 0;
     size_t elem_bytes() const { return fc_map_elem_bytes((int)opt_map_format); }
     size_t out_map_bytes() const { return out_elems() * elem_bytes(); }
+    // fftconv_plan_set_extrema (extrema.hpp): per-map extrema of the delivered maps.  extrema_max_maps > 0 while it is on: EXR holds that
+    // many records (record m: delivered map m of the last convolve), EXP the partials of ONE output launch -- extrema_slots per map,
+    // enough for the fused store of the whole window (its tiles x the waves of a workgroup) and for the scan's blocks of the largest
+    // map the plan can deliver, times extrema_launch_maps, the maps of a launch ("batch_maps" as the setter found it, at most max_maps) --
+    // both sized by the setter, never by a convolve.  extrema_maps: the maps of the last
+    // convolve under it (-1: none yet).  "extrema_store" 1: the output kernel finds them in its store where it can (fast_cols.hpp: EXT)
+    // -- OutExtrema::Fused; 0, and every route it cannot serve: the scan kernel reads the delivered maps (output_route.hpp).
+    long opt_extrema_store = FC_EXTREMA_STORE_DEFAULT;
+    int extrema_max_maps = 0, extrema_slots = 0, extrema_launch_maps = 0, extrema_maps = -1;
+    DevBuf<ExtremaRecord> EXR;
+    DevBuf<ExtremaPartial> EXP;
+    bool extrema_on() const { return extrema_max_maps > 0; }
+    // read-only option "extrema_direct": whether the route of a sink that is not a window finds them in the store
+    bool extrema_direct() const { return plan_output_route(output_route_in(this, SinkKind::Packed)).extrema == OutExtrema::Fused; }
     DevBuf<float> O;   // output staging (pointer-array / host output)
     DevBuf<float> I;   // image staging (host input)
     // Typed image pixels (fftconv_plan_set_images_typed; pixel_format.hpp).  "pixel_store" 1: the image's forward column kernel
@@ -446,7 +465,7 @@ struct fftconv_plan {
         fr_tw1.release(); fr_tw2.release(); fr_map.release();
         fc_tw1.release(); fc_tw2.release(); fc_pairs.release(); fc_rowoff.release(); fc_pair_row_of.release();
         nat_row_of.release(); nat_col_of.release(); NS.release(); queue.release();
-        ND.release(); KN.release(); KC.release(); NS64.release();
+        ND.release(); KN.release(); KC.release(); NS64.release(); EXR.release(); EXP.release();
         pin_img.release(); pin_k.release(); pin_out.release();
         for (int h = 0; h < 2; h++) { if (pin_out_done[h]) (void)hipEventDestroy(pin_out_done[h]); pin_out_done[h] = nullptr; }
     }
@@ -474,6 +493,8 @@ struct Sink {
     // a plan holding several images: maps between the first maps of two images in `packed` / `ptrs` -- the kernels of the whole
     // call, of which the group may be a part (ragged cells); 0 = the kernels of the group
     int image_stride = 0;
+    // per-map extrema: the call's map index of the group's first map (`ptrs` of a later group of a ragged call starts there)
+    int map0 = 0;
 };
 
 struct BatchSizes {
@@ -517,11 +538,15 @@ struct Delivery {
 struct OutLaunch {
     int image0 = 0, per_image = 1;
     const float* consts = nullptr;
+    int record0 = 0;      // per-map extrema: the record of the launch's first map
 };
 // the route of a group into `sink` and the buffers it names, sized for nbY maps per launch (the ring: started)
 int plan_delivery(fftconv_plan* p, const Sink& sink, int nbY, Delivery& d);
 // output columns of ny maps: Y transformed along h into the maps at obase (win: into the window of an overlap-save block)
 int launch_output_cols(fftconv_plan* p, const OutputRoute& r, const OutWindow* win, float* obase, int ny, const OutLaunch& l);
+// per-map extrema of the ny delivered maps at `dest` (dense, in the route's map format), behind the last kernel that writes them and
+// ahead of any copy-out: the fold of the partials the fused store wrote (r.extrema Fused), or the scan and its fold (Scan)
+int launch_extrema(fftconv_plan* p, const OutputRoute& r, const float* dest, int ny, const OutLaunch& l);
 // r.after: nmaps full fp32 windows at src cropped (padded) into dst and combined with the route's plane on the way
 int launch_region(const fftconv_plan* p, const OutputRoute& r, const float* src, float* dst, int nmaps, hipStream_t s, const OutLaunch& l = {});
 // the maps [first, first + ny) are queued into `dest` (staging buffer buf of a streamed group): their way to the caller
@@ -592,6 +617,14 @@ inline int plan_refused(const fftconv_plan* p, Ask ask, long value = 1) {
     s.score = p->opt_score; s.border = p->border_mode; s.filter = p->opt_filter;
     s.rows_fast = p->g.fast_rows.ok; s.filter_built = fast_rows_filter_built(p->g.Lw); s.Lw = p->g.Lw;
     const Refusal r = plan_refusal(s, ask, value);
+    return r ? api_fail(r.rule->code, r.rule->fmt, r.arg) : 0;
+}
+// ... of the output side's table (per-map extrema); window_sink: the group at hand stores through an output window
+inline int plan_refused(const fftconv_plan* p, AskOutput ask, long value, bool window_sink = false) {
+    PlanRuleState s;
+    s.blocks = p->tiled ? p->tiled->nblk : 0;
+    s.window_sink = window_sink;
+    const OutputRefusal r = plan_refusal(s, ask, value);
     return r ? api_fail(r.rule->code, r.rule->fmt, r.arg) : 0;
 }
 }  // namespace fc

@@ -44,6 +44,8 @@ OutputRouteIn output_route_in(const fftconv_plan* p, SinkKind sink) {
     in.fast_cols = g.fast_cols.ok; in.y_tiled = g.y_tiled();
     in.rect_built = fast_cols_rect_built(g.M); in.norm_built = fast_cols_norm_built(g.M); in.sqdiff_built = fast_cols_sqdiff_built(g.M);
     in.stride_h = p->stride_h; in.stride_w = p->stride_w; in.stride_store = p->opt_stride_store != 0; in.stride_built = fast_cols_stride_built(g.M);
+    in.extrema = p->extrema_on(); in.extrema_store = p->opt_extrema_store != 0;
+    in.extrema_rect_built = fast_cols_rect_ext_built(g.M); in.extrema_norm_built = fast_cols_norm_ext_built(g.M); in.extrema_sqdiff_built = fast_cols_sqdiff_ext_built(g.M);
     return in;
 }
 
@@ -63,6 +65,11 @@ int plan_delivery(fftconv_plan* p, const Sink& sink, int nbY, Delivery& d) {
         if (int rc = p->O.ensure(p->g.map_elems() * nbY)) return rc;
     if (d.stage)
         if (int rc = d.stage->ensure(floats_for(d.oe * nbY * d.r.staging_copies, d.eb))) return rc;
+    if (d.r.extrema == OutExtrema::Fused)
+        FC_VERBOSE(p, "extrema: fused -- found by the output kernel in its store, one partial per tile and wave, folded per launch");
+    else if (d.r.extrema == OutExtrema::Scan)
+        FC_VERBOSE(p, "extrema: scanned -- the %s maps of %zu elements are read where they lie, %d blocks per map, folded per launch", kMapFormatNames[d.r.map_format],
+                   d.oe, extrema_scan_blocks(d.oe * d.eb));
     if (d.r.route == Route::Ring) return ring_begin(p);
     return 0;
 }
@@ -105,7 +112,14 @@ int launch_output_cols(fftconv_plan* p, const OutputRoute& r, const OutWindow* w
     } else {
         static const char* const fused[] = {"", "scaled by D (normalisation: fused)", "scaled by Dc (normalisation: fused CCORR_NORMED)",
                                             "plus Q + c (normalisation: fused SQDIFF)"};      // OutPlane
-        const FastColsShape sh = output_rect_shape(p, r, p->Y.p, obase, ny, l);
+        FastColsShape sh = output_rect_shape(p, r, p->Y.p, obase, ny, l);
+        const bool ext = r.extrema == OutExtrema::Fused;
+        if (ext) {      // (the partials of the launch: sized by fftconv_plan_set_extrema for the whole window's tiles, never here)
+            if (fast_cols_extrema_slots(sh, g.fast_cols.NT) > p->extrema_slots || ny > p->extrema_launch_maps)
+                return api_fail(FFTCONV_ERR_INVALID_ARG, "per-map extrema: the launch needs %d partials per map for %d maps, the plan holds %d for %d",
+                                fast_cols_extrema_slots(sh, g.fast_cols.NT), ny, p->extrema_slots, p->extrema_launch_maps);
+            sh.extrema.partials = p->EXP.p;
+        }
         if (r.store == OutStore::RectStride)
             FC_VERBOSE(p, "output kernel: tiled rectangle, stride (%d, %d) fused in the store (%s), %d workgroups on %d tiles, fp32 elements, rows [%d, %d) of columns [%d, %d) into %d x %d maps",
                        p->stride_h, p->stride_w, sh.a.rect_wide ? "pair stores" : "element stores", sh.grid, sh.a.ntiles, sh.a.h_lo, sh.a.fft_h, sh.a.rect_w_lo,
@@ -115,10 +129,34 @@ int launch_output_cols(fftconv_plan* p, const OutputRoute& r, const OutWindow* w
                        sh.grid, sh.a.h_lo, sh.a.fft_h, sh.a.rect_w_lo, sh.a.rect_w_lo + sh.a.rect_w_n, l.image0);
         else
             FC_VERBOSE(p, "output kernel: tiled rectangle, %d workgroups, %s elements, rows [%d, %d) of columns [%d, %d)", sh.grid, kMapFormatNames[format],
-                       p->off_h, p->off_h + p->out_h, p->off_w, p->off_w + p->out_w);
-        HIP_TRY(launch_fast_cols_rect(g.M, g.fast_cols.T, sh, p->stream));
+                       sh.a.h_lo, sh.a.fft_h, sh.a.rect_w_lo, sh.a.rect_w_lo + sh.a.rect_w_n);
+        if (ext) HIP_TRY(launch_fast_cols_rect_extrema(g.M, g.fast_cols.T, sh, p->stream));
+        else HIP_TRY(launch_fast_cols_rect(g.M, g.fast_cols.T, sh, p->stream));
     }
     return p->prof_end();
+}
+
+// per-map extrema of a launch's delivered maps: the records [l.record0, l.record0 + ny)
+int launch_extrema(fftconv_plan* p, const OutputRoute& r, const float* dest, int ny, const OutLaunch& l) {
+    if (r.extrema == OutExtrema::Off) return 0;
+    const size_t oe = p->out_elems();
+    const int out_h = r.after == OutAfter::Pad ? p->out_h : p->map_h();      // rows per column of a delivered map
+    if (l.record0 < 0 || (long)l.record0 + ny > (long)p->extrema_max_maps || ny > p->extrema_launch_maps)
+        return api_fail(FFTCONV_ERR_INVALID_ARG, "per-map extrema: records %d..%d in a launch of %d maps asked of a plan that holds %d records and the partials of %d maps "
+                        "(fftconv_plan_set_extrema sizes them for the \"batch_maps\" of its time)", l.record0, l.record0 + ny - 1, ny, p->extrema_max_maps, p->extrema_launch_maps);
+    int per_map;
+    if (r.extrema == OutExtrema::Fused) {
+        // (what launch_output_cols launched and checked: the tiles that hold a column of the extent x the waves of a workgroup)
+        const FastColsShape sh = output_rect_shape(p, r, p->Y.p, const_cast<float*>(dest), ny, l);
+        per_map = fast_cols_extrema_slots(sh, p->g.fast_cols.NT);
+    } else {
+        per_map = extrema_scan_blocks(oe * fc_map_elem_bytes(r.map_format));
+        if (per_map > p->extrema_slots)
+            return api_fail(FFTCONV_ERR_INVALID_ARG, "per-map extrema: the scan needs %d partials per map, the plan holds %d", per_map, p->extrema_slots);
+        HIP_TRY(launch_extrema_scan(dest, oe, oe, r.map_format, ny, p->EXP.p, p->stream));
+    }
+    HIP_TRY(launch_extrema_fold(p->EXP.p, per_map, ny, out_h, p->EXR.p + l.record0, p->stream));
+    return 0;
 }
 
 // what follows the output kernel on a route with a crop: nmaps full fp32 windows at src compacted into dst -- cropped, or padded to

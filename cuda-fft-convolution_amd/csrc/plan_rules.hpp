@@ -43,7 +43,7 @@ constexpr const SetterEffects& setter_effects(Setter s) { return kSetterEffects[
 
 // ---- exclusions: "asking X is refused while Y holds" ----
 enum class Ask { Score, Border, Filter, ImportSpectrum, MarkSpectrumValid };
-enum class Holds { Blockwise, ScoreOn, ScorePlane, BorderOn, FilterOn, Features, NoFilterKernel };
+enum class Holds { Blockwise, ScoreOn, ScorePlane, BorderOn, FilterOn, Features, NoFilterKernel, WindowSink };
 
 // the state the rules read
 struct PlanRuleState {
@@ -53,6 +53,7 @@ struct PlanRuleState {
     bool rows_fast = false;     // the spectral rows run a specialised kernel ...
     bool filter_built = false;  // ... whose FILTER form exists (fast_paths.hpp: fast_rows_filter_built)
     int Lw = 0;                 // the row length
+    bool window_sink = false;   // the group at hand stores through an output window (the block plan of an overlap-save plan)
 };
 
 // 0 while Y does not hold, else the integer the rule's message names (block count, score, mode, feature_dim, row length)
@@ -65,6 +66,7 @@ inline long holds_value(const PlanRuleState& s, Holds y) {
     case Holds::FilterOn: return s.filter;
     case Holds::Features: return s.F > 1 ? s.F : 0;
     case Holds::NoFilterKernel: return s.rows_fast && !s.filter_built ? s.Lw : 0;
+    case Holds::WindowSink: return s.window_sink ? 1 : 0;
     }
     return 0;
 }
@@ -110,6 +112,42 @@ constexpr PlanRule kPlanRules[] = {
      "a border is on (fftconv_plan_set_border, mode %ld): a spectrum written by the caller carries no border"},
 };
 
+// ---- the output side: per-map extrema (fftconv_plan_set_extrema) ----
+// Tables of their own beside the two above, with the same row types and the same lookups: tests/plan_rules_host holds kSetterEffects and
+// kPlanRules row for row against the entry points they replaced (every row counted, every request of `Ask` walked), so the rows of an
+// entry point that commit did not have are listed here, and setter_effects / plan_refusal answer from both.
+//   effects   output-side state of its own, as the stride is: it keeps the image, the prepared kernels and the stream, stays while extent,
+//             format, score or images change, and a call that changes nothing returns early.  FX_WAIT: launches in flight write the
+//             records and the partials the call reallocates.
+//   refusals  switching it ON on a block-wise plan, whose maps are stored through output windows block by block; a group under
+//             extrema whose sink is such a window.
+enum class SetterAdded { Extrema };
+struct AddedSetterEffects {
+    SetterAdded setter;
+    unsigned changed;
+    bool unchanged_returns;
+};
+constexpr AddedSetterEffects kSetterEffectsAdded[] = {
+    {SetterAdded::Extrema, FX_WAIT, true},      // fftconv_plan_set_extrema
+};
+constexpr const AddedSetterEffects& setter_effects(SetterAdded s) { return kSetterEffectsAdded[(int)s]; }
+
+enum class AskOutput { Extrema, ExtremaGroup };
+struct OutputRule {
+    AskOutput ask;
+    Holds holds;
+    bool off_too;
+    int code;
+    const char* fmt;
+};
+constexpr OutputRule kOutputRules[] = {
+    {AskOutput::Extrema, Holds::Blockwise, false, FFTCONV_ERR_INVALID_ARG,
+     "per-map extrema are not available on a block-wise plan (%ld blocks: its maps are stored through output windows block by block); create a "
+     "one-pass plan (fftconv_plan_options.blockwise = 1)"},
+    {AskOutput::ExtremaGroup, Holds::WindowSink, true, FFTCONV_ERR_INVALID_ARG,
+     "per-map extrema are on (fftconv_plan_set_extrema): an output window holds a part of a map (%ld), not a delivered map"},
+};
+
 struct Refusal {
     const PlanRule* rule = nullptr;      // nullptr: the request passes
     long arg = 0;                        // what rule->fmt formats
@@ -118,6 +156,18 @@ struct Refusal {
 // the first rule that refuses asking `ask` for `value` (the score, the border mode, the filter mode; the spectrum entries: any)
 inline Refusal plan_refusal(const PlanRuleState& s, Ask ask, long value) {
     for (const PlanRule& r : kPlanRules) {
+        if (r.ask != ask || (value == 0 && !r.off_too)) continue;
+        if (const long arg = holds_value(s, r.holds)) return {&r, arg};
+    }
+    return {};
+}
+struct OutputRefusal {
+    const OutputRule* rule = nullptr;
+    long arg = 0;
+    explicit operator bool() const { return rule != nullptr; }
+};
+inline OutputRefusal plan_refusal(const PlanRuleState& s, AskOutput ask, long value) {
+    for (const OutputRule& r : kOutputRules) {
         if (r.ask != ask || (value == 0 && !r.off_too)) continue;
         if (const long arg = holds_value(s, r.holds)) return {&r, arg};
     }

@@ -499,6 +499,41 @@ int fftconv_plan_set_output_rect(fftconv_plan *plan, int off_h, int off_w, int o
  * of the dense maps sliced; read-only option "stride_direct" tells which.  The one-shot, two-step, fftconv_multi_*, plan-cache and
  * MEX entries do not take strides. */
 int fftconv_plan_set_output_stride(fftconv_plan *plan, int stride_h, int stride_w);
+/* Per-map extrema: the largest and the smallest element of every delivered map and where they lie, found on the device while the
+ * maps are written -- what a caller of a matching score does with a map (the largest CCOEFF_NORMED / CCORR_NORMED / phase-correlation
+ * value, the smallest SQDIFF) without reading the maps again.  The maps themselves are written exactly as without this entry.
+ *   What a record covers.  After a convolve of B * n_kernel maps (image-major, as the maps are) record m describes delivered map m --
+ *     the map as the caller receives it: the window, an "output_region" 1-4 (4: the padded map), a rectangle, a strided map, a
+ *     border's "same" map.  The values come from the delivered element; for 16-bit maps that is the exact fp32 value of the rounded
+ *     element.  `row` is the fast index and `col` the slow one of the delivered map: the element lies at col * out_h + row.
+ *   Ties.  The element with the smallest col * out_h + row wins, for max and for min independently; +0 and -0 compare equal, and the
+ *     value reported is that element's bits.
+ *   NaN.  A NaN never wins (the compares are ordered); a map without an element that compares reports NaN and row = col = -1.
+ *   No atomics.  The records are a pure function of the maps: two runs, both routes (below) and both tile deals ("dynamic_tiles")
+ *     give identical records.
+ *   Allocation.  fftconv_plan_set_extrema(plan, 1, max_maps) sizes the record buffer and every scratch the launches need, for
+ *     convolves of up to max_maps maps; a convolve of more maps is refused with FFTCONV_ERR_INVALID_ARG and leaves the plan usable.  A
+ *     convolve under extrema allocates nothing for them and does not wait for the host: it can be captured into a graph.
+ *   Reading.  fftconv_plan_get_extrema waits for the plan's stream and copies the records [first_map, first_map + n_maps) of the
+ *     last convolve to out_host; before any convolve under extrema, and for a range beyond the maps of the last one, it fails with
+ *     FFTCONV_ERR_INVALID_ARG.  fftconv_plan_extrema_device gives the device array of max_maps records and its size: the pointer is
+ *     stable until the next fftconv_plan_set_extrema or fftconv_plan_destroy, its content is ordered on the plan's stream.
+ *   State.  Output-side state of its own, as the stride is: it keeps the image, the prepared kernels and the stream, and it stays
+ *     while extent, format, score or images change; a call that changes nothing returns early, a change synchronises the plan's
+ *     stream.  mode 0 switches it off and frees the buffers.
+ *   Refusals (FFTCONV_ERR_INVALID_ARG, the plan's state untouched): a mode other than 0 / 1, max_maps < 1 with mode 1; mode 1 on a
+ *     block-wise plan, whose maps are stored through output windows block by block.
+ * Routes: on a one-pass plan with the specialised output kernel and the tiled intermediate, fp32 maps of the window or of a
+ * rectangle, no stride -- raw maps and every score -- the output kernel finds the extrema in its store, while it holds the values in
+ * registers (read-only option "extrema_direct" 1).  Everything else -- 16-bit maps, "output_region" 1-4, strides, generic / Bluestein
+ * output kernels, kernel_path 1 or 2, the configurations whose kernel is not built, option "extrema_store" 0 -- is
+ * SCANNED: a small kernel reads the delivered maps once more where they lie on the device, before any copy-out (4P' bytes per map
+ * of P' elements).  Options: "extrema_store" (1 (default): fused where the plan can; 0: always the scan), read-only "extrema" (the
+ * mode), "extrema_direct", "extrema_max_maps", "extrema_maps" (the maps of the last convolve under it; -1 before any).  The one-shot, two-step, fftconv_multi_*, plan-cache and MEX entries do not take it. */
+typedef struct { float max_value; int max_row, max_col; float min_value; int min_row, min_col; } fftconv_extrema;
+int fftconv_plan_set_extrema(fftconv_plan *plan, int mode, int max_maps);   /* mode 0 off, 1 on */
+int fftconv_plan_get_extrema(fftconv_plan *plan, int first_map, int n_maps, fftconv_extrema *out_host);
+int fftconv_plan_extrema_device(fftconv_plan *plan, void **device_ptr, size_t *bytes);
 /* Normalised cross-correlation maps.  mode 0 (default): the maps are the raw sums of products, bit for bit what they are
  * without this entry.  mode 1: every map is the zero-mean normalised cross-correlation (MATLAB's normxcorr2, OpenCV's
  * TM_CCOEFF_NORMED) over the box box_h x box_w, n = box_h * box_w: in [-1, 1], 1 at a perfect match, invariant to gain and
