@@ -57,6 +57,20 @@ struct RowMultiState {
 // the condition.  The argument itself is still to be deleted, together with the visitor and the argument of the two kernels.
 // FILTER (F = 1; k_fast_rows_filter, fftconv_plan_set_spectral_filter): the product of P3 is the pointwise function of
 // spectral_filter.hpp that g.filter_mode names -- one instantiation per configuration for all modes, everything else as it is.
+
+// Issue priority by phase (F = 1, no filter; FC_ROWS_PRIO, fc_common.hpp).  The SIMD's arbiter takes the oldest ready wave first, so
+// of the workgroups resident on a CU the old ones run ahead and the young ones wait, whatever phase they are in.  A wave in P3
+// (butterflies of 22 points and the product: arithmetic for every free slot) that wins against a wave in a stage-2 phase
+// leaves the LDS pipe idle.  FC_ROWS_PRIO_POLICY:
+//   0  every phase at the default priority (the kernels before this switch, instruction for instruction)
+//   1  the phases that feed the LDS and the memory pipes -- the prefetch and P2, P4, P5 -- at priority 1, P3 at 0: two s_setprio
+//      per map.  19.46 -> 18.27 us per map at 4224, 5.02 -> 4.78 at 2112 (medians of five alternating legs a side, spreads 0.15
+//      and 0.34; profiles/rows_issue_slots_ab.txt).
+// (P5 alone at priority 1 measured 19.22 at 4224 and is gone)
+#ifndef FC_ROWS_PRIO_POLICY
+#define FC_ROWS_PRIO_POLICY 1
+#endif
+
 template <class C, int NZ2, bool LINEAR, bool MULTIF = false, bool FILTER = false, class Ctx>
 FC_HD void fast_rows_multi_body(Ctx& ctx, c32* lds, const FastRowsArgs& g, int group, int kernel0, int nk, int rows) {
     static_assert(LINEAR, "the row kernel has one form of its last phase");
@@ -68,6 +82,7 @@ FC_HD void fast_rows_multi_body(Ctx& ctx, c32* lds, const FastRowsArgs& g, int g
     const int kw = g.kw;
     const int row0 = group * RPW;
     const bool tiled = g.y_row_of != nullptr;
+    constexpr int PRIO = (MULTIF || FILTER) ? 0 : FC_ROWS_PRIO_POLICY;
 
     // st.x is zeroed once (below) and only the lanes that hold a kernel element ever load into it: no zero is materialised per map
     auto load_x = [&](int t, State& st, int kernel, int f) {
@@ -186,6 +201,7 @@ FC_HD void fast_rows_multi_body(Ctx& ctx, c32* lds, const FastRowsArgs& g, int g
             });
         });
 
+        if constexpr (PRIO == 1) FC_ROWS_PRIO(1);
         // the next kernel row (next feature of this map, or the next map's first) flies during P2..P5
         if (f + 1 < nF) ctx.phase_nosync([&](int t, State& st) { load_x(t, st, kernel, f + 1); });
         else if (m + 1 < nk) ctx.phase_nosync([&](int t, State& st) { load_x(t, st, kernel + 1, 0); });
@@ -215,6 +231,7 @@ FC_HD void fast_rows_multi_body(Ctx& ctx, c32* lds, const FastRowsArgs& g, int g
         FC_ROWS_STAMP(2);
         // P3: forward stage 3, product with the image spectrum (registers), inverse stage 3
         const bool last_f = (f == nF - 1);
+        if constexpr (PRIO == 1) FC_ROWS_PRIO(0);
         ctx.phase([&](int t_, State& st) {
             int t = t_;
             if constexpr (MULTIF) FC_OPAQUE(t);
@@ -296,6 +313,7 @@ FC_HD void fast_rows_multi_body(Ctx& ctx, c32* lds, const FastRowsArgs& g, int g
 
         FC_ROWS_STAMP(3);
         // P4: inverse stage 2
+        if constexpr (PRIO == 1) FC_ROWS_PRIO(1);
         ctx.phase([&](int t, State&) {
             static_for<0, C::RND2>([&](auto r_) {
                 constexpr int r = decltype(r_)::value;

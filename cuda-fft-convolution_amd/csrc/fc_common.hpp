@@ -100,6 +100,15 @@
 #define FC_WAIT_VMEM() ((void)0)
 #endif
 
+// Issue priority of this wave from here on (s_setprio n, n = 0 ... 3; a wave starts at 0).  Among the waves of a SIMD that are
+// ready the arbiter takes the highest priority first and the oldest among equals, so a wave in a phase that feeds the LDS or
+// the memory pipe can be put ahead of one that has arithmetic to spare.  Nothing on the host and in the emulator.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define FC_ROWS_PRIO(n) __builtin_amdgcn_s_setprio(n)
+#else
+#define FC_ROWS_PRIO(n) ((void)0)
+#endif
+
 // Dynamic tile queue of the persistent column kernels (fast_cols.hpp: TileQueue): one returning agent-scope add on a
 // counter word, a relaxed agent-scope load of one, and the XCD a workgroup runs on (HW_REG_XCC_ID bits 3:0 -- read, not
 // inferred from the block index: with another kernel co-resident the round-robin placement is not what it is alone).  On the

@@ -8,7 +8,8 @@ One iteration is walked from the header to the back edge and a new segment start
 the compiler laid out behind the back edge (cold paths such as the first map's P1) are summed in the column "cold".  The count
 is static: both sides of a branch inside a phase are counted (the cropped and the uncropped store burst of P5, for instance),
 so a column is an upper bound of what one iteration issues.  --arith prints, instead, the multiset of fp32 arithmetic instructions (opcode + modifiers, registers
-dropped) of every matching kernel: equal multisets in two builds = the same floating-point work."""
+dropped) of every matching kernel: equal multisets in two builds = the same floating-point work.  --nops prints, instead, every
+s_nop of the loop by segment and by the pair of instructions around it (nop_pairs)."""
 import collections, re, sys
 
 CLASSES = ["pk_arith", "fp_other", "v_mov", "v_int", "v_cmp", "v_lane", "v_other", "lds", "global", "salu", "s_waitcnt", "s_nop", "s_barrier", "branch"]
@@ -88,6 +89,67 @@ def phases(body):
     return head, cols, cold
 
 
+def regs(operand):
+    """the set of registers an operand names: v7 -> {('v', 7)}, s[4:7] -> {('s', 4) ... ('s', 7)}, vcc -> {('vcc', 0)}"""
+    out = set()
+    for kind, lo, hi, one in re.findall(r"\b(?:([vsa])\[(\d+):(\d+)\]|([vsa]\d+))", operand):
+        if one: out.add((one[0], int(one[1:])))
+        else: out.update((kind, i) for i in range(int(lo), int(hi) + 1))
+    for name in ("vcc", "exec", "m0", "scc"):
+        if re.search(r"\b%s(_lo|_hi)?\b" % name, operand): out.add((name, 0))
+    return out
+
+
+def nop_pairs(body):
+    """Counter of (segment, wait states, instruction ahead, instruction behind, what links them) over the s_nop of one iteration
+    of the loop (and of its cold blocks, segment 'cold').  The instruction ahead is the nearest one that is no s_nop, the one
+    behind the first after the run of s_nop; the wait states of a run are summed (s_nop n stalls n + 1 cycles).  The link is
+    what the pair shares: 'dst->src' a register the first writes (its first operand) and the second reads, 'dst->dst' one
+    both write, '-' nothing (the hazard then lies further back than one instruction, or is one of a kind of instructions)."""
+    bl = blocks(body)
+    size = collections.Counter()
+    for label, hdr, ins in bl:
+        size[label if hdr == "self" else hdr] += len(ins)
+    size.pop(None, None)
+    out = collections.Counter()
+    if not size: return out
+    head = max(size, key=size.get)
+    member = [(label, ins) for label, hdr, ins in bl if (hdr == "self" and label == head) or hdr == head]
+    at = [m[0] for m in member].index(head)
+    latch, chain = member[:at], member[at:]
+    back = {m[0] for m in latch} | {head}
+    end = next((i for i, (label, ins) in enumerate(chain) if ins and re.match(r"s_branch\s+(\S+)", ins[-1]) and ins[-1].split()[1] in back),
+               len(chain) - 1)
+
+    def walk(seq, seg0, count_barriers):
+        seg, prev, wait = seg0, None, 0
+        for s in seq:
+            op = s.split()[0]
+            if op == "s_nop":
+                wait += int(s.split()[1]) + 1
+                continue
+            if wait:
+                link = "-"
+                if prev:
+                    pa, na = (x.split(None, 1)[1] if " " in x else "" for x in (prev, s))
+                    po, no = (re.split(r",(?![^\[]*\])", x) for x in (pa, na))
+                    stores = lambda o: o.split()[0].startswith(("global_store", "ds_write", "ds_store", "buffer_store", "scratch_store", "flat_store"))
+                    pd = set() if stores(prev) else regs(po[0])
+                    ns = regs(na) if stores(s) else regs(",".join(no[1:]))
+                    nd = set() if stores(s) else regs(no[0])
+                    link = "dst->src" if pd & ns else "dst->dst" if pd & nd else "-"
+                out[(seg, wait, prev.split()[0] if prev else "(block start)", op, link)] += 1
+                wait = 0
+            prev = s
+            if count_barriers and op == "s_barrier": seg += 1
+        return seg
+
+    walk([s for label, ins in chain[:end + 1] + latch for s in ins], 0, True)
+    for label, ins in chain[end + 1:]:
+        walk(ins, "cold", False)
+    return out
+
+
 def arith_multiset(body):
     c = collections.Counter()
     for label, hdr, ins in blocks(body):
@@ -108,6 +170,14 @@ def main():
             ms = arith_multiset(body)
             print(name[:160], " fp arithmetic instructions:", sum(ms.values()))
             for k, v in sorted(ms.items()): print("    %5d  %s %s %s" % (v, k[0], k[1], k[2]))
+            continue
+        if "--nops" in sys.argv:
+            pairs = nop_pairs(body)
+            print(name[:160])
+            print("  s_nop of the loop by the instructions around them: %d runs, %d wait states" % (sum(pairs.values()), sum(k[1] * v for k, v in pairs.items())))
+            print("  %-5s %5s %6s  %-26s %-26s %s" % ("seg", "runs", "states", "ahead", "behind", "link"))
+            for (seg, wait, a, b, link), v in sorted(pairs.items(), key=lambda kv: (str(kv[0][0]), -kv[1] * kv[0][1], kv[0][2:])):
+                print("  %-5s %5d %6d  %-26s %-26s %s" % (seg if seg == "cold" else "seg%d" % seg, v, v * wait, a, b, link))
             continue
         head, cols, outl = phases(body)
         print(name[:160])
