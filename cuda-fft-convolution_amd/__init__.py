@@ -86,6 +86,8 @@ _PIXEL_OF_DTYPE = {np.dtype(np.uint8): PIXEL_U8, np.dtype(np.uint16): PIXEL_U16,
 SCORE_NONE, SCORE_CCOEFF_NORMED, SCORE_CCOEFF, SCORE_CCORR_NORMED, SCORE_SQDIFF = 0, 1, 2, 3, 4
 # spectral filters (Plan.set_spectral_filter; FFTCONV_FILTER_* of include/fftconv.h)
 FILTER_PRODUCT, FILTER_PHASE, FILTER_WIENER = 0, 1, 2
+# fftconv_plan_set_peaks modes
+PEAKS_OFF, PEAKS_MAX, PEAKS_MIN = 0, 1, 2
 BORDER_ZERO, BORDER_CONSTANT, BORDER_REPLICATE, BORDER_SYMMETRIC, BORDER_REFLECT101, BORDER_CIRCULAR = 0, 1, 2, 3, 4, 5
 
 
@@ -129,6 +131,8 @@ class Profile(ctypes.Structure):
 
 # fftconv_extrema (include/fftconv.h): one record of Plan.extrema()
 EXTREMA_DTYPE = [("max_value", "<f4"), ("max_row", "<i4"), ("max_col", "<i4"), ("min_value", "<f4"), ("min_row", "<i4"), ("min_col", "<i4")]
+# fftconv_peak (include/fftconv.h): one record of Plan.peaks()
+PEAK_DTYPE = [("value", "<f4"), ("row", "<i4"), ("col", "<i4"), ("d_row", "<f4"), ("d_col", "<f4")]
 
 # every symbol include/fftconv.h declares
 EXPORTED_SYMBOLS = (
@@ -141,7 +145,7 @@ EXPORTED_SYMBOLS = (
     "fftconv_plan_use_spectrum_buffer", "fftconv_plan_export_spectrum", "fftconv_plan_import_spectrum",
     "fftconv_plan_convolve", "fftconv_plan_convolve_packed", "fftconv_plan_prepare_kernels_packed",
     "fftconv_plan_synchronize", "fftconv_plan_set_stream",
-    "fftconv_plan_set_option", "fftconv_plan_set_output_rect", "fftconv_plan_set_output_stride", "fftconv_plan_set_extrema", "fftconv_plan_get_extrema", "fftconv_plan_extrema_device", "fftconv_plan_set_normalisation", "fftconv_plan_set_match_score", "fftconv_plan_set_border", "fftconv_plan_set_spectral_filter", "fftconv_plan_get_option", "fftconv_plan_get_profile",
+    "fftconv_plan_set_option", "fftconv_plan_set_output_rect", "fftconv_plan_set_output_stride", "fftconv_plan_set_extrema", "fftconv_plan_get_extrema", "fftconv_plan_extrema_device", "fftconv_plan_set_peaks", "fftconv_plan_get_peaks", "fftconv_plan_peaks_device", "fftconv_plan_set_normalisation", "fftconv_plan_set_match_score", "fftconv_plan_set_border", "fftconv_plan_set_spectral_filter", "fftconv_plan_get_option", "fftconv_plan_get_profile",
     "fftconv_fft_data", "fftconv_conv_fft_data",
     "fftconv_multi_create", "fftconv_multi_destroy", "fftconv_multi_set_image", "fftconv_multi_import_spectrum",
     "fftconv_multi_convolve", "fftconv_multi_set_option", "fftconv_multi_get_option",
@@ -220,6 +224,9 @@ def load_library():
     lib.fftconv_plan_set_extrema.argtypes = [vp, ci, ci]
     lib.fftconv_plan_get_extrema.argtypes = [vp, ci, ci, vp]
     lib.fftconv_plan_extrema_device.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(cs)]
+    lib.fftconv_plan_set_peaks.argtypes = [vp, ci, ci, ci, ctypes.c_float, ci, ci]
+    lib.fftconv_plan_get_peaks.argtypes = [vp, ci, ci, vp, vp]
+    lib.fftconv_plan_peaks_device.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(cs)]
     lib.fftconv_plan_set_normalisation.argtypes = [vp, ci, ci, ci]
     lib.fftconv_plan_set_match_score.argtypes = [vp, ci, ci, ci]
     lib.fftconv_plan_set_border.argtypes = [vp, ci, ctypes.c_float]
@@ -629,6 +636,50 @@ class Plan:
         ptr, nbytes = ctypes.c_void_p(), ctypes.c_size_t(0)
         _check(self._lib.fftconv_plan_extrema_device(self._h, ctypes.byref(ptr), ctypes.byref(nbytes)))
         return int(ptr.value or 0), int(nbytes.value)
+
+    def set_peaks(self, mode, max_maps=0, max_peaks=0, threshold=0.0, radius=(0, 0)):
+        """peak lists (fftconv_plan_set_peaks): while on (PEAKS_MAX: maxima at or above threshold; PEAKS_MIN: minima at or below
+        it), every convolve of up to max_maps maps also leaves, per delivered map, the number of its peaks and the first max_peaks
+        of them in memory order on the device -- the elements that meet the threshold and that no other element within
+        radius = (rows, columns) beats, with a sub-pixel offset per dimension; the maps themselves are unchanged.  Read them with
+        peaks() or peaks_device().  A change of threshold, radius or mode alone keeps the buffers.  PEAKS_OFF frees them.  Read-only
+        options "peaks", "peaks_max_maps", "peaks_max", "peaks_radius_h", "peaks_radius_w", "peaks_maps"."""
+        rh, rw = radius
+        _check(self._lib.fftconv_plan_set_peaks(self._h, int(mode), int(max_maps), int(max_peaks), float(threshold), int(rh), int(rw)))
+        _check(self._lib.fftconv_plan_get_info(self._h, ctypes.byref(self.info)))
+
+    def peaks(self, first=0, n=None, order="memory"):
+        """(found, lists) of the maps [first, first + n) of the last convolve under set_peaks (n None: up to its last map): found an
+        int32 array -- the peaks of each map, all of them -- and lists one structured array of PEAK_DTYPE per map (value, row, col,
+        d_row, d_col; the peak lies at (row + d_row, col + d_col), row the fast index), trimmed to min(found, max_peaks).
+        order "memory": ascending col * out_h + row, as the device leaves them; "strength": sorted here on the host by value
+        (descending for PEAKS_MAX, ascending for PEAKS_MIN), ties by ascending index.  Waits for the plan's stream."""
+        import numpy as np
+        if order not in ("memory", "strength"):
+            raise ValueError("order is \"memory\" or \"strength\", not %r" % (order,))
+        if n is None:      # ("peaks_maps": the maps of the last convolve under it; -1 before any -- the library then refuses the read)
+            n = max(self.get_option("peaks_maps"), 0) - int(first)
+        n, cap = max(int(n), 0), max(self.get_option("peaks_max"), 0)
+        found = np.zeros(n, dtype=np.int32)
+        recs = np.zeros((n, cap), dtype=PEAK_DTYPE)
+        # (zero maps asked: the arrays are empty, but the pointers the library checks must not be NULL)
+        fbuf, rbuf = (found, recs) if n and cap else (np.zeros(1, dtype=np.int32), np.zeros(1, dtype=PEAK_DTYPE))
+        _check(self._lib.fftconv_plan_get_peaks(self._h, int(first), n, fbuf.ctypes.data_as(ctypes.c_void_p), rbuf.ctypes.data_as(ctypes.c_void_p)))
+        lists = [recs[m, :min(int(found[m]), cap)].copy() for m in range(n)]
+        if order == "strength":
+            out_h, minima = int(self.info.out_h), self.get_option("peaks") == PEAKS_MIN
+            for m, l in enumerate(lists):
+                index = l["col"].astype(np.int64) * out_h + l["row"]
+                lists[m] = l[np.lexsort((index, l["value"] if minima else -l["value"]))]
+        return found, lists
+
+    def peaks_device(self):
+        """(found pointer, records pointer, bytes of the records) of the plan's device arrays: max_maps int32 counts, and max_maps x
+        max_peaks records of PEAK_DTYPE; stable until a set_peaks that changes max_maps or max_peaks or switches the lists off, their
+        content ordered on the plan's stream"""
+        found, recs, nbytes = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t(0)
+        _check(self._lib.fftconv_plan_peaks_device(self._h, ctypes.byref(found), ctypes.byref(recs), ctypes.byref(nbytes)))
+        return int(found.value or 0), int(recs.value or 0), int(nbytes.value)
 
     def set_normalisation(self, mode, box_h=0, box_w=0):
         """mode 1: every map becomes the zero-mean normalised cross-correlation over the box box_h x box_w -- the size every

@@ -231,6 +231,12 @@ int run_group_impl(fftconv_plan* p, int n, const float* dk, int kh, int kw, cons
             return api_fail(FFTCONV_ERR_INVALID_ARG, "per-map extrema: a launch of %d maps, the partials were sized for %d (call fftconv_plan_set_extrema after \"batch_maps\")",
                             nbY, p->extrema_launch_maps);
     }
+    if (p->peaks_on()) {        // (likewise)
+        if (int rc = plan_refused(p, AskPeaks::PeaksGroup, 1, sink.window != nullptr)) return rc;
+        if (nbY > p->peaks_launch_maps)
+            return api_fail(FFTCONV_ERR_INVALID_ARG, "peak lists: a launch of %d maps, the scratch was sized for %d (call fftconv_plan_set_peaks after \"batch_maps\")", nbY,
+                            p->peaks_launch_maps);
+    }
     FC_VERBOSE(p, "Kernel size: h=%d, w=%d", kh, kw);                 // src/cudaConvolutionFFT.cu:240
     FC_VERBOSE(p, "N Kernel: %d (maps per launch %d, kernels per column-spectrum chunk %d, %s)", n, nbY, nbA,
                (sink.packed || sink.window) ? "packed device output" : sink.location == FFTCONV_HOST ? "host output" : "device output");   // :68
@@ -274,6 +280,7 @@ int run_group_impl(fftconv_plan* p, int n, const float* dk, int kh, int kw, cons
             if (d.r.after != OutAfter::None)
                 if (int rc = launch_region(p, d.r, p->O.p, dest, ny, p->stream, ol)) return rc;
             if (int rc = launch_extrema(p, d.r, dest, ny, ol)) return rc;      // (behind the last kernel that writes the maps, ahead of their copy-out)
+            if (int rc = launch_peaks_scan(p, d.r, dest, ny, ol)) return rc;
             if (int rc = deliver_batch(p, d, sink, first, ny, buf, dest)) return rc;
         }
     }
@@ -368,6 +375,13 @@ const ComputedOption kComputedOptions[] = {
     {"extrema_max_maps", [](const fftconv_plan* p) { return (long)p->extrema_max_maps; }, true},
     {"extrema_maps", [](const fftconv_plan* p) { return (long)p->extrema_maps; }, true},      // the maps of the last convolve under it (-1: none yet)
     {"extrema_direct", [](const fftconv_plan* p) { return (long)p->extrema_direct(); }, true},
+    // peak lists (fftconv_plan_set_peaks): the mode, what the lists were sized for, the radii, the maps of the last convolve under it (-1: none yet)
+    {"peaks", [](const fftconv_plan* p) { return (long)p->peaks_mode; }, true},
+    {"peaks_max_maps", [](const fftconv_plan* p) { return (long)p->peaks_max_maps; }, true},
+    {"peaks_max", [](const fftconv_plan* p) { return (long)p->peaks_max; }, true},
+    {"peaks_radius_h", [](const fftconv_plan* p) { return (long)p->peaks_radius_h; }, true},
+    {"peaks_radius_w", [](const fftconv_plan* p) { return (long)p->peaks_radius_w; }, true},
+    {"peaks_maps", [](const fftconv_plan* p) { return (long)p->peaks_maps; }, true},
     // 1 if, with the plan's current settings, the output kernel itself scales normalised maps (else the staged crop does)
     {"normalise", [](const fftconv_plan* p) { return (long)(p->opt_score == FC_SCORE_CCOEFF_NORMED); }, true},      // (mode 1 is score 1)
     {"norm_direct", [](const fftconv_plan* p) { return (long)p->norm_direct(); }, true},
@@ -621,6 +635,24 @@ static int extrema_begin(fftconv_plan* p, int n_kernel) {
 static void extrema_end(fftconv_plan* p, int n_kernel) {
     if (p->extrema_on()) p->extrema_maps = n_kernel * p->images_held();
 }
+// the same around the peak lists; both may be on, and either refusal comes ahead of either's bookkeeping
+static int peaks_check(fftconv_plan* p, int n_kernel) {
+    if (!p->peaks_on()) return 0;
+    const long maps = (long)n_kernel * p->images_held();
+    if (maps > p->peaks_max_maps)
+        return api_fail(FFTCONV_ERR_INVALID_ARG, "peak lists: a convolve of %ld maps on a plan whose lists hold %d (fftconv_plan_set_peaks: max_maps)", maps, p->peaks_max_maps);
+    return 0;
+}
+static int outputs_begin(fftconv_plan* p, int n_kernel) {
+    if (int rc = peaks_check(p, n_kernel)) return rc;
+    if (int rc = extrema_begin(p, n_kernel)) return rc;
+    if (p->peaks_on()) p->peaks_maps = -1;      // (a call that fails half-way leaves no lists to read)
+    return 0;
+}
+static void outputs_end(fftconv_plan* p, int n_kernel) {
+    extrema_end(p, n_kernel);
+    if (p->peaks_on()) p->peaks_maps = n_kernel * p->images_held();
+}
 
 extern "C" {
 
@@ -659,7 +691,8 @@ int fftconv_plan_get_info(const fftconv_plan* plan, fftconv_plan_info* info) {
     info->out_map_bytes = plan->out_map_bytes();
     info->workspace_bytes = plan->A.bytes() + plan->Y.bytes() + plan->K.bytes() + plan->O.bytes() + plan->I.bytes() + plan->IT.bytes() + plan->IE.bytes() +
                             plan->ND.bytes() + plan->KN.bytes() + plan->KC.bytes() + plan->NS64.bytes() +      // (matching scores: all 0 until one is on)
-                            plan->EXR.bytes() + plan->EXP.bytes();                                             // (per-map extrema: likewise)
+                            plan->EXR.bytes() + plan->EXP.bytes() +                                            // (per-map extrema: likewise)
+                            plan->PKF.bytes() + plan->PKS.bytes() + plan->PKR.bytes();                         // (peak lists: likewise)
     if (const TiledState* ts = plan->tiled) {     // block-wise: the window of the whole image; the spectrum is every block's
         info->spectrum_bytes = ts->spec_total() * sizeof(c32);
         info->map_bytes = ts->big_map() * sizeof(float);
@@ -686,11 +719,11 @@ int fftconv_plan_convolve_packed(fftconv_plan* plan, int n_kernel, const float* 
         if (rc) (void)keep_error([&] { return hipStreamSynchronize(plan->tiled->sub->stream); });
         return rc;
     }
-    if (int rc = extrema_begin(plan, n_kernel)) return rc;
+    if (int rc = outputs_begin(plan, n_kernel)) return rc;
     Sink sink;
     sink.packed = out_device;
     const int rc = run_group(plan, n_kernel, kernels_device, kernel_h, kernel_w, sink);
-    if (!rc) extrema_end(plan, n_kernel);
+    if (!rc) outputs_end(plan, n_kernel);
     return rc;
 }
 
@@ -726,7 +759,7 @@ int fftconv_plan_convolve(fftconv_plan* plan, int n_kernel, const float* const* 
     // (a plan holding B images: out[] has B * n_kernel entries, image-major -- out[b * n_kernel + k] is image b (x) kernel k)
     for (long m = n_kernel; m < (long)n_kernel * p->images_held(); m++)
         if (!out[m]) return api_fail(FFTCONV_ERR_INVALID_ARG, "output %ld is NULL (the plan holds %d images: %ld maps)", m, p->n_images, (long)n_kernel * p->n_images);
-    if (int rc = extrema_begin(p, n_kernel)) return rc;
+    if (int rc = outputs_begin(p, n_kernel)) return rc;
     // groups of consecutive kernels of equal size
     for (int k0 = 0, k1; k0 < n_kernel; k0 = k1) {
         k1 = same_size_run_end(kernel_h, kernel_w, k0, n_kernel);
@@ -761,7 +794,7 @@ int fftconv_plan_convolve(fftconv_plan* plan, int n_kernel, const float* const* 
         if (rcg) return rcg;
     }
     if (out_location == FFTCONV_HOST) HIP_TRY(hipStreamSynchronize(p->stream));
-    extrema_end(p, n_kernel);
+    outputs_end(p, n_kernel);
     return 0;
 }
 
@@ -934,6 +967,68 @@ int fftconv_plan_extrema_device(fftconv_plan* plan, void** device_ptr, size_t* b
     if (!plan->extrema_on()) return api_fail(FFTCONV_ERR_INVALID_ARG, "per-map extrema are off (fftconv_plan_set_extrema)");
     *device_ptr = plan->EXR.p;
     *bytes = (size_t)plan->extrema_max_maps * sizeof(ExtremaRecord);
+    return 0;
+}
+
+int fftconv_plan_set_peaks(fftconv_plan* plan, int mode, int max_maps, int max_peaks, float threshold, int radius_h, int radius_w) {
+    if (!plan) return api_fail(FFTCONV_ERR_INVALID_ARG, "plan is NULL");
+    if (mode < FC_PEAKS_OFF || mode > FC_PEAKS_MIN) return api_fail(FFTCONV_ERR_INVALID_ARG, "peak lists: mode is 0 (off), 1 (maxima) or 2 (minima), not %d", mode);
+    if (mode != FC_PEAKS_OFF) {
+        if (max_maps < 1) return api_fail(FFTCONV_ERR_INVALID_ARG, "peak lists: max_maps must be at least 1 (%d asked)", max_maps);
+        if (max_peaks < 1) return api_fail(FFTCONV_ERR_INVALID_ARG, "peak lists: max_peaks must be at least 1 (%d asked)", max_peaks);
+        if (threshold != threshold) return api_fail(FFTCONV_ERR_INVALID_ARG, "peak lists: the threshold is NaN (-inf takes every element)");
+        if (radius_h < 0 || radius_w < 0) return api_fail(FFTCONV_ERR_INVALID_ARG, "peak lists: a radius cannot be negative (%d, %d asked)", radius_h, radius_w);
+    }
+    if (int rc = plan_refused(plan, AskPeaks::Peaks, mode)) return rc;
+    if (mode == FC_PEAKS_OFF) { max_maps = max_peaks = radius_h = radius_w = 0; threshold = 0.0f; }
+    const bool same_size = plan->peaks_max_maps == max_maps && plan->peaks_max == max_peaks;
+    // (bits, not ==: a threshold of -0 after +0 is a change like any other)
+    const bool same_rule = plan->peaks_mode == mode && fc_float_bits(plan->peaks_threshold) == fc_float_bits(threshold) && plan->peaks_radius_h == radius_h &&
+                           plan->peaks_radius_w == radius_w;
+    int rc;
+    if (setter_done(plan, SetterPeaks::Peaks, same_size && same_rule, rc)) return rc;
+    // (output-side state alone: the image, the prepared kernels, the stream and the extent stay)
+    if (!same_size) {      // threshold, radius or mode alone: uniforms of the launches, the buffers stay
+        plan->PKF.release(); plan->PKS.release(); plan->PKR.release();
+        plan->peaks_mode = plan->peaks_max_maps = plan->peaks_max = plan->peaks_launch_maps = 0;
+        plan->peaks_maps = -1;
+        if (mode != FC_PEAKS_OFF) {
+            // the scratch of one launch: the maps of a launch as fftconv_plan_set_extrema bounds them, the units of the largest map
+            const int launch_maps = (int)std::min<long>(max_maps, plan->opt_batch_maps > 0 ? plan->opt_batch_maps : 64);
+            int rce = plan->PKF.ensure((size_t)max_maps);
+            if (!rce) rce = plan->PKR.ensure((size_t)max_maps * (size_t)max_peaks);
+            if (!rce) rce = plan->PKS.ensure((size_t)2 * FC_PEAKS_MAX_UNITS * launch_maps);
+            if (rce) { plan->PKF.release(); plan->PKS.release(); plan->PKR.release(); return rce; }
+            plan->peaks_max_maps = max_maps; plan->peaks_max = max_peaks; plan->peaks_launch_maps = launch_maps;
+        }
+    }
+    if (!same_rule) plan->peaks_maps = -1;      // (the lists of the last convolve belong to the rule it ran under)
+    plan->peaks_mode = mode; plan->peaks_threshold = threshold; plan->peaks_radius_h = radius_h; plan->peaks_radius_w = radius_w;
+    return 0;
+}
+
+int fftconv_plan_get_peaks(fftconv_plan* plan, int first_map, int n_maps, int* found_host, fftconv_peak* peaks_host) {
+    if (!plan || !found_host || !peaks_host) return api_fail(FFTCONV_ERR_INVALID_ARG, "NULL argument");
+    if (!plan->peaks_on()) return api_fail(FFTCONV_ERR_INVALID_ARG, "peak lists are off (fftconv_plan_set_peaks)");
+    if (plan->peaks_maps < 0) return api_fail(FFTCONV_ERR_INVALID_ARG, "peak lists: no convolve has run since fftconv_plan_set_peaks");
+    if (first_map < 0 || n_maps < 0 || (long)first_map + n_maps > plan->peaks_maps)
+        return api_fail(FFTCONV_ERR_INVALID_ARG, "peak lists: maps [%d, %d) asked, the last convolve wrote %d", first_map, first_map + n_maps, plan->peaks_maps);
+    if (n_maps == 0) return 0;
+    if (int rc = use_device(plan)) return rc;
+    static_assert(sizeof(fftconv_peak) == sizeof(PeakRecord) && sizeof(PeakRecord) == 20, "the record the kernels write is the caller's");
+    HIP_TRY(hipMemcpyAsync(found_host, plan->PKF.p + first_map, (size_t)n_maps * sizeof(int), hipMemcpyDeviceToHost, plan->stream));
+    HIP_TRY(hipMemcpyAsync(peaks_host, plan->PKR.p + (size_t)first_map * plan->peaks_max, (size_t)n_maps * plan->peaks_max * sizeof(PeakRecord), hipMemcpyDeviceToHost,
+                           plan->stream));
+    HIP_TRY(hipStreamSynchronize(plan->stream));
+    return 0;
+}
+
+int fftconv_plan_peaks_device(fftconv_plan* plan, void** found_device, void** peaks_device, size_t* peaks_bytes) {
+    if (!plan || !found_device || !peaks_device || !peaks_bytes) return api_fail(FFTCONV_ERR_INVALID_ARG, "NULL argument");
+    if (!plan->peaks_on()) return api_fail(FFTCONV_ERR_INVALID_ARG, "peak lists are off (fftconv_plan_set_peaks)");
+    *found_device = plan->PKF.p;
+    *peaks_device = plan->PKR.p;
+    *peaks_bytes = (size_t)plan->peaks_max_maps * plan->peaks_max * sizeof(PeakRecord);
     return 0;
 }
 

@@ -6,6 +6,7 @@
 
 #include "fast_paths.hpp"
 #include "kernels_body.hpp"
+#include "peaks.hpp"
 
 namespace fc {
 
@@ -116,6 +117,11 @@ hipError_t launch_fast_cols_rect_extrema(int M, int T, const FastColsShape& shap
 hipError_t launch_extrema_scan(const void* maps, size_t map_elems, size_t map_stride, int format, int nmaps, ExtremaPartial* partials, hipStream_t s);
 // the fold: records[m] = the record of the per_map partials of map m (maps of out_h rows per column), m < nmaps
 hipError_t launch_extrema_fold(const ExtremaPartial* partials, int per_map, int nmaps, int out_h, ExtremaRecord* records, hipStream_t s);
+// ---- peak lists (kernels_peaks.hip; peaks.hpp)
+// nmaps dense maps as launch_extrema_scan takes them, of out_h rows per column: found[m] = the peaks of map m under `rule`, all of them;
+// peaks[m * max_peaks ...] the first min(found[m], max_peaks) in ascending index order.  scratch: 2 * peaks_units(map bytes) ints per map
+hipError_t launch_peaks(const void* maps, size_t map_elems, size_t map_stride, int format, int out_h, int nmaps, const PeakRule& rule, int max_peaks, int* scratch,
+                        int* found, PeakRecord* peaks, hipStream_t s);
 hipError_t launch_fast_cols_fwd(int M, int T, bool pruned, const FastColsFwdArgs& a, int num_cus, hipStream_t s);
 // image columns of typed pixels (kernels_cols_fwd_px_g<G>.hip; pixel_format.hpp): a.in holds elements of px.format, px from
 // fast_cols_fwd_pixel_load; hipErrorInvalidValue for fp32 pixels and for a configuration that is not built (fast_cols_fwd_px_built)

@@ -351,6 +351,17 @@ struct fftconv_plan {
     bool extrema_on() const { return extrema_max_maps > 0; }
     // read-only option "extrema_direct": whether the route of a sink that is not a window finds them in the store
     bool extrema_direct() const { return plan_output_route(output_route_in(this, SinkKind::Packed)).extrema == OutExtrema::Fused; }
+    // fftconv_plan_set_peaks (peaks.hpp): the thresholded local maxima of every delivered map.  peaks_mode != 0 while it is on: PKF holds
+    // peaks_max_maps counts and PKR peaks_max_maps x peaks_max records (map m of the last convolve: found[m], and its first
+    // min(found[m], peaks_max) peaks from m * peaks_max on), PKS the unit counts and offsets of ONE launch -- 2 x FC_PEAKS_MAX_UNITS ints
+    // per map, times peaks_launch_maps, the maps of a launch as the extrema setter bounds them -- all sized by the setter, never by a
+    // convolve.  Threshold, radii and mode are uniforms of the launches: changing them alone keeps the buffers.  peaks_maps: the maps of
+    // the last convolve under it (-1: none yet).
+    int peaks_mode = 0, peaks_max_maps = 0, peaks_max = 0, peaks_launch_maps = 0, peaks_radius_h = 0, peaks_radius_w = 0, peaks_maps = -1;
+    float peaks_threshold = 0.0f;
+    DevBuf<int> PKF, PKS;
+    DevBuf<PeakRecord> PKR;
+    bool peaks_on() const { return peaks_mode != 0; }
     DevBuf<float> O;   // output staging (pointer-array / host output)
     DevBuf<float> I;   // image staging (host input)
     // Typed image pixels (fftconv_plan_set_images_typed; pixel_format.hpp).  "pixel_store" 1: the image's forward column kernel
@@ -465,7 +476,7 @@ struct fftconv_plan {
         fr_tw1.release(); fr_tw2.release(); fr_map.release();
         fc_tw1.release(); fc_tw2.release(); fc_pairs.release(); fc_rowoff.release(); fc_pair_row_of.release();
         nat_row_of.release(); nat_col_of.release(); NS.release(); queue.release();
-        ND.release(); KN.release(); KC.release(); NS64.release(); EXR.release(); EXP.release();
+        ND.release(); KN.release(); KC.release(); NS64.release(); EXR.release(); EXP.release(); PKF.release(); PKS.release(); PKR.release();
         pin_img.release(); pin_k.release(); pin_out.release();
         for (int h = 0; h < 2; h++) { if (pin_out_done[h]) (void)hipEventDestroy(pin_out_done[h]); pin_out_done[h] = nullptr; }
     }
@@ -547,6 +558,8 @@ int launch_output_cols(fftconv_plan* p, const OutputRoute& r, const OutWindow* w
 // per-map extrema of the ny delivered maps at `dest` (dense, in the route's map format), behind the last kernel that writes them and
 // ahead of any copy-out: the fold of the partials the fused store wrote (r.extrema Fused), or the scan and its fold (Scan)
 int launch_extrema(fftconv_plan* p, const OutputRoute& r, const float* dest, int ny, const OutLaunch& l);
+// the peak lists of the same maps (fftconv_plan_set_peaks), behind launch_extrema: found and records [l.record0, l.record0 + ny)
+int launch_peaks_scan(fftconv_plan* p, const OutputRoute& r, const float* dest, int ny, const OutLaunch& l);
 // r.after: nmaps full fp32 windows at src cropped (padded) into dst and combined with the route's plane on the way
 int launch_region(const fftconv_plan* p, const OutputRoute& r, const float* src, float* dst, int nmaps, hipStream_t s, const OutLaunch& l = {});
 // the maps [first, first + ny) are queued into `dest` (staging buffer buf of a streamed group): their way to the caller
@@ -625,6 +638,14 @@ inline int plan_refused(const fftconv_plan* p, AskOutput ask, long value, bool w
     s.blocks = p->tiled ? p->tiled->nblk : 0;
     s.window_sink = window_sink;
     const OutputRefusal r = plan_refusal(s, ask, value);
+    return r ? api_fail(r.rule->code, r.rule->fmt, r.arg) : 0;
+}
+// ... of the peak lists' table
+inline int plan_refused(const fftconv_plan* p, AskPeaks ask, long value, bool window_sink = false) {
+    PlanRuleState s;
+    s.blocks = p->tiled ? p->tiled->nblk : 0;
+    s.window_sink = window_sink;
+    const PeaksRefusal r = plan_refusal(s, ask, value);
     return r ? api_fail(r.rule->code, r.rule->fmt, r.arg) : 0;
 }
 }  // namespace fc

@@ -70,6 +70,10 @@ int plan_delivery(fftconv_plan* p, const Sink& sink, int nbY, Delivery& d) {
     else if (d.r.extrema == OutExtrema::Scan)
         FC_VERBOSE(p, "extrema: scanned -- the %s maps of %zu elements are read where they lie, %d blocks per map, folded per launch", kMapFormatNames[d.r.map_format],
                    d.oe, extrema_scan_blocks(d.oe * d.eb));
+    if (p->peaks_on())
+        FC_VERBOSE(p, "peaks: scanned -- the %s maps of %zu elements are read where they lie, %d units per map, %s at threshold %g, radius (%d, %d), at most %d per map",
+                   kMapFormatNames[d.r.map_format], d.oe, peaks_units(d.oe * d.eb), p->peaks_mode == FC_PEAKS_MIN ? "minima" : "maxima", (double)p->peaks_threshold,
+                   p->peaks_radius_h, p->peaks_radius_w, p->peaks_max);
     if (d.r.route == Route::Ring) return ring_begin(p);
     return 0;
 }
@@ -156,6 +160,19 @@ int launch_extrema(fftconv_plan* p, const OutputRoute& r, const float* dest, int
         HIP_TRY(launch_extrema_scan(dest, oe, oe, r.map_format, ny, p->EXP.p, p->stream));
     }
     HIP_TRY(launch_extrema_fold(p->EXP.p, per_map, ny, out_h, p->EXR.p + l.record0, p->stream));
+    return 0;
+}
+
+// peak lists of a launch's delivered maps: found and records [l.record0, l.record0 + ny), always by the scan of the maps where they lie
+int launch_peaks_scan(fftconv_plan* p, const OutputRoute& r, const float* dest, int ny, const OutLaunch& l) {
+    if (!p->peaks_on()) return 0;
+    const size_t oe = p->out_elems();
+    const int out_h = r.after == OutAfter::Pad ? p->out_h : p->map_h();      // rows per column of a delivered map
+    if (l.record0 < 0 || (long)l.record0 + ny > (long)p->peaks_max_maps || ny > p->peaks_launch_maps)
+        return api_fail(FFTCONV_ERR_INVALID_ARG, "peak lists: records %d..%d in a launch of %d maps asked of a plan that holds %d lists and the scratch of %d maps "
+                        "(fftconv_plan_set_peaks sizes them for the \"batch_maps\" of its time)", l.record0, l.record0 + ny - 1, ny, p->peaks_max_maps, p->peaks_launch_maps);
+    const PeakRule rule = peak_rule(p->peaks_mode, p->peaks_threshold, p->peaks_radius_h, p->peaks_radius_w);
+    HIP_TRY(launch_peaks(dest, oe, oe, r.map_format, out_h, ny, rule, p->peaks_max, p->PKS.p, p->PKF.p + l.record0, p->PKR.p + (size_t)l.record0 * p->peaks_max, p->stream));
     return 0;
 }
 

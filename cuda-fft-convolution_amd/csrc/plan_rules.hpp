@@ -148,6 +148,37 @@ constexpr OutputRule kOutputRules[] = {
      "per-map extrema are on (fftconv_plan_set_extrema): an output window holds a part of a map (%ld), not a delivered map"},
 };
 
+// ---- the output side: peak lists (fftconv_plan_set_peaks) ----
+// Tables of their own again, for the same reason: tests/extrema_host counts the rows of the two tables above.  The rows are the extrema
+// rows' in effect and in wording -- output-side state of its own, FX_WAIT because launches in flight write the lists a change
+// reallocates, an early return for a call that changes nothing; refused on a block-wise plan and for a group whose sink is a window.
+enum class SetterPeaks { Peaks };
+struct PeaksSetterEffects {
+    SetterPeaks setter;
+    unsigned changed;
+    bool unchanged_returns;
+};
+constexpr PeaksSetterEffects kSetterEffectsPeaks[] = {
+    {SetterPeaks::Peaks, FX_WAIT, true},      // fftconv_plan_set_peaks: the effects the extrema setter has
+};
+constexpr const PeaksSetterEffects& setter_effects(SetterPeaks s) { return kSetterEffectsPeaks[(int)s]; }
+
+enum class AskPeaks { Peaks, PeaksGroup };
+struct PeaksRule {
+    AskPeaks ask;
+    Holds holds;
+    bool off_too;
+    int code;
+    const char* fmt;
+};
+constexpr PeaksRule kPeaksRules[] = {
+    {AskPeaks::Peaks, Holds::Blockwise, false, FFTCONV_ERR_INVALID_ARG,
+     "peak lists are not available on a block-wise plan (%ld blocks: its maps are stored through output windows block by block); create a "
+     "one-pass plan (fftconv_plan_options.blockwise = 1)"},
+    {AskPeaks::PeaksGroup, Holds::WindowSink, true, FFTCONV_ERR_INVALID_ARG,
+     "peak lists are on (fftconv_plan_set_peaks): an output window holds a part of a map (%ld), not a delivered map"},
+};
+
 struct Refusal {
     const PlanRule* rule = nullptr;      // nullptr: the request passes
     long arg = 0;                        // what rule->fmt formats
@@ -168,6 +199,18 @@ struct OutputRefusal {
 };
 inline OutputRefusal plan_refusal(const PlanRuleState& s, AskOutput ask, long value) {
     for (const OutputRule& r : kOutputRules) {
+        if (r.ask != ask || (value == 0 && !r.off_too)) continue;
+        if (const long arg = holds_value(s, r.holds)) return {&r, arg};
+    }
+    return {};
+}
+struct PeaksRefusal {
+    const PeaksRule* rule = nullptr;
+    long arg = 0;
+    explicit operator bool() const { return rule != nullptr; }
+};
+inline PeaksRefusal plan_refusal(const PlanRuleState& s, AskPeaks ask, long value) {
+    for (const PeaksRule& r : kPeaksRules) {
         if (r.ask != ask || (value == 0 && !r.off_too)) continue;
         if (const long arg = holds_value(s, r.holds)) return {&r, arg};
     }

@@ -534,6 +534,59 @@ typedef struct { float max_value; int max_row, max_col; float min_value; int min
 int fftconv_plan_set_extrema(fftconv_plan *plan, int mode, int max_maps);   /* mode 0 off, 1 on */
 int fftconv_plan_get_extrema(fftconv_plan *plan, int first_map, int n_maps, fftconv_extrema *out_host);
 int fftconv_plan_extrema_device(fftconv_plan *plan, void **device_ptr, size_t *bytes);
+/* Peak lists: the thresholded local maxima of every delivered map, found on the device behind the kernel that writes the maps -- what a
+ * matcher that looks for more than one instance does with a score map (threshold, non-maximum suppression, a list of (row, col,
+ * score)), and what a registration caller does around the peak of a phase correlation (the shift to a fraction of a pixel), without
+ * reading the maps again.  The maps themselves are written exactly as without this entry.
+ *   Modes.  0 off.  1 maxima at or above `threshold` (CCOEFF_NORMED, CCORR_NORMED, phase correlation).  2 minima at or below
+ *     `threshold` (SQDIFF): mode 1 on the negated values with the negated threshold; the record carries the element's own value.
+ *   The element.  (value, index), index = col * out_h + row of the delivered map -- the map as the caller receives it: the window, an
+ *     "output_region" 1-4, a rectangle, a strided map, a border's "same" map.  For 16-bit maps the value is the exact fp32 of the
+ *     rounded element.  `row` is the fast index.
+ *   A peak (mode 1).  An element v at (r, c) with v >= threshold that no other element of its neighbourhood beats; the neighbourhood is
+ *     rows r +- radius_h and columns c +- radius_w, clipped to the map.  The compare is ordered: a NaN is never a peak and never
+ *     beats anything.  "Beats" is the tie rule of the extrema: a larger value, or an equal value at a smaller index; +0 and -0
+ *     compare equal.  A plateau of equal values therefore yields exactly one peak per neighbourhood chain -- an all-equal map with a
+ *     radius >= 1 has one peak, at index 0.  With radius (0, 0) every element that meets the threshold is a peak: plain thresholding.
+ *   Sub-pixel offsets.  d_row and d_col are a three-point parabola per dimension, computed in float64 from the exact element values
+ *     and rounded to fp32 once: along rows a = U[r-1, c], b = U[r+1, c], den = (a - v) + (b - v), d = 0.5 * (a - b) / den, clamped to
+ *     [-0.5, 0.5]; 0 where the neighbour pair does not exist (a map edge), where a, b or v is not finite, where den == 0, and where
+ *     the radius of that dimension is 0.  Columns likewise.  The peak lies at (row + d_row, col + d_col).
+ *   What a convolve leaves.  Per delivered map m (image-major, numbered as the extrema records are): found[m], the number of peaks of
+ *     the map, all of them; the first min(found[m], max_peaks) peaks in ascending index order (memory order) from
+ *     peaks[m * max_peaks] on.  Records beyond that are undefined; nothing is cleared.  Overflow is not an error: the caller sees
+ *     found[m] > max_peaks and raises the threshold.
+ *   No atomics.  The lists are a pure function of the maps: two runs, both tile deals ("dynamic_tiles") and every delivery route give
+ *     identical bytes.
+ *   Allocation.  The setter sizes found, peaks and every scratch of a launch, for convolves of up to max_maps maps; a convolve of more
+ *     maps is refused with FFTCONV_ERR_INVALID_ARG and leaves the plan usable.  A convolve under it allocates nothing, does not
+ *     wait for the host and can be captured into a graph.  A change of threshold, radius or mode alone keeps the buffers (it
+ *     synchronises the plan's stream, and the lists of the last convolve are no longer readable: they belong to the rule they were
+ *     found under).
+ *   Reading.  fftconv_plan_get_peaks waits for the plan's stream and copies found[first_map .. first_map + n_maps) to found_host and
+ *     the n_maps * max_peaks records to peaks_host (map m's start at (m - first_map) * max_peaks); before any convolve under peaks,
+ *     and for a range beyond the maps of the last one, it fails with FFTCONV_ERR_INVALID_ARG.  fftconv_plan_peaks_device gives the
+ *     device arrays (max_maps ints; max_maps * max_peaks records and their size in bytes): stable until the next call that changes
+ *     max_maps or max_peaks or switches the lists off, their content ordered on the plan's stream.
+ *   State.  Output-side state of its own, beside the stride and the extrema, and independent of the extrema (both may be on): it
+ *     keeps the image, the prepared kernels, the stream and the extent, and it stays while format, score, extent or images change; a
+ *     call that changes nothing returns early.
+ *   Refusals (FFTCONV_ERR_INVALID_ARG, the plan's state untouched): a mode outside 0..2; with a mode on, max_maps < 1, max_peaks < 1, a
+ *     NaN threshold (+-inf are allowed), a negative radius (a radius larger than the map is simply clipped); a mode on on a
+ *     block-wise plan, whose maps are stored through output windows block by block.
+ *   Cost.  Three small launches behind every output launch: a pass that reads the delivered maps once more where they lie (4P' bytes
+ *     per map of P' elements, 2P' for 16-bit maps) and walks the neighbourhood of the elements that meet the threshold alone; a scan
+ *     of the per-wave counts; a pass that re-reads the runs that hold peaks.  A threshold of -inf with a large radius makes every
+ *     element a candidate: the cost then grows with P' * (2 radius_h + 1) * (2 radius_w + 1).  That is the caller's choice and is
+ *     not optimised.
+ * Read-only options: "peaks" (the mode), "peaks_max_maps", "peaks_max", "peaks_radius_h", "peaks_radius_w", "peaks_maps" (the maps of
+ * the last convolve under it; -1 before any).  There is no creation option.  The one-shot, two-step, fftconv_multi_*, plan-cache
+ * and MEX entries do not take it. */
+typedef struct { float value; int row, col; float d_row, d_col; } fftconv_peak;   /* 20 bytes */
+int fftconv_plan_set_peaks(fftconv_plan *plan, int mode, int max_maps, int max_peaks,
+                           float threshold, int radius_h, int radius_w);
+int fftconv_plan_get_peaks(fftconv_plan *plan, int first_map, int n_maps, int *found_host, fftconv_peak *peaks_host);
+int fftconv_plan_peaks_device(fftconv_plan *plan, void **found_device, void **peaks_device, size_t *peaks_bytes);
 /* Normalised cross-correlation maps.  mode 0 (default): the maps are the raw sums of products, bit for bit what they are
  * without this entry.  mode 1: every map is the zero-mean normalised cross-correlation (MATLAB's normxcorr2, OpenCV's
  * TM_CCOEFF_NORMED) over the box box_h x box_w, n = box_h * box_w: in [-1, 1], 1 at a perfect match, invariant to gain and
